@@ -17,8 +17,15 @@ gather), issued asynchronously so it overlaps the next step's compute.  W
 untimed warmup steps, then exactly K steps bracketed by barrier + synchronize;
 the MAX over ranks is reported.
 
-After the headline, the secondary BASELINE configurations are measured the same
-way and added to the SAME JSON line (``extras``; a failure in an extra's untimed
+A plain run measures the headline alone: set-up, W warmup steps, the K timed
+steps, the ``--dump-outputs`` arrays if asked for, and the JSON line.
+``--dump-outputs DIR`` writes what the last timed step returned to its caller
+as ``DIR/<name>.npy`` (float32; inputs and weights are seeded, so two builds
+can be compared output for output): ``flow_final`` is the final iteration's
+flows, ``flows_sample`` a fixed, seeded sample of all iterations' flows.
+
+With ``--full``, the secondary BASELINE configurations are measured after the
+headline, the same way, and added to the SAME JSON line (``extras``; a failure in an extra's untimed
 set-up gives ``null`` on every rank without losing the headline): raft_large batch
 1 as a pipelined stream (``b1_fps``) and with the reference's synchronous per-pair
 protocol (``b1_sync``: H2D + forward + sync, 1 / mean latency,
@@ -172,12 +179,38 @@ def agree(ctx: Ctx, ok: bool, what: str) -> None:
         raise ExtraFailed(what)
 
 
+DUMP_FINAL_MAX = 1 << 23    # elements: 32 MiB of float32 (the headline's final flows are 3.6 M elements)
+DUMP_SAMPLE = 1 << 22       # elements of the sample of all iterations' flows (16 MiB of float32)
+
+
+def dump_outputs(out: torch.Tensor, dump_dir: str) -> None:
+    """``--dump-outputs``: the flows (iterations, B, H, W, 2) a timed step returned, as float32
+    ``.npy`` files: the final iteration's flows (``flow_final``: what a caller uses; whole up to
+    DUMP_FINAL_MAX elements), and of all iterations' flows -- 461 MB at the headline size -- a
+    sample of DUMP_SAMPLE elements (``flows_sample``).  A sample is the elements at flat
+    positions drawn with a seeded generator: the same positions for every run of one
+    configuration.  An array no larger than its limit is written whole."""
+    import numpy as np
+
+    def sampled(t, limit, seed):
+        flat = t.detach().reshape(-1)
+        if flat.numel() <= limit:
+            return t.detach().float().cpu().numpy()
+        idx = torch.randint(0, flat.numel(), (limit,), generator=torch.Generator().manual_seed(seed))
+        return flat[idx.to(flat.device)].float().cpu().numpy()
+
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "flow_final.npy"), sampled(out[-1], DUMP_FINAL_MAX, 4321))
+    np.save(os.path.join(dump_dir, "flows_sample.npy"), sampled(out, DUMP_SAMPLE, 4322))
+
+
 def run_inference(ctx: Ctx, model, *, B: int, H: int, W: int, iters: int, steps: int, warmup: int,
                   final_only: bool, gather: bool, seed: int, engine_kw: dict, pipeline: str = "auto",
-                  h2d: bool = True, sync_h2d: bool = False, guarded: bool = False) -> dict:
+                  h2d: bool = True, sync_h2d: bool = False, guarded: bool = False, dump_dir: str = "") -> dict:
     """Time ``steps`` inference steps of ``B`` pairs per rank; returns the run record.
     ``guarded``: the untimed part (engine, plan build, warmup: no collectives) may fail on
-    one rank; the ranks then agree on the failure before any collective (:func:`agree`)."""
+    one rank; the ranks then agree on the failure before any collective (:func:`agree`).
+    ``dump_dir``: rank 0 writes the last timed step's output there (:func:`dump_outputs`)."""
     from jax_raft_amd.runtime.pipeline import InputPrefetcher
 
     dev = ctx.dev
@@ -244,12 +277,16 @@ def run_inference(ctx: Ctx, model, *, B: int, H: int, W: int, iters: int, steps:
     ctx.barrier()
     t0 = time.perf_counter()
     events[0].record()
-    run(steps, events)
+    last = run(steps, events)
     if gat is not None:
         gat.drain()
     torch.cuda.synchronize(dev)
     t1 = time.perf_counter()
     ctx.barrier()
+    if dump_dir and ctx.rank == 0:
+        if last is None:
+            raise RuntimeError("--dump-outputs: the timed steps returned no output")
+        dump_outputs(last, dump_dir)
     if copipe:
         eng.flush()   # the last prologue's batch (untimed)
         torch.cuda.synchronize(dev)
@@ -419,8 +456,15 @@ def main():
                          "raft_small, final-only; measured faster there) else off; 'graph' = each step replays ONE "
                          "hipGraph holding batch i's refinement loop and batch i+1's encoders + correlation pyramid")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the RCCL gather of the final flows")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last timed step's output (rank 0's) to DIR/<name>.npy: "
+                         "flow_final (the final flows) and flows_sample (a seeded sample of all iterations' flows)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the secondary configs (extras: other batch sizes, "
+                         "protocols, precisions, sizes, training); a plain run measures the headline only")
     ap.add_argument("--extras", default="auto", choices=["auto", "on", "off"],
-                    help="secondary configs after the headline (auto: on for the default headline config)")
+                    help="with --full: which headline configs get the extras (auto: the default one; on: any; "
+                         "off: none)")
     ap.add_argument("--extra-steps", type=int, default=20)
     ap.add_argument("--step-times", action="store_true", help="print every timed step's device time (stderr)")
     ap.add_argument("--skip-extras", default="", help="comma list of extras to leave out (diagnostics)")
@@ -432,6 +476,10 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL on ROCm) for real runs; gloo only to rehearse >1 rank on fewer GPUs")
     args = ap.parse_args()
+    if args.extras == "on" and not args.full:
+        ap.error("--extras on needs --full (a plain run measures the headline only)")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `bench.py --gpus N` without a launcher: start torch.distributed.run as a
@@ -458,7 +506,8 @@ def main():
     else:
         head = run_inference(ctx, model, B=B, H=H, W=W, iters=args.iters, steps=args.steps, warmup=args.warmup,
                              final_only=args.final_only, gather=not args.no_gather, seed=1234, engine_kw=engine_kw,
-                             pipeline=args.pipeline, h2d=not args.no_h2d, sync_h2d=args.sync_h2d)
+                             pipeline=args.pipeline, h2d=not args.no_h2d, sync_h2d=args.sync_h2d,
+                             dump_dir=args.dump_outputs)
         rccl_world = ctx.world_check()
     del model
     torch.cuda.empty_cache()
@@ -466,7 +515,7 @@ def main():
     default_cfg = (args.arch == "raft_large" and (B, H, W, args.iters) == (4, 440, 1024, 32) and not args.final_only
                    and not args.no_graph and args.precision == "bf16")
     extras = {}
-    if args.extras == "on" or (args.extras == "auto" and default_cfg) or args.only_extra:
+    if (args.full and (args.extras == "on" or (args.extras == "auto" and default_cfg))) or args.only_extra:
         t_ex = time.perf_counter()
         ks, kw_ = args.extra_steps, max(3, args.warmup)
         # *_b1_fps: batch-1 stream throughput (graph-pipelined: pair i's loop overlaps pair i+1's

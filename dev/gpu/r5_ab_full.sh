@@ -9,7 +9,7 @@ mkdir -p $o
 for v in base new base new; do
   so=""; [ $v = base ] && so=$PWD/dev/bin/_C_base.so
   i=$(ls $o | grep -c "^bench_$v")
-  JR_NATIVE_SO=$so timeout -k 10 900 python -u bench.py > $o/bench_${v}_$i.json 2> $o/bench_${v}_$i.err || { tail $o/bench_${v}_$i.err; exit 1; }
+  JR_NATIVE_SO=$so timeout -k 10 900 python -u bench.py --full > $o/bench_${v}_$i.json 2> $o/bench_${v}_$i.err || { tail $o/bench_${v}_$i.err; exit 1; }
   python -c "
 import json; d=json.load(open('$o/bench_${v}_$i.json'))
 print('$v', 'headline', d['value'], ' '.join(f'{k}={v[\"value\"] if isinstance(v, dict) else v}' for k, v in d.get('extras', {}).items()))

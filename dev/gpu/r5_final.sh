@@ -9,7 +9,7 @@ timeout -k 10 1500 python -u -m pytest tests/ -x -q -m gpu --timeout 600 --timeo
 tail -2 $o/gpu_tests.txt
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.txt 2>&1 || { tail $o/smoke.txt; exit 1; }
 tail -1 $o/smoke.txt
-timeout -k 10 900 python -u bench.py > $o/bench.json 2> $o/bench.err || { tail $o/bench.err; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $o/bench.json 2> $o/bench.err || { tail $o/bench.err; exit 1; }
 python -c "
 import json; d=json.load(open('$o/bench.json'))
 print('headline', d['value'], d['ms_per_step'])

@@ -10,7 +10,7 @@ timeout -k 10 900 python -u -m pytest tests/test_engine_gpu.py tests/test_input_
 tail -1 $o/tests.txt
 timeout -k 10 900 python -u tools/autotune_db.py --out $o/gfx950.json > $o/tune.log 2>&1 || { tail -20 $o/tune.log; exit 1; }
 tail -1 $o/tune.log
-JR_TUNE_DB=$PWD/$o/gfx950.json timeout -k 10 900 python -u bench.py > $o/bench.json 2> $o/bench.err || { tail $o/bench.err; exit 1; }
+JR_TUNE_DB=$PWD/$o/gfx950.json timeout -k 10 900 python -u bench.py --full > $o/bench.json 2> $o/bench.err || { tail $o/bench.err; exit 1; }
 python -c "
 import json; d=json.load(open('$o/bench.json'))
 print('headline', d['value'], d['ms_per_step'], ' '.join(f'{k}={v[\"value\"] if isinstance(v, dict) else v}' for k, v in (d.get('extras') or {}).items()))

@@ -8,7 +8,7 @@ mkdir -p $o
 SK=fp32_b1_fps,hires_b1,small_b1_sync_32it_mixed
 for r in 1 2; do
   for v in 1 0; do
-    timeout -k 10 600 python -u dev/probes/bench_with.py CORR_PERSIST_B1=$v -- --steps 3 --warmup 2 --extras on --skip-extras $SK > $o/b_$v.json 2> $o/b_$v.err || { tail $o/b_$v.err; exit 1; }
+    timeout -k 10 600 python -u dev/probes/bench_with.py CORR_PERSIST_B1=$v -- --steps 3 --warmup 2 --full --extras on --skip-extras $SK > $o/b_$v.json 2> $o/b_$v.err || { tail $o/b_$v.err; exit 1; }
     python -c "
 import json; d=json.load(open('$o/b_$v.json'))
 ex=d.get('extras',{})

@@ -16,7 +16,7 @@ PY
 ALL=train_pairs_per_s
 for r in 1 2; do
   for v in 0 1; do
-    timeout -k 10 600 python -u dev/probes/bench_with.py CE_LANE_B1=$v -- --skip-extras fp32_b1_fps,hires_b1,small_b1_sync_32it_mixed > $o/f_$v.json 2> $o/f_$v.err || { tail $o/f_$v.err; exit 1; }
+    timeout -k 10 600 python -u dev/probes/bench_with.py CE_LANE_B1=$v -- --full --skip-extras fp32_b1_fps,hires_b1,small_b1_sync_32it_mixed > $o/f_$v.json 2> $o/f_$v.err || { tail $o/f_$v.err; exit 1; }
     echo "r$r CE_LANE_B1=$v $(summ $o/f_$v.json)"
   done
 done

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 export PYTHONPATH=$PWD${PYTHONPATH:+:$PYTHONPATH}
 o=gpurun_out/${OUT:-r6_extra_standalone}
 mkdir -p $o
-timeout -k 10 700 python -u bench.py > $o/full.json 2> $o/full.err || { tail $o/full.err; exit 1; }
+timeout -k 10 700 python -u bench.py --full > $o/full.json 2> $o/full.err || { tail $o/full.err; exit 1; }
 python - $o/full.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

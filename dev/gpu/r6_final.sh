@@ -8,7 +8,7 @@ mkdir -p $o
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.txt 2>&1 || { tail -20 $o/smoke.txt; exit 1; }
 tail -1 $o/smoke.txt
 for r in 1 2; do
-  timeout -k 10 700 python -u bench.py > $o/bench_$r.json 2> $o/bench_$r.err || { tail $o/bench_$r.err; exit 1; }
+  timeout -k 10 700 python -u bench.py --full > $o/bench_$r.json 2> $o/bench_$r.err || { tail $o/bench_$r.err; exit 1; }
   python - $o/bench_$r.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

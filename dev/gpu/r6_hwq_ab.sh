@@ -14,7 +14,7 @@ PY
 }
 for q in 4 8; do
   for v in auto off; do
-    GPU_MAX_HW_QUEUES=$q timeout -k 10 600 python -u dev/probes/bench_with.py PRO_LANES=$v -- > $o/q${q}_$v.json 2> $o/q${q}_$v.err || { tail $o/q${q}_$v.err; exit 1; }
+    GPU_MAX_HW_QUEUES=$q timeout -k 10 600 python -u dev/probes/bench_with.py PRO_LANES=$v -- --full > $o/q${q}_$v.json 2> $o/q${q}_$v.err || { tail $o/q${q}_$v.err; exit 1; }
     echo "hwq=$q PRO_LANES=$v $(summ $o/q${q}_$v.json)"
   done
 done

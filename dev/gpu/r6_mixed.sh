@@ -13,7 +13,7 @@ timeout -k 10 600 python -u tools/drift.py measure --arch raft_small raft_large 
 cat $o/drift.txt
 timeout -k 10 300 python -u -m pytest tests/test_drift.py -x -q -m gpu --timeout 250 --timeout-method thread > $o/drift_tests.txt 2>&1 || { tail -30 $o/drift_tests.txt; exit 1; }
 tail -1 $o/drift_tests.txt
-timeout -k 10 900 python -u bench.py > $o/bench.json 2> $o/bench.err || { tail $o/bench.err; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $o/bench.json 2> $o/bench.err || { tail $o/bench.err; exit 1; }
 python -c "
 import json; d=json.load(open('$o/bench.json'))
 print('headline', d['value'], d['ms_per_step'])

@@ -13,7 +13,7 @@ print(round(d["value"], 1), " ".join(f"{k}={v['value']}" for k, v in ex.items() 
 PY
 }
 for v in off auto; do
-  timeout -k 10 600 python -u dev/probes/bench_with.py PRO_LANES=$v -- > $o/p_$v.json 2> $o/p_$v.err || { tail $o/p_$v.err; exit 1; }
+  timeout -k 10 600 python -u dev/probes/bench_with.py PRO_LANES=$v -- --full > $o/p_$v.json 2> $o/p_$v.err || { tail $o/p_$v.err; exit 1; }
   echo "prio PRO_LANES=$v $(summ $o/p_$v.json)"
 done
 timeout -k 10 300 python -u tools/train_bench.py --steps 15 > $o/tb.json 2> $o/tb.err || { tail $o/tb.err; exit 1; }

@@ -14,7 +14,7 @@ PY
 }
 for r in 1 2; do
   for v in auto off; do
-    timeout -k 10 600 python -u dev/probes/bench_with.py PRO_LANES=$v -- > $o/full_$v.json 2> $o/full_$v.err || { tail $o/full_$v.err; exit 1; }
+    timeout -k 10 600 python -u dev/probes/bench_with.py PRO_LANES=$v -- --full > $o/full_$v.json 2> $o/full_$v.err || { tail $o/full_$v.err; exit 1; }
     echo "r$r PRO_LANES=$v $(summ $o/full_$v.json)"
   done
 done

@@ -15,6 +15,6 @@ print(round(d["value"], 1), " ".join(f"{k}={v['value']}" for k, v in ex.items() 
 PY
 }
 for r in 1 2; do
-  timeout -k 10 700 python -u bench.py > $o/full_$r.json 2> $o/full_$r.err || { tail $o/full_$r.err; exit 1; }
+  timeout -k 10 700 python -u bench.py --full > $o/full_$r.json 2> $o/full_$r.err || { tail $o/full_$r.err; exit 1; }
   echo "r$r $(summ $o/full_$r.json)"
 done

@@ -25,9 +25,13 @@ def _env():
 
 
 @pytest.mark.gpu
-def test_bench_single_process_json():
-    r = subprocess.run([sys.executable, "bench.py"] + SMALL, cwd=ROOT, env=_env(), capture_output=True, text=True,
-                       timeout=110)
+def test_bench_single_process_json(tmp_path):
+    """A plain run: the headline alone (no extras), and --dump-outputs writes the last timed
+    step's flows as float32 arrays."""
+    import numpy as np
+
+    r = subprocess.run([sys.executable, "bench.py", "--dump-outputs", str(tmp_path)] + SMALL, cwd=ROOT, env=_env(),
+                       capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
     recs = _json_lines(r.stdout)
     assert len(recs) == 1, r.stdout
@@ -35,6 +39,13 @@ def test_bench_single_process_json():
     assert KEYS <= set(rec), set(KEYS) - set(rec)
     assert rec["n_gpus"] == 1 and rec["steps"] == 2 and rec["value"] > 0
     assert rec["config"]["global_batch"] == 1 and rec["config"]["model"] == "raft_large"
+    assert rec["ms_per_step"] > 0 and rec["extras"] is None
+    assert sorted(os.listdir(tmp_path)) == ["flow_final.npy", "flows_sample.npy"]
+    final, sample = np.load(tmp_path / "flow_final.npy"), np.load(tmp_path / "flows_sample.npy")
+    assert final.dtype == np.float32 and final.shape == (1, 128, 256, 2) and np.isfinite(final).all()
+    # 3 iterations x 128 x 256 x 2 elements: below the sample size, so all iterations' flows, whole
+    assert sample.dtype == np.float32 and sample.shape == (3, 1, 128, 256, 2)
+    assert np.array_equal(sample[-1], final) and np.abs(final).max() > 0
 
 
 @pytest.mark.gpu
@@ -55,9 +66,9 @@ def test_bench_two_ranks_gloo_one_json_line():
 
 @pytest.mark.gpu
 def test_bench_extras_keys():
-    """--extras on: the secondary configs land in the same JSON line (each a
+    """--full --extras on: the secondary configs land in the same JSON line (each a
     record or null), here at a small size so the test stays short."""
-    r = subprocess.run([sys.executable, "bench.py", "--extras", "on", "--extra-steps", "2", "--train-batch", "1",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--extras", "on", "--extra-steps", "2", "--train-batch", "1",
                         "--train-size", "128", "256"] + SMALL, cwd=ROOT,
                        env=_env(), capture_output=True, text=True, timeout=115)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -34,12 +34,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-FIXDIR = os.path.join(ROOT, "tests", "fixtures")
+FIXDIR = os.path.join(ROOT, "tests", "golden")
 H, W, ITERS = 440, 1024, 32
+PARTS = 4   # row slabs per fixture: a 440x1024x2 fp32 flow compresses to ~3.2 MB; each file stays below 1 MiB
 
 
-def fixture_path(arch: str) -> str:
-    return os.path.join(FIXDIR, f"golden_{arch}_440x1024_32it.npz")
+def fixture_path(arch: str, part: int = 0) -> str:
+    return os.path.join(FIXDIR, f"golden_{arch}_440x1024_32it.part{part}of{PARTS}.npz")
 
 
 def inputs(B: int = 1, H_: int = H, W_: int = W, seed: int = 0):
@@ -74,15 +75,20 @@ def write_fixtures() -> None:
         t = time.time()
         g = golden(arch)
         mags = g.norm(dim=-1).mean(dim=(1, 2, 3)).tolist()
-        np.savez_compressed(fixture_path(arch), final=g[-1, 0].numpy().astype(np.float32),
-                            mean_mag=np.asarray(mags, dtype=np.float64))
+        final = g[-1, 0].numpy().astype(np.float32)
+        for k, rows in enumerate(np.array_split(final, PARTS, axis=0)):
+            np.savez_compressed(fixture_path(arch, k), final=rows, mean_mag=np.asarray(mags, dtype=np.float64))
         print(f"{arch}: golden in {time.time() - t:.1f} s, |flow| it1 {mags[0]:.3f} it32 {mags[-1]:.3f} "
               f"-> {fixture_path(arch)}", flush=True)
 
 
 def load_fixture(arch: str):
-    with np.load(fixture_path(arch), allow_pickle=False) as z:
-        return torch.from_numpy(z["final"]), z["mean_mag"].tolist()
+    rows = []
+    for k in range(PARTS):
+        with np.load(fixture_path(arch, k), allow_pickle=False) as z:
+            rows.append(z["final"])
+            mags = z["mean_mag"].tolist()
+    return torch.from_numpy(np.concatenate(rows, axis=0)), mags
 
 
 @torch.no_grad()
