@@ -281,6 +281,19 @@ int jr_taps_gemm(const void* fm, int fcs, int fcoff, int K, const void* wpk, flo
 int jr_flow_taps(const float* t, int tcs, const float* bias, int N, int h, int w, float* coords, float* flow32,
                  void* hx, int hx_cs, int hx_off, void* qx, int qx_cs, int qx_off, void* f8, int f8_cs,
                  hipStream_t stream);
+// Warm start (warm.hip).  jr_init_flow: the seed of a warm plan, in place of jr_init_coords:
+// coords = grid + flow_init, flow32 = flow_init (fp32 [M][2]) and bf16(flow_init) into
+// hx / qx (channel offsets) and f8 (channels 0, 1), i.e. the state jr_flow_taps leaves behind.
+int jr_init_flow(const float* flow_init, int N, int h, int w, float* coords, float* flow32, void* hx, int hx_cs,
+                 int hx_off, void* qx, int qx_cs, int qx_off, void* f8, int f8_cs, hipStream_t stream);
+// the fp32 engine's form: hx / qx fp32, flow4 [M][4] rows (fx, fy, 0, 0) (jr_flow_update_f32's state)
+int jr_init_flow_f32(const float* flow_init, int N, int h, int w, float* coords, float* flow32, float* hx, int hx_cs,
+                     int hx_off, float* qx, int qx_cs, int qx_off, float* flow4, hipStream_t stream);
+// Forward projection of a flow field (models/reference.py:forward_project, bitwise): flow, out
+// fp32 [B][h][w][2]; keys: 2 * B*h*w + 2 64-bit words, all ones when allocated and left clean by
+// every call (two launches: atomic-min splat, resolve + hole fill); 0 <= fill_radius <= 8.
+int jr_forward_project(const float* flow, void* keys, float* out, int B, int h, int w, int fill_radius,
+                       hipStream_t stream);
 // Conv of a 2-channel input (the flow branch's 7x7 / 3x3): x bf16 NHWC
 // [N][H][W][x_cstride] (channels 0, 1 used), stride 1, output H x W; w bf16
 // MFMA A fragments [cout/16][NKC][64 lanes][8] (jax_raft_amd/ops/native.py:

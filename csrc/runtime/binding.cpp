@@ -1631,6 +1631,68 @@ static Launch make_flow_update_f32(const TList& t, const IList& i, std::vector<a
   };
 }
 
+// ----------------------------------------------------------------- warm start
+// (kernels warm.hip).  The seed of a warm plan, in place of init_coords:
+// t = [flow_init (fp32 [M][2]), coords, flow32, hx, qx?, flow8? (bf16) | flow4? (fp32 [M][4])],
+// i = [N, h, w, hx_off, qx_off]; f32: the fp32 engine's buffers (flow_update_f32's state)
+static Launch make_init_flow(const TList& t, const IList& i, bool f32, std::vector<at::Tensor>* keep) {
+  at::Tensor fi = opt(t, 0), coords = opt(t, 1), flow32 = opt(t, 2), hx = opt(t, 3), qx = opt(t, 4), fz = opt(t, 5);
+  TORCH_CHECK(i.size() == 5, "init_flow: expected 5 ints");
+  const int N = (int)i[0], h = (int)i[1], w = (int)i[2], hx_off = (int)i[3], qx_off = (int)i[4];
+  TORCH_CHECK(N >= 1 && h >= 1 && w >= 1 && hx_off >= 0 && qx_off >= 0, "init_flow: sizes / offsets");
+  const int64_t M = (int64_t)N * h * w;
+  auto check = f32 ? check_f32 : check_bf16;
+  check_f32_min(fi, "flow_init", 2 * M); check_f32_min(coords, "coords", 2 * M); check_f32_min(flow32, "flow32", 2 * M);
+  for (const at::Tensor* v : {&fi, &coords, &flow32})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(v->data_ptr()) % 8 == 0, "init_flow: flow_init / coords / flow32 8-byte aligned");
+  check(hx, "hx");
+  TORCH_CHECK(hx.numel() >= M * cs(hx) && hx_off + 2 <= cs(hx), "init_flow: hx");
+  if (qx.defined()) { check(qx, "qx"); TORCH_CHECK(qx.numel() >= M * cs(qx) && qx_off + 2 <= cs(qx), "init_flow: qx"); }
+  if (fz.defined()) {
+    check(fz, f32 ? "flow4" : "flow8");
+    TORCH_CHECK(fz.numel() >= M * cs(fz) && (f32 ? cs(fz) == 4 : cs(fz) >= 2), "init_flow: flow8 [M][>=2] / flow4 [M][4]");
+  }
+  if (keep) for (auto& v : {fi, coords, flow32, hx, qx, fz}) if (v.defined()) keep->push_back(v);
+  const float* fip = fi.data_ptr<float>();
+  float* cp = coords.data_ptr<float>();
+  float* flp = flow32.data_ptr<float>();
+  void* hp = hx.data_ptr();
+  void* qp = ptr(qx);
+  void* fzp = ptr(fz);
+  const int hcs = cs(hx), qcs = qx.defined() ? cs(qx) : 0, fzcs = fz.defined() ? cs(fz) : 0;
+  if (f32)
+    return [=](hipStream_t s, int) {
+      return jr_init_flow_f32(fip, N, h, w, cp, flp, (float*)hp, hcs, hx_off, (float*)qp, qcs, qx_off, (float*)fzp, s);
+    };
+  return [=](hipStream_t s, int) {
+    return jr_init_flow(fip, N, h, w, cp, flp, hp, hcs, hx_off, qp, qcs, qx_off, fzp, fzcs, s);
+  };
+}
+
+// t = [flow (fp32 [B][h][w][2]), keys (int64 [2*B*h*w + 2], all ones when allocated), out (like flow)],
+// i = [B, h, w, fill_radius]
+static Launch make_forward_project(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+  at::Tensor flow = opt(t, 0), keys = opt(t, 1), out = opt(t, 2);
+  TORCH_CHECK(i.size() == 4, "forward_project: expected 4 ints");
+  const int B = (int)i[0], h = (int)i[1], w = (int)i[2], R = (int)i[3];
+  TORCH_CHECK(B >= 1 && h >= 1 && w >= 1 && (int64_t)h * w <= INT32_MAX, "forward_project: sizes");
+  TORCH_CHECK(R >= 0 && R <= 8, "forward_project: fill_radius must be in [0, 8]");
+  const int64_t M = (int64_t)B * h * w;
+  check_f32(flow, "flow"); check_f32(out, "out");
+  TORCH_CHECK(flow.numel() == 2 * M && out.numel() == 2 * M, "forward_project: flow / out [B][h][w][2]");
+  TORCH_CHECK(flow.data_ptr() != out.data_ptr(), "forward_project: not in place");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(flow.data_ptr()) % 8 == 0 && reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0,
+              "forward_project: flow / out 8-byte aligned");
+  TORCH_CHECK(keys.defined() && keys.is_cuda() && keys.scalar_type() == at::kLong && keys.is_contiguous() &&
+                  keys.numel() == 2 * M + 2,
+              "forward_project: keys must be a contiguous device int64 [2*B*h*w + 2]");
+  if (keep) { keep->push_back(flow); keep->push_back(keys); keep->push_back(out); }
+  const float* fp = flow.data_ptr<float>();
+  void* kp = keys.data_ptr();
+  float* op = out.data_ptr<float>();
+  return [=](hipStream_t s, int) { return jr_forward_project(fp, kp, op, B, h, w, R, s); };
+}
+
 static void run_now(const Launch& l) { JR_CHECK_OK(l(cur_stream(), 0)); }
 
 // ------------------------------------------------------------- sequence loss
@@ -1676,6 +1738,9 @@ void upsample_convex_f32_op(const TList& t, IList i) { run_now(make_upsample_con
 void corr_pool_f32_op(const TList& t, IList i) { run_now(make_corr_pool_f32(t, i, nullptr)); }
 void lookup_f32_op(const TList& t, IList i) { run_now(make_lookup_f32(t, i, nullptr)); }
 void flow_update_f32_op(const TList& t, IList i) { run_now(make_flow_update_f32(t, i, nullptr)); }
+void init_flow_op(const TList& t, IList i) { run_now(make_init_flow(t, i, false, nullptr)); }
+void init_flow_f32_op(const TList& t, IList i) { run_now(make_init_flow(t, i, true, nullptr)); }
+void forward_project_op(const TList& t, IList i) { run_now(make_forward_project(t, i, nullptr)); }
 
 void corr_op(const TList& t, IList i, double scale) { run_now(make_corr(t, i, scale, nullptr)); }
 // a stand-alone lookup applies its fused flow update when one is given (in a
@@ -1860,6 +1925,8 @@ class Plan : public torch::CustomClassHolder {
   void add_norm_act(TList t, IList i, double eps) { push(make_norm_act(t, i, eps, &keep_), "norm_act"); }
   void add_prep(TList t, IList i) { push(make_prep(t, i, &keep_), "prep"); }
   void add_init_coords(TList t, IList i) { push(make_init_coords(t, i, &keep_), "init_coords"); }
+  void add_init_flow(TList t, IList i) { push(make_init_flow(t, i, false, &keep_), "init_flow"); }
+  void add_init_flow_f32(TList t, IList i) { push(make_init_flow(t, i, true, &keep_), "init_flow_f32"); }
   void add_memset(TList t) { push(make_memset(t, &keep_), "memset"); }
   void add_copy(TList t) { push(make_copy(t, &keep_), "copy"); }
   void add_copy_channels(TList t, IList i) { push(make_copy_channels(t, i, &keep_), "copy_channels"); }
@@ -2346,6 +2413,9 @@ TORCH_LIBRARY(jax_raft_amd, m) {
   m.def("corr_pool_f32(Tensor?[] t, int[] i) -> ()", &jr::corr_pool_f32_op);
   m.def("lookup_f32(Tensor?[] t, int[] i) -> ()", &jr::lookup_f32_op);
   m.def("flow_update_f32(Tensor?[] t, int[] i) -> ()", &jr::flow_update_f32_op);
+  m.def("init_flow(Tensor?[] t, int[] i) -> ()", &jr::init_flow_op);
+  m.def("init_flow_f32(Tensor?[] t, int[] i) -> ()", &jr::init_flow_f32_op);
+  m.def("forward_project(Tensor?[] t, int[] i) -> ()", &jr::forward_project_op);
   m.class_<jr::Plan>("Plan")
       .def(torch::init<>())
       .def("set_segment", &jr::Plan::set_segment)
@@ -2372,6 +2442,8 @@ TORCH_LIBRARY(jax_raft_amd, m) {
       .def("add_norm_act", &jr::Plan::add_norm_act)
       .def("add_prep", &jr::Plan::add_prep)
       .def("add_init_coords", &jr::Plan::add_init_coords)
+      .def("add_init_flow", &jr::Plan::add_init_flow)
+      .def("add_init_flow_f32", &jr::Plan::add_init_flow_f32)
       .def("add_memset", &jr::Plan::add_memset)
       .def("add_copy", &jr::Plan::add_copy)
       .def("add_copy_channels", &jr::Plan::add_copy_channels)

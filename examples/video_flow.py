@@ -4,10 +4,16 @@
 previous pair's refinement loop and this pair's encoders + correlation
 pyramid, and returns the previous pair's flow; ``flush()`` drains the last.
 
-  python examples/video_flow.py frame_0000.png frame_0001.png ... [--arch raft_small] [--iters 12]
+  python examples/video_flow.py frame_0000.png frame_0001.png ... [--arch raft_small] [--iters 12] [--warm-start]
+
+``--warm-start`` runs the synchronous path instead (``RaftEngine.forward``) and
+starts every pair after the first from the previous pair's flow, projected
+forward in time on the GPU (``flow_init="previous"``); ``--iters`` applies as
+given.  (A pipelined step cannot warm-start: it runs the next pair's prologue
+next to the previous pair's loop.)
 
 Without frames a synthetic drifting sequence is used.  Needs an MI355X (the
-native engine); prints the pairs/s of the steady-state pipeline.
+native engine); prints the pairs/s of the steady state.
 """
 import argparse
 import os
@@ -40,6 +46,8 @@ def main():
     ap.add_argument("--arch", default="raft_large", choices=["raft_large", "raft_small"])
     ap.add_argument("--weights", default=None, help="Flax msgpack checkpoint (else random init)")
     ap.add_argument("--iters", type=int, default=32)
+    ap.add_argument("--warm-start", action="store_true",
+                    help="synchronous forwards, each pair after the first started from the previous pair's flow")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "the pipelined engine runs on the GPU"
     factory = raft_large if args.arch == "raft_large" else raft_small
@@ -55,7 +63,15 @@ def main():
             padder = InputPadder(img.shape, channels_last=True)
         (cur,) = padder.pad(img)
         cur = cur.to(dev)
-        if prev is not None:
+        if prev is not None and args.warm_start:
+            out = eng.forward(prev, cur, args.iters, return_all_iters=False, flow_init="previous" if flows else None)
+            flows.append(padder.unpad(out[-1]))
+            if t0 is None:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+            else:
+                n_pairs += 1
+        elif prev is not None:
             out = eng.pipelined(prev, cur, args.iters, return_all_iters=False)   # the previous pair's flow
             if out is not None:
                 flows.append(padder.unpad(out[-1]))

@@ -77,16 +77,31 @@ class RAFT(nn.Module):
         return ckpt.variables_from_module(self)
 
     def forward(self, image1, image2, train: bool = False, num_flow_updates: int = 12, return_all_iters: bool = True,
-                **engine_kw):
+                flow_init=None, return_flow_low: bool = False, **engine_kw):
         """Upsampled flows of every refinement iteration, (num_flow_updates, B, H, W, 2)
         (reference semantics, ``model.py:605``).  ``return_all_iters=False`` (inference
-        serving mode) upsamples and returns only the final flow, shape (1, B, H, W, 2)."""
+        serving mode) upsamples and returns only the final flow, shape (1, B, H, W, 2).
+
+        Warm start (video; not in the reference, original RAFT's ``flow_init``):
+        ``flow_init`` (B, H/8, W/8, 2) fp32 NHWC, channel 0 = x, in 1/8-resolution pixels,
+        starts the refinement at ``coords1 = coords0 + flow_init`` instead of at zero flow;
+        ``flow_init="previous"`` (native engine only) projects the flow of the engine's previous
+        call forward in time on the GPU (:func:`reference.forward_project`).
+        ``return_flow_low=True`` returns ``(flows, flow_low)``, ``flow_low`` (B, H/8, W/8, 2) the
+        final ``coords1 - coords0``.  For uint8 frames of any size both are at the *padded*
+        size divided by 8 (``runtime/engine.py:sintel_pad``), not at the frame size.  Inference
+        only: with ``train=True`` / ``autograd=True`` they raise ``NotImplementedError``."""
         image1, image2 = _as_tensor(image1), _as_tensor(image2)
         B, H, W, _ = image1.shape
         assert (H, W) == tuple(image2.shape[-3:-1]), "input images should have the same shape"
+        warm = dict(flow_init=flow_init, return_flow_low=return_flow_low)
+        if (train or engine_kw.get("autograd")) and (flow_init is not None or return_flow_low):
+            raise NotImplementedError("flow_init / return_flow_low: warm start is inference only (not with train / autograd)")
         if image1.dtype == torch.uint8:
-            return self._forward_u8(image1, image2, train, num_flow_updates, return_all_iters, engine_kw)
+            return self._forward_u8(image1, image2, train, num_flow_updates, return_all_iters, engine_kw, warm)
         assert (H % 8 == 0) and (W % 8 == 0), "input image H and W should be divisible by 8"
+        if flow_init is not None and not isinstance(flow_init, str):
+            flow_init = warm["flow_init"] = check_flow_init(flow_init, B, H, W)
         dev = self._param_device()
         if dev.type == "cuda" and not image1.is_cuda:   # host arrays / tensors for a model on the GPU
             image1, image2 = image1.to(dev), image2.to(dev)
@@ -100,15 +115,15 @@ class RAFT(nn.Module):
                 return out if return_all_iters else out[-1:]
             eng = None if self._lowering_error is not None else self._try_engine(image1.device, engine_kw)
             if eng is not None:
-                return eng.forward(image1, image2, num_flow_updates, return_all_iters=return_all_iters)
+                return eng.forward(image1, image2, num_flow_updates, return_all_iters=return_all_iters, **warm)
             # a model the engine cannot lower (injected sub-modules, custom blocks / norms, channel
             # counts outside the fused kernels' tiling): op by op on the same native kernels
             # (convs, correlation pyramid, lookup: ops/functional.py), no graph
             with torch.no_grad():
-                return self.forward_reference(image1, image2, False, num_flow_updates, return_all_iters)
-        return self.forward_reference(image1, image2, train, num_flow_updates, return_all_iters)
+                return self.forward_reference(image1, image2, False, num_flow_updates, return_all_iters, **warm)
+        return self.forward_reference(image1, image2, train, num_flow_updates, return_all_iters, **warm)
 
-    def _forward_u8(self, image1, image2, train, num_flow_updates, return_all_iters, engine_kw):
+    def _forward_u8(self, image1, image2, train, num_flow_updates, return_all_iters, engine_kw, warm):
         """Raw uint8 NHWC frames of any size: the reference's input protocol
         (``scripts/validate_sintel.py:177-191``: x / 255 * 2 - 1, InputPadder('sintel') replicate
         padding to /8, unpad of the flows) -- on the GPU inside the engine's prep kernel, elsewhere
@@ -119,7 +134,7 @@ class RAFT(nn.Module):
             # bytes of normalised fp32 frames)
             eng = self._try_engine(dev, {k: v for k, v in engine_kw.items() if k not in ("autograd", "fused")})
             if eng is not None:
-                return eng.forward(image1, image2, num_flow_updates, return_all_iters=return_all_iters)
+                return eng.forward(image1, image2, num_flow_updates, return_all_iters=return_all_iters, **warm)
         if dev.type == "cuda" and not image1.is_cuda:
             image1, image2 = image1.to(dev), image2.to(dev)
         from ..runtime.engine import sintel_pad, u8_table
@@ -132,7 +147,9 @@ class RAFT(nn.Module):
             x = lut[x.long()].permute(0, 3, 1, 2)
             return torch.nn.functional.pad(x, [pl, pr, pt, pb], mode="replicate").permute(0, 2, 3, 1).contiguous()
 
-        out = self.forward(prep(image1), prep(image2), train, num_flow_updates, return_all_iters, **engine_kw)
+        out = self.forward(prep(image1), prep(image2), train, num_flow_updates, return_all_iters, **warm, **engine_kw)
+        if warm["return_flow_low"]:   # the flows cropped to the frame; flow_low stays at the padded size / 8
+            return out[0][:, :, pt:pt + H0, pl:pl + W0], out[1]
         return out[:, :, pt:pt + H0, pl:pl + W0]
 
     def _param_device(self) -> torch.device:
@@ -154,7 +171,8 @@ class RAFT(nn.Module):
 
     def apply(self, variables: Mapping[str, Any], image1, image2, train: bool = False, num_flow_updates: int = 12,
               mutable=False, **kw):
-        """Flax-style ``model.apply(variables, image1, image2, train, num_flow_updates)``.
+        """Flax-style ``model.apply(variables, image1, image2, train, num_flow_updates)``
+        (``flow_init=`` / ``return_flow_low=`` pass through to :meth:`forward`).
 
         With ``mutable=['batch_stats']`` (and ``train=True``) returns
         ``(flows, {'batch_stats': updated})`` like Flax."""
@@ -181,10 +199,19 @@ class RAFT(nn.Module):
         return out
 
     # ------------------------------------------------------- golden execution
-    def forward_reference(self, image1, image2, train: bool, num_flow_updates: int, return_all_iters: bool = True):
+    def forward_reference(self, image1, image2, train: bool, num_flow_updates: int, return_all_iters: bool = True,
+                          flow_init: Optional[torch.Tensor] = None, return_flow_low: bool = False):
         """Reference-semantics forward (``model.py:557-605`` with the scan body
-        ``UpdateCell.__call__``, ``model.py:495-510``)."""
+        ``UpdateCell.__call__``, ``model.py:495-510``).  ``flow_init`` (B, H/8, W/8, 2):
+        ``coords1 = coords0 + flow_init`` (warm start), everything else unchanged;
+        ``return_flow_low``: ``(flows, final coords1 - coords0)``."""
         B, H, W, _ = image1.shape
+        if isinstance(flow_init, str):
+            raise ValueError(f"flow_init={flow_init!r} is a mode of the native engine; this path takes a tensor")
+        if flow_init is not None:
+            if train:
+                raise NotImplementedError("flow_init: warm start is inference only (not with train=True)")
+            flow_init = check_flow_init(flow_init, B, H, W).to(image1.device)
         fmaps = self.feature_encoder(torch.cat([image1, image2], dim=0), train)
         fmap1, fmap2 = torch.chunk(fmaps, 2, dim=0)
         assert tuple(fmap1.shape[1:3]) == (H // 8, W // 8), "The feature encoder should downsample H and W by 8"
@@ -199,7 +226,7 @@ class RAFT(nn.Module):
         hidden = torch.tanh(hidden)
         context = torch.relu(context)
         coords0 = R.make_coords_grid(B, H // 8, W // 8, device=image1.device)
-        coords1 = coords0.clone()
+        coords1 = coords0.clone() if flow_init is None else coords0 + flow_init
         preds = []
         for it in range(num_flow_updates):
             coords1 = coords1.detach()  # stop_gradient, model.py:498
@@ -211,6 +238,8 @@ class RAFT(nn.Module):
                 continue
             up_mask = None if self.mask_predictor is None else self.mask_predictor(hidden, train)
             preds.append(R.upsample_flow(coords1 - coords0, up_mask))
+        if return_flow_low:
+            return torch.stack(preds, dim=0), coords1 - coords0
         return torch.stack(preds, dim=0)
 
     # -------------------------------------------------------- native engine
@@ -238,6 +267,16 @@ class RAFT(nn.Module):
             if "_engines" in self.__dict__:
                 self.__dict__["_engines"] = {}
         super().__setattr__(name, value)
+
+
+def check_flow_init(flow_init, B: int, H: int, W: int) -> torch.Tensor:
+    """``flow_init`` as an fp32 tensor of the shape a (B, H, W) forward expects, else ``ValueError``."""
+    t = flow_init if isinstance(flow_init, torch.Tensor) else torch.as_tensor(np.asarray(flow_init, dtype=np.float32))
+    want = (B, H // 8, W // 8, 2)
+    if tuple(t.shape) != want:
+        raise ValueError(f"flow_init must have shape {want} (B, H/8, W/8, 2; for uint8 frames H, W are the "
+                         f"padded size), got {tuple(t.shape)}")
+    return t.float()
 
 
 def _same_leaves(a: Mapping[str, Any], b: Mapping[str, Any]) -> bool:

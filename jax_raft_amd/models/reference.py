@@ -30,6 +30,8 @@ __all__ = [
     "build_pyramid",
     "index_pyramid",
     "neighborhood_offsets",
+    "forward_project",
+    "fill_offsets",
 ]
 
 
@@ -351,3 +353,68 @@ def index_pyramid(pyramid: Sequence[torch.Tensor], coords: torch.Tensor, radius:
         out.append(s)
         c = c / 2
     return torch.cat(out, dim=-1)
+
+
+# ------------------------------------------------------------------ warm start
+# (no counterpart in the reference: original RAFT's ``forward_interpolate``, defined
+# here with single fp32 operations and integers only so that the HIP kernel,
+# csrc/kernels/warm.hip, matches bit for bit)
+
+def fill_offsets(fill_radius: int) -> List[Tuple[int, int]]:
+    """The hole search's neighbour offsets ``(dy, dx)``, ``|dy|, |dx| <= fill_radius``,
+    ascending by ``(dy*dy + dx*dx, dy, dx)``."""
+    r = range(-fill_radius, fill_radius + 1)
+    return sorted(((dy, dx) for dy in r for dx in r), key=lambda o: (o[0] * o[0] + o[1] * o[1], o[0], o[1]))
+
+
+def forward_project(flow: torch.Tensor, fill_radius: int = 4) -> torch.Tensor:
+    """Project a flow field forward in time: the initial flow of pair t + 1 from the
+    (1/8-resolution) flow of pair t.  flow, result: (B, h, w, 2) fp32, channel 0 = x.
+
+    1. A source cell (x, y) with flow (fx, fy) lands at ``x1 = float(x) + fx``,
+       ``y1 = float(y) + fy``; its target cell is ``tx = floor(x1 + 0.5)``,
+       ``ty = floor(y1 + 0.5)``.  It is valid iff ``0 <= tx <= w-1`` and ``0 <= ty <= h-1``
+       (float comparisons: NaN / inf are invalid).
+    2. Key of a valid source: ``ix = rint((x1 - tx) * 256)``, ``iy`` likewise (half to even),
+       ``d2 = ix*ix + iy*iy`` (integer), key = ``(d2 << 32) | (y*w + x)``.
+    3. A target cell takes the flow of the valid source with the minimum key that lands in
+       it: the nearest landing, ties to the lower source index.
+    4. A cell nothing landed in takes the value of the first hit cell among
+       :func:`fill_offsets` (out-of-map neighbours skipped), else (0, 0); holes are filled
+       from hit cells only, never from other filled holes.
+    """
+    assert flow.ndim == 4 and flow.shape[-1] == 2 and flow.dtype == torch.float32, "flow: (B, h, w, 2) fp32"
+    assert 0 <= fill_radius <= 8, "fill_radius must be in [0, 8]"
+    B, h, w, _ = flow.shape
+    dev = flow.device
+    grid = make_coords_grid(1, h, w, device=dev)
+    x1 = grid[..., 0] + flow[..., 0]
+    y1 = grid[..., 1] + flow[..., 1]
+    tx = torch.floor(x1 + 0.5)
+    ty = torch.floor(y1 + 0.5)
+    valid = (tx >= 0) & (tx <= w - 1) & (ty >= 0) & (ty <= h - 1)
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    ix = torch.where(valid, torch.round((x1 - tx) * 256.0), zero).long()
+    iy = torch.where(valid, torch.round((y1 - ty) * 256.0), zero).long()
+    src = torch.arange(h * w, device=dev).view(1, h, w)
+    empty = torch.iinfo(torch.int64).max
+    key = torch.where(valid, ((ix * ix + iy * iy) << 32) | src, torch.full((), empty, device=dev))
+    tgt = torch.where(valid, ty * w + tx, zero).long()
+    keys = torch.full((B, h * w), empty, dtype=torch.int64, device=dev)
+    keys.scatter_reduce_(1, tgt.reshape(B, -1), key.reshape(B, -1), "amin", include_self=True)
+    hit = keys != empty
+    win = torch.where(hit, keys & 0xFFFFFFFF, torch.zeros((), dtype=torch.int64, device=dev))
+    splat = torch.gather(flow.reshape(B, h * w, 2), 1, win.unsqueeze(-1).expand(-1, -1, 2))
+    hit = hit.view(B, h, w)
+    splat = torch.where(hit.unsqueeze(-1), splat.view(B, h, w, 2), zero)
+    R = fill_radius
+    hit_p = F.pad(hit.to(torch.uint8), (R, R, R, R)).bool()
+    splat_p = F.pad(splat, (0, 0, R, R, R, R))
+    out = torch.zeros_like(flow)
+    done = torch.zeros_like(hit)
+    for dy, dx in fill_offsets(R):
+        nb_hit = hit_p[:, R + dy:R + dy + h, R + dx:R + dx + w]
+        take = nb_hit & ~done
+        out = torch.where(take.unsqueeze(-1), splat_p[:, R + dy:R + dy + h, R + dx:R + dx + w], out)
+        done = done | take
+    return out

@@ -552,6 +552,35 @@ def convex_head(feat: torch.Tensor, wpk: torch.Tensor, bias: torch.Tensor, flow:
     return out
 
 
+def project_keys(B: int, h: int, w: int, device) -> torch.Tensor:
+    """The key buffer of :func:`forward_project` for (B, h, w) maps: two planes of 64-bit
+    splat keys + two control words, all ones (csrc/kernels/warm.hip).  Every call leaves it
+    clean for the next, so one buffer serves any number of calls on one stream."""
+    return torch.full((2 * B * h * w + 2,), -1, dtype=torch.int64, device=device)
+
+
+def forward_project(flow: torch.Tensor, fill_radius: int = 4, keys: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Project a (B, h, w, 2) fp32 flow field forward in time (the warm-start flow of the
+    next pair): ``models/reference.py:forward_project`` -- that golden op itself on a CPU
+    tensor, the HIP kernels (bitwise equal, two launches, no host synchronisation) on a GPU
+    tensor.  ``keys``: a :func:`project_keys` buffer to reuse across calls."""
+    if not flow.is_cuda:
+        from ..models.reference import forward_project as golden
+
+        return golden(flow, fill_radius)
+    if flow.ndim != 4 or flow.shape[-1] != 2 or flow.dtype != torch.float32:
+        raise ValueError(f"forward_project: flow must be (B, h, w, 2) fp32, got {tuple(flow.shape)} {flow.dtype}")
+    B, h, w, _ = flow.shape
+    flow = flow.contiguous()
+    if keys is None:
+        keys = project_keys(B, h, w, flow.device)
+    if out is None:
+        out = torch.empty_like(flow)
+    ops().forward_project([flow, keys, out], [B, h, w, int(fill_radius)])
+    return out
+
+
 def conv2d(spec: ConvSpec, x: torch.Tensor, act: int = ACT_NONE, out_dtype=torch.bfloat16, alpha: float = 1.0,
            res: Optional[torch.Tensor] = None, res_post: int = 0, cfg: Optional[int] = None) -> torch.Tensor:
     """Eager NHWC conv of a contiguous bf16 tensor [N, H, W, C] (C == cin8)."""

@@ -149,6 +149,12 @@ class _PlanState:
     cp: Optional[dict] = None
     # raw uint8 frames (K14): (H0, W0, pt, pl) of the frames inside the padded plan size, else None
     src: Optional[Tuple[int, int, int, int]] = None
+    # warm start: the plan's static initial-flow input (B, h, w, 2) fp32 (warm plans only), the key
+    # buffer of the "previous" projection, and every plan's final-flow buffers, one
+    # (b0, nb, flow32, odd-iteration flow32 or None) per batch part
+    flow_init: Optional[torch.Tensor] = None
+    keys: Optional[torch.Tensor] = None
+    flow_out: List[tuple] = field(default_factory=list)
 
 
 _VERSION = operator.attrgetter("_version")
@@ -259,6 +265,7 @@ class RaftEngine:
     MASK_PARITY = False   # lane schedule: parity-buffered h copy for the mask lane (slower at b4)
     CORR_PERSIST_B1 = True   # the persistent blocked pyramid kernel at batch 1 too (plans outside pipelined slots)
     HOST_GATE = True      # host gate of long replays (see GATE_MIN_ITERS)
+    WARM_FILL_RADIUS = 4  # flow_init="previous": hole-filling radius of the forward projection (1/8-res cells)
 
     def __init__(self, model, device, use_graph: bool = True, copy_output: bool = True,
                  corr_dtype: torch.dtype = torch.bfloat16, gate_dtype: torch.dtype = torch.bfloat16,
@@ -316,6 +323,7 @@ class RaftEngine:
         self._states: "OrderedDict[tuple, _PlanState]" = OrderedDict()
         self._snap = None    # parameter / module snapshot of the last repack (_snapshot / _stale)
         self._pp = None   # pipelined(): {key, n, pending slot}
+        self._last = None   # flow_init="previous": ((B, H, W), n_iters, flow_out) of the last forward()
         self._analyse()
         self._pack()
 
@@ -358,8 +366,9 @@ class RaftEngine:
         return (B, H, W, n_iters, bool(all_iters))
 
     def _build_key(self, key: tuple) -> _PlanState:
+        """Key layout: (B, H, W, n, all)[ + ("u8", H0, W0, pt, pl)][ + ("warm",)][ + ("pslot", slot)]."""
         src = tuple(key[6:10]) if len(key) >= 10 and key[5] == "u8" else None
-        return self._build(*key[:5], src=src)
+        return self._build(*key[:5], src=src, warm="warm" in key[5:])
 
     @staticmethod
     def _crop(st: _PlanState, out: torch.Tensor) -> torch.Tensor:
@@ -432,6 +441,7 @@ class RaftEngine:
         self._quiesce()
         self._states.clear()
         self._pp = None
+        self._last = None
         self._done_ev = None
 
     def num_plans(self) -> int:
@@ -1082,7 +1092,9 @@ class RaftEngine:
         return nb >= self.AUTO_STREAMS_MIN_BATCH
 
     def _build(self, B: int, H: int, W: int, n_iters: int, all_iters: bool = True,
-               src: Optional[Tuple[int, int, int, int]] = None) -> _PlanState:
+               src: Optional[Tuple[int, int, int, int]] = None, warm: bool = False) -> _PlanState:
+        if warm and self.cp:
+            raise NotImplementedError("warm start (flow_init) is not lowered under context parallelism")
         on = self.uses_lanes(B, all_iters)
         self.streams = on
         self.mask_head = "split" if on else "fused"
@@ -1109,17 +1121,21 @@ class RaftEngine:
         st.out = torch.zeros((n_iters if all_iters else 1, B, H, W, 2), dtype=F32, device=dev)
         st.slot_ptr = st.out.data_ptr()
         st.out_slot = torch.tensor([st.slot_ptr], dtype=torch.int64, device=dev)
+        if warm:
+            st.flow_init = torch.zeros((B, h, w, 2), dtype=F32, device=dev)
         lanes = (0, 1, 2) if on else (0, 0, 0)
         for part, plan in enumerate(plans):
-            self._build_part(st, plan, part * nb, nb, H, W, n_iters, f"p{part}.", lanes, 0, all_iters)
+            self._build_part(st, plan, part * nb, nb, H, W, n_iters, f"p{part}.", lanes, 0, all_iters, warm)
             plan.set_lane(0)
             plan.set_segment(2)
         return st
 
     def _build_part(self, st: _PlanState, plan, b0: int, B: int, H: int, W: int, n_iters: int, pt: str,
-                    lanes: Tuple[int, int, int], ev0: int, all_iters: bool = True):
+                    lanes: Tuple[int, int, int], ev0: int, all_iters: bool = True, warm: bool = False):
         """Lower one forward over images [b0, b0 + B) onto ``plan`` using lanes
-        (main, side, side2) and events ev0 .. ev0 + 8.
+        (main, side, side2) and events ev0 .. ev0 + 8.  ``warm``: the loop starts from the
+        plan's ``flow_init`` slice instead of zero flow (``init_flow`` in place of
+        ``init_coords``; everything else, and every cold plan, is unchanged).
 
         Three loop schedules (``model.py:495-510`` per iteration):
 
@@ -1224,7 +1240,18 @@ class RaftEngine:
             gb = alloc(f"gru{gi}.cbias", (M, self.gate_cs), self.gate_dtype)
             self._conv(plan, sp[f"gru{gi}.ctx"], ce_out, B, h, w, gb, x_coff=self.hidden)
             gbias.append(gb)
-        plan.add_init_coords([coords], [B, h, w])
+        if warm:
+            # the seed sits where init_coords sits: on the context lane, which waited for E_PREP
+            # (recorded on the main lane after the memsets of hx / qx / flow8 / flow32 above, so
+            # the seed is not zeroed again) and records E_CTX, which the main lane waits for before
+            # the lane schedule's iteration-0 flow features and the first lookup.  It writes the
+            # state a flow update leaves (flowhead.hip:flow_taps_kernel), qx only where that does.
+            gp = self._gru_path(B, h, w)
+            seed_qx = gp != "halo" or len(m.update_block.recurrent_block.kernel_size) == 1
+            plan.add_init_flow([st.flow_init[b0:b0 + B], coords, flow32, hx, qx if seed_qx else None, flow8],
+                               [B, h, w, self.flow_off, self.flow_off])
+        else:
+            plan.add_init_coords([coords], [B, h, w])
         plan.add_record(E_CTX)
 
         fmap = alloc("fmap", (2 * B, h, w, self.fmap_ch))
@@ -1331,6 +1358,7 @@ class RaftEngine:
                   and self.MASK_PARITY)
         hm2 = alloc("hm2", (M, self.hidden)) if parity else None
         flow32b = alloc("flow32b", (M, 2), F32) if parity else None
+        st.flow_out.append((b0, B, flow32, flow32b))
 
         # one-lane schedule: the flow conv + the previous iteration's upsampling as one grid (merged.hip)
         c1k = me.convflow1.layers_0.kernel
@@ -1572,20 +1600,66 @@ class RaftEngine:
     # --------------------------------------------------------------- forward
     @torch.no_grad()
     def forward(self, image1: torch.Tensor, image2: torch.Tensor, num_flow_updates: int = 12,
-                return_all_iters: bool = True) -> torch.Tensor:
+                return_all_iters: bool = True, flow_init=None, return_flow_low: bool = False):
         """All ``num_flow_updates`` upsampled flows (N, B, H, W, 2), as the reference
-        returns; ``return_all_iters=False`` returns only the final one, (1, B, H, W, 2)."""
+        returns; ``return_all_iters=False`` returns only the final one, (1, B, H, W, 2).
+
+        Warm start (video): ``flow_init`` -- a (B, h, w, 2) fp32 tensor in 1/8-resolution
+        pixels, channel 0 = x (h, w = the plan's size / 8: the *padded* size for uint8 frames)
+        -- starts the refinement at ``coords1 = coords0 + flow_init``.  Such a call runs a plan
+        of its own (plan key + "warm") whose seed kernel replaces ``init_coords``;
+        ``flow_init=None`` runs today's cold plan, untouched.  ``flow_init="previous"``
+        projects the final 1/8-resolution flow of the most recent :meth:`forward` of the same
+        (B, H, W) -- any iteration count or output mode -- forward in time
+        (``ops/native.py:forward_project``, two small launches on the current stream before
+        the replay; no host synchronisation, no host copy) and starts from that; ``ValueError``
+        when there is no such call or the weights were repacked since.
+        ``return_flow_low=True`` returns ``(flows, flow_low)``: a fresh (B, h, w, 2) fp32 copy
+        of the final ``coords1 - coords0``.
+
+        Not with :meth:`pipelined` (a slot's prologue, where the seed runs, is replayed
+        concurrently with the previous pair's loop, whose final flow "previous" would need),
+        not under context parallelism (its host-driven loop is not lowered for a seed) and
+        not in training."""
         if self._stale():
             self._pack()
+            self._last = None
+        if self.cp and flow_init is not None:
+            raise NotImplementedError("forward(flow_init=...): not with context parallelism (cp_group)")
         if image1.dtype == torch.uint8 and not self._native_u8:
             a, b, src = self._host_u8(image1, image2)
-            out = self.forward(a, b, num_flow_updates, return_all_iters)
+            res = self.forward(a, b, num_flow_updates, return_all_iters, flow_init, return_flow_low)
             H0, W0, pt, pl = src
-            return out[:, :, pt:pt + H0, pl:pl + W0]
+            if return_flow_low:
+                return res[0][:, :, pt:pt + H0, pl:pl + W0], res[1]
+            return res[:, :, pt:pt + H0, pl:pl + W0]
         key = self._key(image1, image2, num_flow_updates, return_all_iters)
+        B, h, w = key[0], key[1] // 8, key[2] // 8
+        prev = None
+        if isinstance(flow_init, str):
+            if flow_init != "previous":
+                raise ValueError(f"flow_init must be a (B, h, w, 2) tensor, None or 'previous', got {flow_init!r}")
+            prev = self._last
+            if prev is None or prev[0] != key[:3]:
+                raise ValueError(f"flow_init='previous': no previous forward() of shape (B, H, W) = {key[:3]} "
+                                 "on this engine since its weights were last packed")
+        elif flow_init is not None:
+            if tuple(flow_init.shape) != (B, h, w, 2):
+                raise ValueError(f"flow_init must have shape {(B, h, w, 2)} (B, H/8, W/8, 2; for uint8 frames "
+                                 f"H, W are the padded size), got {tuple(flow_init.shape)}")
+        if flow_init is not None:
+            key = key + ("warm",)
         st = self._plan_state(key, lambda: self._build_key(key))
         st.inp1.copy_(image1)
         st.inp2.copy_(image2)
+        if prev is not None:
+            # before the replay overwrites the previous call's flow buffers (stream order)
+            if st.keys is None:
+                st.keys = nat.project_keys(B, h, w, self.device)
+            nat.forward_project(self._flow_low(prev[2], prev[1], h, w, copy=False), self.WARM_FILL_RADIUS,
+                                keys=st.keys, out=st.flow_init)
+        elif flow_init is not None:
+            st.flow_init.copy_(flow_init)
         self._pre_launch(st)
         fresh = self.copy_output and st.slot_ok
         out = torch.empty_like(st.out) if fresh else st.out
@@ -1607,9 +1681,23 @@ class RaftEngine:
                 p0.merge_finish(num_flow_updates)
             p0.replay_pipelined()
         self._mark()
-        if fresh:
-            return self._crop(st, out)
-        return self._crop(st, st.out.clone() if self.copy_output else st.out)
+        self._last = (key[:3], num_flow_updates, st.flow_out)
+        res = self._crop(st, out) if fresh else self._crop(st, st.out.clone() if self.copy_output else st.out)
+        if return_flow_low:
+            return res, self._flow_low(st.flow_out, num_flow_updates, h, w)
+        return res
+
+    @staticmethod
+    def _flow_low(flow_out, n_iters: int, h: int, w: int, copy: bool = True) -> torch.Tensor:
+        """The final 1/8-resolution flow (B, h, w, 2) of a plan that ran ``n_iters`` iterations,
+        assembled across its batch parts.  The update of launch index j writes the odd-iteration
+        buffer when j is odd (MASK_PARITY) and the last update runs at j = n_iters, so that
+        buffer holds the final flow iff ``n_iters`` is odd.  ``copy=False`` may return a view of
+        the plan's buffer (a one-part plan)."""
+        bufs = [(fb if (fb is not None and n_iters & 1) else f).view(nb, h, w, 2) for _, nb, f, fb in flow_out]
+        if len(bufs) == 1:
+            return bufs[0].clone() if copy else bufs[0]
+        return torch.cat(bufs, dim=0)
 
     def _pre_launch(self, st: _PlanState) -> None:
         """Work a forward runs before replaying its plan (RaftEngineMixed: the fp32 feature encoder)."""
@@ -1650,7 +1738,7 @@ class RaftEngine:
 
     @torch.no_grad()
     def pipelined(self, image1: torch.Tensor, image2: torch.Tensor, num_flow_updates: int = 12,
-                  return_all_iters: bool = True) -> Optional[torch.Tensor]:
+                  return_all_iters: bool = True, flow_init=None) -> Optional[torch.Tensor]:
         """Software-pipelined forward for throughput (batch inference, serving):
         returns the flows of the PREVIOUS call's images (``None`` on the first
         call); :meth:`flush` returns the last pending batch's flows.
@@ -1665,8 +1753,16 @@ class RaftEngine:
         one loop, i.e. one forward's work.  (:meth:`submit` replays the two
         phases as separate graphs on two streams, which serialise on this
         ROCm.)  The result of each batch is bitwise equal to :meth:`forward`
-        (tests/test_engine_gpu.py)."""
+        (tests/test_engine_gpu.py).
+
+        No warm start here (``flow_init`` raises ``NotImplementedError``): a slot's prologue,
+        where the seed would run, is replayed concurrently with the previous pair's loop, so
+        that pair's final flow -- what "previous" starts from -- does not exist yet."""
+        if flow_init is not None:
+            raise NotImplementedError("pipelined(flow_init=...): warm start needs the previous pair's final flow, "
+                                      "which a pipelined slot's prologue runs concurrently with; use forward()")
         if self._stale():
+            self._last = None
             if self._pp is not None and self._pp["pending"] is not None:
                 # the pending batch's encoders + pyramid ran with the old weights; its loop
                 # would run with the new ones (a result matching neither forward)

@@ -161,8 +161,11 @@ class RaftEngineF32(RaftEngine):
                 H, W = h_, w_
         return x, H, W
 
-    def _build(self, B: int, H: int, W: int, n_iters: int, all_iters: bool = True, src=None) -> _PlanState:
+    def _build(self, B: int, H: int, W: int, n_iters: int, all_iters: bool = True, src=None,
+               warm: bool = False) -> _PlanState:
         assert src is None, "fp32 engine: uint8 frames are prepared by RaftEngine._host_u8"
+        if warm and self.cp:
+            raise NotImplementedError("warm start (flow_init) is not lowered under context parallelism")
         m = self.model
         dev = self.device
         sp = self._specs
@@ -222,7 +225,12 @@ class RaftEngineF32(RaftEngine):
             gb = alloc(f"gru{gi}.cbias", (M, self.gate_cs))
             self._conv(plan, sp[f"gru{gi}.ctx"], ce_out, B, h, w, gb, x_coff=self.hidden)
             gbias.append(gb)
-        plan.add_init_coords([coords], [B, h, w])
+        if warm:   # the seed: the state flow_update_f32 leaves, after the memsets above (one lane, in order)
+            st.flow_init = alloc("flow_init", (B, h, w, 2))
+            plan.add_init_flow_f32([st.flow_init, coords, flow32, hx, qx, flow4], [B, h, w, self.flow_off, self.flow_off])
+        else:
+            plan.add_init_coords([coords], [B, h, w])
+        st.flow_out.append((0, B, flow32, None))
         # correlation pyramid (model.py:418-446, 472-481): level 0 = fmap1 . fmap2^T / sqrt(C)
         # per image on the fp32 MFMA GEMM, then 2x2 floor average pooling per level; with
         # context parallelism only this rank's query rows [r0, r1)
@@ -336,9 +344,10 @@ class RaftEngineMixed(RaftEngine):
         super()._hold_model_weakly()
         self._f32._hold_model_weakly()
 
-    def _build(self, B: int, H: int, W: int, n_iters: int, all_iters: bool = True, src=None) -> _PlanState:
+    def _build(self, B: int, H: int, W: int, n_iters: int, all_iters: bool = True, src=None,
+               warm: bool = False) -> _PlanState:
         assert src is None, "mixed engine: uint8 frames are prepared by RaftEngine._host_u8"
-        st = super()._build(B, H, W, n_iters, all_iters, src)
+        st = super()._build(B, H, W, n_iters, all_iters, src, warm)
         f = self._f32
         if f._stale():
             f._pack()
