@@ -1,5 +1,6 @@
-// jax_raft_amd native runtime: TORCH_LIBRARY ops over the gfx950 kernels and
-// a plan executor with hipGraph capture.
+// jax_raft_amd native runtime: the launch builders over the gfx950 kernels (make_<op>: checked
+// arguments -> a launch closure), the op table that lists them, and the TORCH_LIBRARY
+// registration generated from the table.  The plan executor is plan.h.
 //
 // The reference has no native code; XLA emits its kernels
 // and runs the refinement loop as a device while-loop (jax_raft/model.py:589-603,
@@ -10,31 +11,27 @@
 //     with all pointers, shapes and tile configs resolved, and either launches
 //     them straight from C++ (no per-op Python overhead) or captures the whole
 //     N-iteration forward into one hipGraph and replays it.
+// A maker pushes every tensor its launch points into onto `keep`: the plan's list, or the
+// eager op's local one, which lives until the launch is queued.
 #include <torch/custom_class.h>
 #include <torch/library.h>
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
-#include <rocprofiler-sdk-roctx/roctx.h>
 
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 #include <functional>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../kernels/kernels.h"
+#include "plan.h"
 
 namespace jr {
 
 using TList = c10::List<c10::optional<at::Tensor>>;
 using IList = std::vector<int64_t>;
-using Launch = std::function<int(hipStream_t, int)>;
-
-static inline hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 static inline at::Tensor opt(const TList& t, size_t i) {
   if (i >= t.size()) return at::Tensor();
@@ -43,12 +40,6 @@ static inline at::Tensor opt(const TList& t, size_t i) {
 }
 static inline void* ptr(const at::Tensor& t) { return t.defined() ? t.data_ptr() : nullptr; }
 static inline int cs(const at::Tensor& t) { return t.defined() ? (int)t.size(-1) : 0; }
-
-#define JR_CHECK_OK(expr)                                                                 \
-  do {                                                                                    \
-    int e__ = (expr);                                                                     \
-    TORCH_CHECK(e__ == 0, "jax_raft_amd kernel launch failed: ", hipGetErrorString((hipError_t)e__)); \
-  } while (0)
 
 static void check_bf16(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.defined(), name, " must be defined");
@@ -70,9 +61,9 @@ static void check_f32(const at::Tensor& t, const char* name) {
 //      (, OH_override, OW_override, log2 dil_h, log2 dil_w (, bmap_coff))]
 static int64_t check_flow_out(const at::Tensor& out, int B, int h, int w);
 
-static void conv_train_extras(ConvParams& p, int epi, const TList& tx, const IList& ix, std::vector<at::Tensor>* keep);
+static void conv_train_extras(ConvParams& p, int epi, const TList& tx, const IList& ix, std::vector<at::Tensor>& keep);
 
-static ConvParams build_conv(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>* keep,
+static ConvParams build_conv(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>& keep,
                              const TList* tx, const IList* ix, int* epi_out, int* cfg_out) {
   TORCH_CHECK(i.size() == 22 || i.size() == 26 || i.size() == 27, "conv: expected 22, 26 or 27 ints");
   at::Tensor x = opt(t, 0), w = opt(t, 1), bias = opt(t, 2), y = opt(t, 3), y2 = opt(t, 4), res = opt(t, 5);
@@ -197,7 +188,7 @@ static ConvParams build_conv(const TList& t, const IList& i, double alpha, std::
   }
   TORCH_CHECK(cfg >= 0 && cfg <= 43 && !(cfg >= 29 && cfg <= 32), "conv: unknown tile config ", cfg);
   if (tx) conv_train_extras(p, epi, *tx, *ix, keep);
-  if (keep) for (auto& v : {x, w, bias, y, y2, res, h32, zbuf, coords, flow32, y3, bmap, tapw}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {x, w, bias, y, y2, res, h32, zbuf, coords, flow32, y3, bmap, tapw}) if (v.defined()) keep.push_back(v);
   *epi_out = epi;
   *cfg_out = cfg;
   return p;
@@ -214,8 +205,8 @@ bool conv_halo_ok_cfg(int64_t cfg, int64_t cin8, int64_t cout) {
   return c[0] == cin8 && cout <= 512 && jr_conv_halo_lds((int)(cfg - kHaloCfg0)) <= 160 * 1024;
 }
 
-static Launch make_conv_halo(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>* keep) {
-  TORCH_CHECK(i.size() >= 22, "conv: expected >= 22 ints");
+static Launch make_conv_halo(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>& keep) {
+  // (both callers, make_conv and make_conv_alt, come here with i.size() >= 22)
   const int cfg = (int)i[20] - kHaloCfg0;
   int c[6];
   TORCH_CHECK(jr_conv_halo_cfg(cfg, c), "conv_halo: unknown tile config ", i[20]);
@@ -276,7 +267,7 @@ static Launch make_conv_halo(const TList& t, const IList& i, double alpha, std::
     TORCH_CHECK(i.size() >= 29, "conv_halo: the input norm needs [.., in_relu, in_hw]");
     TORCH_CHECK(ist.numel() >= (int64_t)N * cin8 * 2 && i[28] > 0, "conv_halo: input stats [N][cin][2]");
     p.in_stats = ist.data_ptr<float>(); p.in_relu = (int)i[27]; p.in_hw = (int)i[28]; p.in_eps = 1e-5f;
-    if (keep) keep->push_back(ist);
+    keep.push_back(ist);
   }
   // optional t[15..17]: the input's residual (bf16 [N][H][W][>= cin], channel offset 0), its
   // stats ([N][cin][2], instance-normalised if given), the write-back of the built input
@@ -289,14 +280,14 @@ static Launch make_conv_halo(const TList& t, const IList& i, double alpha, std::
       TORCH_CHECK(cs(ires) % 8 == 0 && cs(ires) >= cin8 && ires.numel() >= M * cs(ires) &&
                   (int64_t)ires.numel() * 2 <= (1LL << 31), "conv_halo: input residual [N][H][W][>= cin]");
       p.in_res = ires.data_ptr(); p.in_rcs = cs(ires); p.in_res_bytes = (long)ires.numel() * 2;
-      if (keep) keep->push_back(ires);
+      keep.push_back(ires);
     }
     if (irst.defined()) {
       TORCH_CHECK(ires.defined(), "conv_halo: residual stats without a residual");
       check_f32(irst, "residual stats");
       TORCH_CHECK(irst.numel() >= (int64_t)N * cin8 * 2, "conv_halo: residual stats [N][cin][2]");
       p.in_res_stats = irst.data_ptr<float>();
-      if (keep) keep->push_back(irst);
+      keep.push_back(irst);
     }
     if (xn.defined()) {
       check_bf16(xn, "input write-back");
@@ -304,18 +295,18 @@ static Launch make_conv_halo(const TList& t, const IList& i, double alpha, std::
       TORCH_CHECK(!(xn.data_ptr() == x.data_ptr()) && !(ires.defined() && xn.data_ptr() == ires.data_ptr()),
                   "conv_halo: xn must not alias the input or its residual (neighbouring tiles read them)");
       p.xn = xn.data_ptr(); p.xncs = cs(xn);
-      if (keep) keep->push_back(xn);
+      keep.push_back(xn);
     }
   }
   p.x_bytes = (long)x.numel() * 2;
   TORCH_CHECK(p.x_bytes < (1LL << 31), "conv_halo: input larger than 2 GiB");
   for (const at::Tensor* v : {&x, &wh, &y})
     TORCH_CHECK(reinterpret_cast<uintptr_t>(v->data_ptr()) % 16 == 0, "conv_halo: 16-byte aligned operands");
-  if (keep) for (auto& v : {x, bias, y, y2, res, wh, part}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {x, bias, y, y2, res, wh, part}) if (v.defined()) keep.push_back(v);
   return [p, cfg](hipStream_t s, int) { return jr_conv_halo(&p, cfg, s); };
 }
 
-static Launch make_conv(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>* keep,
+static Launch make_conv(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>& keep,
                         const TList* tx = nullptr, const IList* ix = nullptr) {
   if (i.size() >= 22 && (i[20] & 255) >= kHaloCfg0 && tx == nullptr) return make_conv_halo(t, i, alpha, keep);
   int epi = 0, cfg = 0;
@@ -326,7 +317,7 @@ static Launch make_conv(const TList& t, const IList& i, double alpha, std::vecto
 // A conv whose input on ODD loop iterations is x_alt (same shape as x): the reader of a state
 // that ping-pongs between two buffers (raft_small's FlowHead after the single-stage halo GRU).
 static Launch make_conv_alt(const TList& t, const IList& i, double alpha, const at::Tensor& x_alt,
-                            std::vector<at::Tensor>* keep) {
+                            std::vector<at::Tensor>& keep) {
   if (i.size() >= 22 && (i[20] & 255) >= kHaloCfg0) {   // halo kernel: two launch closures (cfg bits 8+: igemm variants)
     TList t2 = t.copy();
     t2.set(0, c10::optional<at::Tensor>(x_alt));
@@ -340,7 +331,7 @@ static Launch make_conv_alt(const TList& t, const IList& i, double alpha, const 
   TORCH_CHECK(x_alt.sizes() == x.sizes(), "conv_alt: x_alt must have x's shape");
   ConvParams q = p;
   q.x = x_alt.data_ptr();
-  if (keep) keep->push_back(x_alt);
+  keep.push_back(x_alt);
   return [p, q, epi, cfg](hipStream_t s, int it) { return jr_conv_forward((it & 1) ? &q : &p, cfg, epi, s); };
 }
 
@@ -348,7 +339,7 @@ static Launch make_conv_alt(const TList& t, const IList& i, double alpha, const 
 // conv_grouped_kernel; configs of conv_fam_grp.hip), e.g. the one-lane loop's convcorr2 +
 // convflow2 at batch 1.
 static Launch make_conv_group(const TList& t1, const IList& i1, double a1, const TList& t2, const IList& i2,
-                              double a2, std::vector<at::Tensor>* keep) {
+                              double a2, std::vector<at::Tensor>& keep) {
   int e1 = 0, c1 = 0, e2 = 0, c2 = 0;
   const ConvParams p1 = build_conv(t1, i1, a1, keep, nullptr, nullptr, &e1, &c1);
   const ConvParams p2 = build_conv(t2, i2, a2, keep, nullptr, nullptr, &e2, &c2);
@@ -363,7 +354,7 @@ static Launch make_conv_group(const TList& t1, const IList& i1, double a1, const
 // ix = [seg0.mode, seg0.gin_coff, seg0.mask_coff, seg0.valid, seg0.out_coff,  (same for seg1)]
 // Channel strides are the tensors' last dims.  GRU operands are [M][hidden]
 // (gdzr [M][2 hidden]); see BwdSeg (kernels.h) for the segment semantics.
-static void conv_train_extras(ConvParams& p, int epi, const TList& tx, const IList& ix, std::vector<at::Tensor>* keep) {
+static void conv_train_extras(ConvParams& p, int epi, const TList& tx, const IList& ix, std::vector<at::Tensor>& keep) {
   TORCH_CHECK(tx.size() == 15 && ix.size() == 10, "conv_train: expected 15 tensors and 10 ints");
   std::vector<at::Tensor> ts;
   for (size_t k = 0; k < 15; ++k) ts.push_back(opt(tx, k));
@@ -421,7 +412,7 @@ static void conv_train_extras(ConvParams& p, int epi, const TList& tx, const ILi
         TORCH_CHECK(g.out_f32 && g.out_cs == hd && g.out_coff == 0, "conv_train: GRU segment output is fp32 [M][hidden]");
         if (g.mode == 2) TORCH_CHECK(!gin.defined(), "conv_train: reset-gate segment takes no gradient input");
       }
-      if (keep) for (auto* v : {&gin, &mask, &out}) if (v->defined()) keep->push_back(*v);
+      for (auto* v : {&gin, &mask, &out}) if (v->defined()) keep.push_back(*v);
     }
     if (gru) {
       TORCH_CHECK(hd > 0, "conv_train: GRU segment needs hidden > 0");
@@ -434,20 +425,19 @@ static void conv_train_extras(ConvParams& p, int epi, const TList& tx, const ILi
       p.ghp = ts[6].data_ptr<float>(); p.gdq = ptr(ts[7]); p.gdzr = ts[8].data_ptr();
     }
   }
-  if (keep) for (auto& v : ts) if (v.defined()) keep->push_back(v);
+  for (auto& v : ts) if (v.defined()) keep.push_back(v);
 }
 
 // t = [mask, flow, gout, dmask, taps], i = [B, h, w], alpha
-static Launch make_upsample_convex_bwd(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>* keep) {
+static Launch make_upsample_convex_bwd(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>& keep) {
   at::Tensor mask = opt(t, 0), flow = opt(t, 1), g = opt(t, 2), dm = opt(t, 3), taps = opt(t, 4);
-  TORCH_CHECK(i.size() == 3, "upsample_convex_bwd: expected 3 ints");
   check_bf16(mask, "mask"); check_f32(flow, "flow"); check_f32(g, "gout"); check_bf16(dm, "dmask"); check_f32(taps, "taps");
   const int B = (int)i[0], h = (int)i[1], w = (int)i[2];
   const int64_t M = (int64_t)B * h * w;
   TORCH_CHECK(cs(mask) >= 576 && mask.numel() >= M * cs(mask), "upsample_convex_bwd: mask [M][>=576]");
   TORCH_CHECK(cs(dm) >= 576 && dm.numel() >= M * cs(dm), "upsample_convex_bwd: dmask [M][>=576]");
   TORCH_CHECK(flow.numel() >= 2 * M && g.numel() >= 128 * M && taps.numel() >= 18 * M, "upsample_convex_bwd: sizes");
-  if (keep) for (auto& v : {mask, flow, g, dm, taps}) keep->push_back(v);
+  for (auto& v : {mask, flow, g, dm, taps}) keep.push_back(v);
   const void* mp = mask.data_ptr();
   const float* fp = flow.data_ptr<float>();
   const float* gp = g.data_ptr<float>();
@@ -459,10 +449,9 @@ static Launch make_upsample_convex_bwd(const TList& t, const IList& i, double al
 }
 
 // t = [gout, om?, y, stats?, gamma?, beta?, red?, partial?, dy, gres?], i = [mode, relu, N, HW, C]
-static Launch make_norm_bwd(const TList& t, const IList& i, double eps, std::vector<at::Tensor>* keep) {
+static Launch make_norm_bwd(const TList& t, const IList& i, double eps, std::vector<at::Tensor>& keep) {
   at::Tensor g = opt(t, 0), om = opt(t, 1), y = opt(t, 2), st = opt(t, 3), gam = opt(t, 4), bet = opt(t, 5);
   at::Tensor red = opt(t, 6), part = opt(t, 7), dy = opt(t, 8), gres = opt(t, 9);
-  TORCH_CHECK(i.size() == 5, "norm_bwd: expected [mode, relu, N, HW, C]");
   const int mode = (int)i[0], relu = (int)i[1], N = (int)i[2], HW = (int)i[3], C = (int)i[4];
   const int64_t n = (int64_t)N * HW * C;
   TORCH_CHECK(mode >= 0 && mode <= 2 && C % 8 == 0 && C <= 2048, "norm_bwd: mode 0..2, C % 8 == 0");
@@ -486,7 +475,7 @@ static Launch make_norm_bwd(const TList& t, const IList& i, double eps, std::vec
     TORCH_CHECK(part.numel() >= need, "norm_bwd: partial workspace too small");
   }
   for (auto* v : {&gam, &bet}) if (v->defined()) { check_f32(*v, "affine"); TORCH_CHECK(v->numel() >= C, "norm_bwd: affine"); }
-  if (keep) for (auto& v : {g, om, y, st, gam, bet, red, part, dy, gres}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {g, om, y, st, gam, bet, red, part, dy, gres}) if (v.defined()) keep.push_back(v);
   auto fp = [](const at::Tensor& v) -> float* { return v.defined() ? v.data_ptr<float>() : nullptr; };
   const void *gp = g.data_ptr(), *op = ptr(om), *yp = y.data_ptr();
   const float *sp = fp(st), *gmp = fp(gam), *btp = fp(bet);
@@ -501,12 +490,11 @@ static Launch make_norm_bwd(const TList& t, const IList& i, double eps, std::vec
 }
 
 // t = [table (int64 [n][16] device), *sources, *destinations (kept alive)], i = [n, max_elems]
-static Launch make_pack(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_pack(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor tab = opt(t, 0);
-  TORCH_CHECK(i.size() == 2, "pack: expected [n, max_elems]");
   TORCH_CHECK(tab.defined() && tab.is_cuda() && tab.is_contiguous() && tab.scalar_type() == at::kLong &&
                   tab.numel() == i[0] * 16, "pack: table must be a contiguous int64 [n][16] GPU tensor");
-  if (keep) for (size_t k = 0; k < t.size(); ++k) { at::Tensor v = opt(t, k); if (v.defined()) keep->push_back(v); }
+  for (size_t k = 0; k < t.size(); ++k) { at::Tensor v = opt(t, k); if (v.defined()) keep.push_back(v); }
   const void* tp = tab.data_ptr();
   const int n = (int)i[0];
   const long me = (long)i[1];
@@ -515,9 +503,8 @@ static Launch make_pack(const TList& t, const IList& i, std::vector<at::Tensor>*
 
 // t = [x, dy, dw (fp32 HWIO), db?, part?, bpart?],
 // i = [N, H, W, xoff, cin8, KH, KW, SH, SW, PH, PW, yoff, OH, OW, cout, cin]
-static Launch make_wgrad(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_wgrad(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor x = opt(t, 0), dy = opt(t, 1), dw = opt(t, 2), db = opt(t, 3), part = opt(t, 4), bpart = opt(t, 5);
-  TORCH_CHECK(i.size() == 16, "wgrad: expected 16 ints");
   check_bf16(x, "x"); check_bf16(dy, "dy"); check_f32(dw, "dw");
   const int N = (int)i[0], H = (int)i[1], W = (int)i[2], xoff = (int)i[3], cin8 = (int)i[4], KH = (int)i[5];
   const int KW = (int)i[6], SH = (int)i[7], SW = (int)i[8], PH = (int)i[9], PW = (int)i[10], yoff = (int)i[11];
@@ -537,7 +524,7 @@ static Launch make_wgrad(const TList& t, const IList& i, std::vector<at::Tensor>
   if (!bpart.defined()) bpart = at::empty({(int64_t)S * cp}, dw.options());
   check_f32(part, "part"); check_f32(bpart, "bpart");
   TORCH_CHECK(part.numel() >= (int64_t)S * cp * kp && bpart.numel() >= (int64_t)S * cp, "wgrad: workspace");
-  if (keep) for (auto& v : {x, dy, dw, db, part, bpart}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {x, dy, dw, db, part, bpart}) if (v.defined()) keep.push_back(v);
   const void *xp = x.data_ptr(), *yp = dy.data_ptr();
   float *dwp = dw.data_ptr<float>(), *dbp = db.defined() ? db.data_ptr<float>() : nullptr;
   float *pp = part.data_ptr<float>(), *bp = bpart.data_ptr<float>();
@@ -549,27 +536,25 @@ static Launch make_wgrad(const TList& t, const IList& i, std::vector<at::Tensor>
 }
 
 // t = [table (int64 [n][8] device), *referenced tensors (kept alive)], i = [n, max_c]
-static Launch make_bn_table(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_bn_table(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor tab = opt(t, 0);
-  TORCH_CHECK(i.size() == 2, "bn_table: expected [n, max_c]");
   TORCH_CHECK(tab.defined() && tab.is_cuda() && tab.is_contiguous() && tab.scalar_type() == at::kLong &&
                   tab.numel() == i[0] * 8, "bn_table: table must be a contiguous int64 [n][8] GPU tensor");
-  if (keep) for (size_t k = 0; k < t.size(); ++k) { at::Tensor v = opt(t, k); if (v.defined()) keep->push_back(v); }
+  for (size_t k = 0; k < t.size(); ++k) { at::Tensor v = opt(t, k); if (v.defined()) keep.push_back(v); }
   const void* tp = tab.data_ptr();
   const int n = (int)i[0], mc = (int)i[1];
   return [=](hipStream_t s, int) { return jr_bn_table(tp, n, mc, s); };
 }
 
 // t = [taps, dflow], i = [N, h, w]
-static Launch make_flow_gather_bwd(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_flow_gather_bwd(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor taps = opt(t, 0), df = opt(t, 1);
-  TORCH_CHECK(i.size() == 3, "flow_gather_bwd: expected 3 ints");
   check_f32(taps, "taps"); check_bf16(df, "dflow");
   const int N = (int)i[0], h = (int)i[1], w = (int)i[2];
   const int64_t M = (int64_t)N * h * w;
   TORCH_CHECK(cs(taps) >= 18 && cs(taps) % 2 == 0 && taps.numel() >= M * cs(taps), "flow_gather_bwd: taps");
   TORCH_CHECK(cs(df) >= 2 && df.numel() >= M * cs(df), "flow_gather_bwd: dflow");
-  if (keep) { keep->push_back(taps); keep->push_back(df); }
+  keep.push_back(taps); keep.push_back(df);
   const float* tp = taps.data_ptr<float>();
   void* dp = df.data_ptr();
   const int tcs = cs(taps), dcs = cs(df);
@@ -577,14 +562,13 @@ static Launch make_flow_gather_bwd(const TList& t, const IList& i, std::vector<a
 }
 
 // t = [gout, dflow], i = [B, h, w]
-static Launch make_upsample_bilinear_bwd(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_upsample_bilinear_bwd(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor g = opt(t, 0), df = opt(t, 1);
-  TORCH_CHECK(i.size() == 3, "upsample_bilinear_bwd: expected 3 ints");
   check_f32(g, "gout"); check_bf16(df, "dflow");
   const int B = (int)i[0], h = (int)i[1], w = (int)i[2];
   const int64_t M = (int64_t)B * h * w;
   TORCH_CHECK(g.numel() >= 128 * M && cs(df) >= 2 && df.numel() >= M * cs(df), "upsample_bilinear_bwd: sizes");
-  if (keep) { keep->push_back(g); keep->push_back(df); }
+  keep.push_back(g); keep.push_back(df);
   const float* gp = g.data_ptr<float>();
   void* dp = df.data_ptr();
   const int dcs = cs(df);
@@ -595,10 +579,9 @@ static Launch make_upsample_bilinear_bwd(const TList& t, const IList& i, std::ve
 // ------------------------------------------------------------------ flow taps
 // t = [taps (fp32 [M][tcs]), bias (fp32 [2]), coords, flow32, hx, qx?, flow8?]
 // i = [N, h, w, hx_off, qx_off]
-static Launch make_flow_taps(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_flow_taps(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor tp = opt(t, 0), bias = opt(t, 1), coords = opt(t, 2), flow32 = opt(t, 3), hx = opt(t, 4), qx = opt(t, 5),
              f8 = opt(t, 6);
-  TORCH_CHECK(i.size() == 5, "flow_taps: expected 5 ints");
   check_f32(tp, "taps"); check_f32(bias, "bias"); check_f32(coords, "coords"); check_f32(flow32, "flow32");
   check_bf16(hx, "hx");
   const int N = (int)i[0], h = (int)i[1], w = (int)i[2], hx_off = (int)i[3], qx_off = (int)i[4];
@@ -608,7 +591,7 @@ static Launch make_flow_taps(const TList& t, const IList& i, std::vector<at::Ten
   TORCH_CHECK(hx.numel() >= M * cs(hx) && hx_off + 2 <= cs(hx), "flow_taps: hx");
   if (qx.defined()) { check_bf16(qx, "qx"); TORCH_CHECK(qx.numel() >= M * cs(qx) && qx_off + 2 <= cs(qx), "flow_taps: qx"); }
   if (f8.defined()) { check_bf16(f8, "flow8"); TORCH_CHECK(f8.numel() >= M * cs(f8) && cs(f8) >= 2, "flow_taps: flow8"); }
-  if (keep) for (auto& v : {tp, bias, coords, flow32, hx, qx, f8}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {tp, bias, coords, flow32, hx, qx, f8}) if (v.defined()) keep.push_back(v);
   const float* tpp = tp.data_ptr<float>();
   const float* bp = bias.data_ptr<float>();
   float* cp = coords.data_ptr<float>();
@@ -623,7 +606,7 @@ static Launch make_flow_taps(const TList& t, const IList& i, std::vector<at::Ten
     check_f32(fb, "flow32 (odd)");
     TORCH_CHECK(fb.numel() >= 2 * M, "flow_taps: odd-iteration flow32 [M][2]");
     f32b = fb.data_ptr<float>();
-    if (keep) keep->push_back(fb);
+    keep.push_back(fb);
   }
   return [=](hipStream_t s, int it) {
     float* f = (f32b && (it & 1)) ? f32b : f32p;
@@ -633,10 +616,9 @@ static Launch make_flow_taps(const TList& t, const IList& i, std::vector<at::Ten
 
 // t = [x (bf16 [M][cs]), wpk (bf16, pack_conv1x1), bias (fp32 [cout]), y (bf16 [M][ycs])],
 // i = [M, kvalid, kpad, cout, act, y_coff]
-static Launch make_conv1x1(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_conv1x1(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor x = opt(t, 0), wpk = opt(t, 1), bias = opt(t, 2), y = opt(t, 3);
   check_bf16(x, "x"); check_bf16(wpk, "wpk"); check_f32(bias, "bias"); check_bf16(y, "y");
-  TORCH_CHECK(i.size() == 6, "conv1x1: expected 6 ints");
   const int64_t M = i[0];
   const int kvalid = (int)i[1], kpad = (int)i[2], cout = (int)i[3], act = (int)i[4], ycoff = (int)i[5];
   TORCH_CHECK(cout % 64 == 0 && kpad % 32 == 0 && kvalid <= kpad && kvalid % 8 == 0 && kvalid <= cs(x),
@@ -649,7 +631,7 @@ static Launch make_conv1x1(const TList& t, const IList& i, std::vector<at::Tenso
   TORCH_CHECK(cs(y) % 8 == 0 && ycoff % 8 == 0 && ycoff + cout <= cs(y) && y.numel() >= M * cs(y) &&
                   reinterpret_cast<uintptr_t>(y.data_ptr()) % 16 == 0,
               "conv1x1: y [M][cs] with a 16-byte aligned cout-channel slice");
-  if (keep) { keep->push_back(x); keep->push_back(wpk); keep->push_back(bias); keep->push_back(y); }
+  keep.push_back(x); keep.push_back(wpk); keep.push_back(bias); keep.push_back(y);
   const void* xp = x.data_ptr();
   const void* wp = wpk.data_ptr();
   const float* bp = bias.data_ptr<float>();
@@ -672,11 +654,10 @@ bool gru_fused_fits(int64_t H, int64_t W, int64_t vertical) {
 // i = [N, H, W, vertical(, g2all)].  Tiles: a row (1x5, W <= 128) or J = 2 / 1 columns (5x1, J * H <= 128).
 // g2all (default 1): GEMM 2 on all 16 waves with z through LDS; 0: on the 8 z waves, z in registers
 // (measured 334-341 vs 335 pairs/s at the headline, profiles/r3_gru_fused_ab.txt; kept for the tests).
-static Launch make_gru_fused(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_gru_fused(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor hx = opt(t, 0), wa = opt(t, 1), wb = opt(t, 2), bmap = opt(t, 3), h32 = opt(t, 4), y = opt(t, 5),
              y2 = opt(t, 6), dbg = opt(t, 7);
   check_bf16(hx, "hx"); check_bf16(wa, "wa"); check_bf16(wb, "wb"); check_f32(h32, "h32"); check_bf16(y, "y");
-  TORCH_CHECK(i.size() == 4 || i.size() == 5, "gru_fused: expected 4 or 5 ints");
   GruFusedParams p{};
   p.N = (int)i[0]; p.H = (int)i[1]; p.W = (int)i[2]; p.vertical = (int)i[3];
   p.g2all = i.size() == 5 ? (int)(i[4] != 0) : 1;
@@ -712,7 +693,7 @@ static Launch make_gru_fused(const TList& t, const IList& i, std::vector<at::Ten
   }
   p.hx_bytes = (long)hx.numel() * 2; p.wa_bytes = (long)wa.numel() * 2; p.wb_bytes = (long)wb.numel() * 2;
   TORCH_CHECK(p.hx_bytes < (1LL << 31), "gru_fused: hx larger than 2 GiB");
-  if (keep) for (auto& v : {hx, wa, wb, bmap, h32, y, y2}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {hx, wa, wb, bmap, h32, y, y2}) if (v.defined()) keep.push_back(v);
   // optional t[8]: the y2 copy of ODD loop iterations (a parity-buffered h copy for the mask lane,
   // runtime/engine.py: the lane reads iteration i's copy while iteration i+1 writes the other one)
   at::Tensor y2b = opt(t, 8);
@@ -723,7 +704,7 @@ static Launch make_gru_fused(const TList& t, const IList& i, std::vector<at::Ten
                 "gru_fused: odd-iteration y2 must have y2's shape");
     GruFusedParams q = p;
     q.y2 = y2b.data_ptr();
-    if (keep) keep->push_back(y2b);
+    keep.push_back(y2b);
     return [p, q](hipStream_t s, int it) { return jr_gru_fused((it & 1) ? &q : &p, s); };
   }
   return [p](hipStream_t s, int) { return jr_gru_fused(&p, s); };
@@ -745,12 +726,11 @@ bool gru_halo_geom_ok(int64_t hd, int64_t mode, int64_t TR, int64_t TC, int64_t 
          jr_gru_halo_lds((int)hd, (int)mode, (int)TR, (int)TC, (int)nb1, (int)nb2) <= 160 * 1024;
 }
 
-static Launch make_gru_halo(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_gru_halo(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor hs = opt(t, 0), xs = opt(t, 1), wa = opt(t, 2), wb = opt(t, 3), bmap = opt(t, 4), h32 = opt(t, 5),
              y = opt(t, 6), y2 = opt(t, 7);
   check_bf16(hs, "hsrc"); check_bf16(xs, "xsrc"); check_bf16(wa, "wa"); check_bf16(wb, "wb"); check_bf16(bmap, "bmap");
   check_f32(h32, "h32"); check_bf16(y, "y");
-  TORCH_CHECK(i.size() == 9, "gru_halo: expected [N, H, W, mode, axis, TR, TC, nb1, nb2]");
   GruHaloParams p{};
   p.N = (int)i[0]; p.H = (int)i[1]; p.W = (int)i[2]; p.mode = (int)i[3]; p.axis = (int)i[4];
   p.TR = (int)i[5]; p.TC = (int)i[6]; p.nb1 = (int)i[7]; p.nb2 = (int)i[8];
@@ -793,7 +773,7 @@ static Launch make_gru_halo(const TList& t, const IList& i, std::vector<at::Tens
   p.ntiles = (int)nt;
   p.src_bytes = (long)hs.numel() * 2; p.wa_bytes = (long)wa.numel() * 2; p.wb_bytes = (long)wb.numel() * 2;
   TORCH_CHECK(p.src_bytes < (1LL << 31), "gru_halo: loop buffers larger than 2 GiB");
-  if (keep) for (auto& v : {hs, xs, wa, wb, bmap, h32, y, y2}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {hs, xs, wa, wb, bmap, h32, y, y2}) if (v.defined()) keep.push_back(v);
   // optional t[11..15] (training forward, train/fused.py): h32in (fp32 [M][hd]: h is read there and
   // h' written to h32), and the saved gates zo / ro / qo (bf16 [M][hd]) + r*h into rh (bf16 [M][>= hd])
   {
@@ -803,7 +783,7 @@ static Launch make_gru_halo(const TList& t, const IList& i, std::vector<at::Tens
       TORCH_CHECK(cs(h32in) == hd && h32in.numel() >= M * hd && h32in.data_ptr() != h32.data_ptr() &&
                       reinterpret_cast<uintptr_t>(h32in.data_ptr()) % 16 == 0, "gru_halo: h32in [M][hd], not h32");
       p.h32in = h32in.data_ptr<float>();
-      if (keep) keep->push_back(h32in);
+      keep.push_back(h32in);
     }
     const bool any = zo.defined() || ro.defined() || qo.defined() || rh.defined();
     if (any) {
@@ -818,7 +798,7 @@ static Launch make_gru_halo(const TList& t, const IList& i, std::vector<at::Tens
                       reinterpret_cast<uintptr_t>(rh.data_ptr()) % 16 == 0 && rh.data_ptr() != hs.data_ptr() &&
                       rh.data_ptr() != xs.data_ptr(), "gru_halo: rh [M][>= hd], not a source");
       p.zo = zo.data_ptr(); p.ro = ro.data_ptr(); p.qo = qo.data_ptr(); p.rh = rh.data_ptr(); p.rh_cs = cs(rh);
-      if (keep) for (auto& v : {zo, ro, qo, rh}) keep->push_back(v);
+      for (auto& v : {zo, ro, qo, rh}) keep.push_back(v);
     }
   }
   // optional t[8..10] = hsrc / xsrc / y of ODD loop iterations: a single-stage GRU (raft_small)
@@ -834,17 +814,16 @@ static Launch make_gru_halo(const TList& t, const IList& i, std::vector<at::Tens
     TORCH_CHECK(hs2.data_ptr() != y_2.data_ptr(), "gru_halo: odd-iteration y must not alias its hsrc");
     GruHaloParams q = p;
     q.hsrc = hs2.data_ptr(); q.xsrc = xs2.data_ptr(); q.y = y_2.data_ptr(); q.y_cs = cs(y_2);
-    if (keep) for (auto& v : {hs2, xs2, y_2}) keep->push_back(v);
+    for (auto& v : {hs2, xs2, y_2}) keep.push_back(v);
     return [p, q](hipStream_t s, int it) { return jr_gru_halo((it & 1) ? &q : &p, s); };
   }
   return [p](hipStream_t s, int) { return jr_gru_halo(&p, s); };
 }
 
 // t = [fm (bf16 [M][cs]), wpk (bf16, pack_taps), taps (fp32 [M][>=24])], i = [M, K, fcoff]
-static Launch make_taps_gemm(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_taps_gemm(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor fm = opt(t, 0), wpk = opt(t, 1), taps = opt(t, 2);
   check_bf16(fm, "fm"); check_bf16(wpk, "wpk"); check_f32(taps, "taps");
-  TORCH_CHECK(i.size() == 3, "taps_gemm: expected 3 ints");
   const int64_t M = i[0];
   const int K = (int)i[1], fcoff = (int)i[2];
   TORCH_CHECK(K == 128 || K == 256, "taps_gemm: K must be 128 or 256");
@@ -856,7 +835,7 @@ static Launch make_taps_gemm(const TList& t, const IList& i, std::vector<at::Ten
   TORCH_CHECK(cs(taps) >= 24 && cs(taps) % 4 == 0 && taps.numel() >= M * cs(taps) &&
                   reinterpret_cast<uintptr_t>(taps.data_ptr()) % 16 == 0,
               "taps_gemm: taps [M][>=24], 16-byte rows");
-  if (keep) { keep->push_back(fm); keep->push_back(wpk); keep->push_back(taps); }
+  keep.push_back(fm); keep.push_back(wpk); keep.push_back(taps);
   const void* fp = fm.data_ptr();
   const void* wp = wpk.data_ptr();
   float* tp = taps.data_ptr<float>();
@@ -867,9 +846,8 @@ static Launch make_taps_gemm(const TList& t, const IList& i, std::vector<at::Ten
 // ---------------------------------------------------------------- direct conv
 // t = [x (bf16 NHWC, 2 channels used), w (bf16 A fragments [cout/16][NKC][64][8]), bias (fp32 [cout]), y (bf16)]
 // i = [N, H, W, cin, KH, KW, PH, PW, cout, relu, y_coff]   (stride 1, output H x W)
-static Launch make_conv_direct(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_conv_direct(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor x = opt(t, 0), w = opt(t, 1), bias = opt(t, 2), y = opt(t, 3);
-  TORCH_CHECK(i.size() == 11, "conv_direct: expected 11 ints");
   check_bf16(x, "x"); check_bf16(w, "w"); check_f32(bias, "bias"); check_bf16(y, "y");
   const int N = (int)i[0], H = (int)i[1], W = (int)i[2], cin = (int)i[3], KH = (int)i[4], KW = (int)i[5];
   const int PH = (int)i[6], PW = (int)i[7], cout = (int)i[8], relu = (int)i[9], y_coff = (int)i[10];
@@ -878,7 +856,7 @@ static Launch make_conv_direct(const TList& t, const IList& i, std::vector<at::T
   const int kwp = KW <= 4 ? 4 : 8, nkc = (KH * kwp * 2 + 31) / 32;
   TORCH_CHECK(cin == 2 && w.numel() == (int64_t)cout * nkc * 32 && bias.numel() >= cout, "conv_direct: w / bias");
   TORCH_CHECK(y.numel() >= M * cs(y) && y_coff + cout <= cs(y), "conv_direct: y");
-  if (keep) for (auto& v : {x, w, bias, y}) keep->push_back(v);
+  for (auto& v : {x, w, bias, y}) keep.push_back(v);
   const void* xp = x.data_ptr();
   const void* wp = w.data_ptr();
   const float* bp = bias.data_ptr<float>();
@@ -898,7 +876,7 @@ static Launch make_conv_direct(const TList& t, const IList& i, std::vector<at::T
 // i = [conv_direct's 11 ints, mode, stride, slot_off, feat_coff,  (M, kvalid, kpad, cout, act, ycoff)?]
 // With the conv1x1 operands (mode 2): the correlation features' 1x1 conv runs in the same grid,
 // every iteration (iteration 0: with the flow conv alone).
-static Launch make_flowin_dual(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>* keep) {
+static Launch make_flowin_dual(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>& keep) {
   Launch conv = make_conv_direct(t, IList(i.begin(), i.begin() + 11), keep);
   TORCH_CHECK((i.size() == 15 || i.size() == 21) && i[4] == 7 && i[5] == 7,
               "flowin_dual: expected 15 (+6) ints, a 7x7 flow conv");
@@ -935,7 +913,7 @@ static Launch make_flowin_dual(const TList& t, const IList& i, double alpha, std
     TORCH_CHECK(wpk.numel() == 576 * 256 && cb.numel() == 576 && reinterpret_cast<uintptr_t>(out.data_ptr()) % 32 == 0,
                 "flowin_dual: convex head operands");
   }
-  if (keep) for (auto& v : {flow, out, slot, feat, wpk, cb}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {flow, out, slot, feat, wpk, cb}) if (v.defined()) keep.push_back(v);
   const void* xp = x.data_ptr();
   const void* wp = w.data_ptr();
   const float* bp = bias.data_ptr<float>();
@@ -970,7 +948,7 @@ static void check_level(const at::Tensor& v, at::ScalarType dt) {
   TORCH_CHECK(v.scalar_type() == dt && (dt == at::kFloat || dt == at::kBFloat16), "pyramid levels: fp32 or bf16, one dtype");
 }
 
-static Launch make_corr(const TList& t, const IList& i, double scale, std::vector<at::Tensor>* keep) {
+static Launch make_corr(const TList& t, const IList& i, double scale, std::vector<at::Tensor>& keep) {
   at::Tensor f1 = opt(t, 0), f2 = opt(t, 1);
   check_bf16(f1, "f1"); check_bf16(f2, "f2");
   const int B = (int)i[0], h = (int)i[1], w = (int)i[2], C = (int)i[3], L = (int)i[4];
@@ -997,10 +975,10 @@ static Launch make_corr(const TList& t, const IList& i, double scale, std::vecto
     const int64_t per_q = (blocked && l < 2) ? (int64_t)nty * ntx * (128 >> (2 * l)) : (int64_t)hl * wl;
     TORCH_CHECK(v.numel() >= (int64_t)B * nq * per_q, "corr: level ", l, " too small");
     lv[l] = v.data_ptr();
-    if (keep) keep->push_back(v);
+    keep.push_back(v);
     hl >>= 1; wl >>= 1;
   }
-  if (keep) { keep->push_back(f1); keep->push_back(f2); }
+  keep.push_back(f1); keep.push_back(f2);
   const void* a = f1.data_ptr();
   const void* b = f2.data_ptr();
   const int fcs = cs(f1);
@@ -1012,7 +990,7 @@ static Launch make_corr(const TList& t, const IList& i, double scale, std::vecto
 }
 
 // t = [coords, out, l0, l1, l2, l3], i = [num_levels, B, h, w, radius]
-static Launch make_lookup(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_lookup(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor coords = opt(t, 0), out = opt(t, 1);
   check_f32(coords, "coords"); check_bf16(out, "out");
   const int L = (int)i[0], B = (int)i[1], h = (int)i[2], w = (int)i[3], r = (int)i[4];
@@ -1035,10 +1013,10 @@ static Launch make_lookup(const TList& t, const IList& i, std::vector<at::Tensor
     const int64_t per_q = (blocked && l < 2) ? (int64_t)nty * ntx * (128 >> (2 * l)) : (int64_t)hl * wl;
     TORCH_CHECK(v.numel() >= (int64_t)B * nq * per_q, "lookup: level size");
     lv[l] = v.data_ptr();
-    if (keep) keep->push_back(v);
+    keep.push_back(v);
     hl >>= 1; wl >>= 1;
   }
-  if (keep) { keep->push_back(coords); keep->push_back(out); }
+  keep.push_back(coords); keep.push_back(out);
   const float* cp = coords.data_ptr<float>();
   void* op = out.data_ptr();
   const int ocs = cs(out);
@@ -1060,7 +1038,7 @@ static Launch make_lookup(const TList& t, const IList& i, std::vector<at::Tensor
     if (f8.defined()) { check_bf16(f8, "flow8"); TORCH_CHECK(f8.numel() >= M * cs(f8) && cs(f8) >= 2, "lookup: flow8"); }
     upd = TapsUpd{tp.data_ptr<float>(), cs(tp), bias.data_ptr<float>(), coords.data_ptr<float>(), f32.data_ptr<float>(),
                   hx.data_ptr(), cs(hx), hx_off, ptr(qx), cs(qx), qx_off, ptr(f8), cs(f8), 1};
-    if (keep) for (auto& v : {tp, bias, f32, hx, qx, f8}) if (v.defined()) keep->push_back(v);
+    for (auto& v : {tp, bias, f32, hx, qx, f8}) if (v.defined()) keep.push_back(v);
   }
   // optional t[12]: flow32 of ODD iterations (parity-buffered for the mask lane's convex head)
   float* f32b = nullptr;
@@ -1069,7 +1047,7 @@ static Launch make_lookup(const TList& t, const IList& i, std::vector<at::Tensor
     check_f32(fb, "flow32 (odd)");
     TORCH_CHECK(fb.numel() >= (int64_t)B * nq * 2, "lookup: odd-iteration flow32 [M][2]");
     f32b = fb.data_ptr<float>();
-    if (keep) keep->push_back(fb);
+    keep.push_back(fb);
   }
   return [=](hipStream_t s, int it) {
     TapsUpd u = upd;
@@ -1094,14 +1072,14 @@ static int64_t check_flow_out(const at::Tensor& out, int B, int h, int w) {
 }
 
 // t = [mask, flow, out], i = [B, h, w, out_iter_stride]
-static Launch make_upsample_convex(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_upsample_convex(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor mask = opt(t, 0), flow = opt(t, 1), out = opt(t, 2);
   check_bf16(mask, "mask"); check_f32(flow, "flow");
   const int B = (int)i[0], h = (int)i[1], w = (int)i[2];
   const int64_t stride = i[3];
   TORCH_CHECK(cs(mask) >= 576, "upsample: mask needs 576 channels");
   const int64_t cap = check_flow_out(out, B, h, w);
-  if (keep) { keep->push_back(mask); keep->push_back(flow); keep->push_back(out); }
+  keep.push_back(mask); keep.push_back(flow); keep.push_back(out);
   const void* mp = mask.data_ptr();
   const float* fp = flow.data_ptr<float>();
   float* op = out.data_ptr<float>();
@@ -1116,10 +1094,9 @@ static Launch make_upsample_convex(const TList& t, const IList& i, std::vector<a
 // t = [feat, wpk, bias, flow, out, out_slot?], i = [B, h, w, feat_coff, out_iter_stride(, tiles per wave: 0 =
 // auto(, out_slot offset in floats))].  out_slot: device int64 holding the output base address at run time
 // (the engine points it at a fresh tensor per call); `out` (same shape) bounds the writes.
-static Launch make_convex_head(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>* keep) {
+static Launch make_convex_head(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>& keep) {
   at::Tensor feat = opt(t, 0), wpk = opt(t, 1), bias = opt(t, 2), flow = opt(t, 3), out = opt(t, 4), slot = opt(t, 5);
   check_bf16(feat, "feat"); check_bf16(wpk, "wpk"); check_f32(bias, "bias"); check_f32(flow, "flow");
-  TORCH_CHECK(i.size() >= 5 && i.size() <= 7, "convex_head: expected 5 to 7 ints");
   const int tiles = i.size() >= 6 ? (int)i[5] : 0;
   const int64_t slot_off = i.size() >= 7 ? i[6] : 0;
   TORCH_CHECK(!slot.defined() || (slot.is_cuda() && slot.scalar_type() == at::kLong && slot.numel() == 1),
@@ -1139,8 +1116,8 @@ static Launch make_convex_head(const TList& t, const IList& i, double alpha, std
   TORCH_CHECK(stride >= 0 && stride % 8 == 0, "convex_head: iteration stride");
   const int64_t cap = check_flow_out(out, B, h, w);
   TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 32 == 0, "convex_head: out must be 32-byte aligned");
-  if (keep) { keep->push_back(feat); keep->push_back(wpk); keep->push_back(bias); keep->push_back(flow); keep->push_back(out); }
-  if (keep && slot.defined()) keep->push_back(slot);
+  keep.push_back(feat); keep.push_back(wpk); keep.push_back(bias); keep.push_back(flow); keep.push_back(out);
+  if (slot.defined()) keep.push_back(slot);
   const void* sp = slot.defined() ? slot.data_ptr() : nullptr;
   const void* fp = feat.data_ptr();
   const void* wp = wpk.data_ptr();
@@ -1155,7 +1132,7 @@ static Launch make_convex_head(const TList& t, const IList& i, double alpha, std
     check_f32(fb, "flow (odd)");
     TORCH_CHECK(fb.numel() >= 2 * M, "convex_head: odd flow [M][2]");
     flb = fb.data_ptr<float>();
-    if (keep) keep->push_back(fb);
+    keep.push_back(fb);
   }
   return [=](hipStream_t s, int it) {
     const int64_t off = stride * it;
@@ -1167,7 +1144,7 @@ static Launch make_convex_head(const TList& t, const IList& i, double alpha, std
 
 // t = [flow, out], i = [B, h, w, out_iter_stride]
 // (t[2]: optional out_slot, i[4]: its offset in floats; see make_convex_head)
-static Launch make_upsample_bilinear(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_upsample_bilinear(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor flow = opt(t, 0), out = opt(t, 1), slot = opt(t, 2);
   check_f32(flow, "flow");
   const int B = (int)i[0], h = (int)i[1], w = (int)i[2];
@@ -1176,7 +1153,7 @@ static Launch make_upsample_bilinear(const TList& t, const IList& i, std::vector
   TORCH_CHECK(!slot.defined() || (slot.is_cuda() && slot.scalar_type() == at::kLong && slot.numel() == 1),
               "upsample_bilinear: out_slot must be one device int64");
   const int64_t cap = check_flow_out(out, B, h, w);
-  if (keep) { keep->push_back(flow); keep->push_back(out); if (slot.defined()) keep->push_back(slot); }
+  keep.push_back(flow); keep.push_back(out); if (slot.defined()) keep.push_back(slot);
   const float* fp = flow.data_ptr<float>();
   float* op = out.data_ptr<float>();
   const void* sp = slot.defined() ? slot.data_ptr() : nullptr;
@@ -1190,7 +1167,7 @@ static Launch make_upsample_bilinear(const TList& t, const IList& i, std::vector
 // ---------------------------------------------------------------------- norm
 // t = [x, stats, partial?], i = [N, HW, C]; the partial workspace is allocated
 // here when not given (eager use), never inside a launch (capture safety).
-static Launch make_stats(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_stats(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor x = opt(t, 0), st = opt(t, 1), part = opt(t, 2);
   check_bf16(x, "x"); check_f32(st, "stats");
   const int N = (int)i[0], HW = (int)i[1], C = (int)i[2];
@@ -1204,7 +1181,7 @@ static Launch make_stats(const TList& t, const IList& i, std::vector<at::Tensor>
   if (!part.defined()) part = at::empty({need}, st.options());
   check_f32(part, "partial");
   TORCH_CHECK(part.numel() >= need, "stats: partial workspace too small");
-  if (keep) { keep->push_back(x); keep->push_back(st); keep->push_back(part); }
+  keep.push_back(x); keep.push_back(st); keep.push_back(part);
   const void* xp = x.data_ptr();
   float* sp = st.data_ptr<float>();
   float* pp = part.data_ptr<float>();
@@ -1212,7 +1189,7 @@ static Launch make_stats(const TList& t, const IList& i, std::vector<at::Tensor>
 }
 
 // t = [x, sx, gx, bx, r, sr, gr, br, y], i = [mode_x, mode_r, N, HW, C, relu]
-static Launch make_norm_act(const TList& t, const IList& i, double eps, std::vector<at::Tensor>* keep) {
+static Launch make_norm_act(const TList& t, const IList& i, double eps, std::vector<at::Tensor>& keep) {
   at::Tensor x = opt(t, 0), sx = opt(t, 1), gx = opt(t, 2), bx = opt(t, 3);
   at::Tensor r = opt(t, 4), sr = opt(t, 5), gr = opt(t, 6), br = opt(t, 7), y = opt(t, 8);
   check_bf16(x, "x"); check_bf16(y, "y");
@@ -1222,7 +1199,7 @@ static Launch make_norm_act(const TList& t, const IList& i, double eps, std::vec
   if (mx) check_f32(sx, "sx");
   if (r.defined()) { check_bf16(r, "res"); TORCH_CHECK(cs(r) == C, "norm_act: residual channels"); if (mr) check_f32(sr, "sr"); }
   for (auto* v : {&gx, &bx, &gr, &br}) if (v->defined()) check_f32(*v, "affine");
-  if (keep) for (auto& v : {x, sx, gx, bx, r, sr, gr, br, y}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {x, sx, gx, bx, r, sr, gr, br, y}) if (v.defined()) keep.push_back(v);
   auto fp = [](const at::Tensor& v) -> const float* { return v.defined() ? v.data_ptr<float>() : nullptr; };
   const void* xp = x.data_ptr();
   const void* rp = ptr(r);
@@ -1238,7 +1215,7 @@ static Launch make_norm_act(const TList& t, const IList& i, double eps, std::vec
 // t = [img1, img2, out], i = [B, H, W]
 // uint8 frames: t = [img1, img2 (uint8 [B][H0][W0][3]), out, lut (fp32 [256])],
 // i = [B, H, W, s2d, H0, W0, pt, pl] (K14: normalise + replicate pad + layout, jr_prep_u8)
-static Launch make_prep_u8(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_prep_u8(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor a = opt(t, 0), b = opt(t, 1), out = opt(t, 2), lut = opt(t, 3);
   TORCH_CHECK(a.defined() && b.defined() && a.scalar_type() == at::kByte && b.scalar_type() == at::kByte &&
                   a.is_cuda() && b.is_cuda() && a.is_contiguous() && b.is_contiguous(), "prep: uint8 frames");
@@ -1254,7 +1231,7 @@ static Launch make_prep_u8(const TList& t, const IList& i, std::vector<at::Tenso
   } else {
     TORCH_CHECK(out.numel() >= 2LL * B * H * W * 8 && cs(out) == 8, "prep: output");
   }
-  if (keep) for (auto& v : {a, b, out, lut}) keep->push_back(v);
+  for (auto& v : {a, b, out, lut}) keep.push_back(v);
   const void* ap = a.data_ptr();
   const void* bp = b.data_ptr();
   const float* lp = lut.data_ptr<float>();
@@ -1262,7 +1239,7 @@ static Launch make_prep_u8(const TList& t, const IList& i, std::vector<at::Tenso
   return [=](hipStream_t s, int) { return jr_prep_u8(ap, bp, lp, B, H0, W0, H, W, pt, pl, s2d, op, s); };
 }
 
-static Launch make_prep(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_prep(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   if (opt(t, 0).defined() && opt(t, 0).scalar_type() == at::kByte) return make_prep_u8(t, i, keep);
   at::Tensor a = opt(t, 0), b = opt(t, 1), out = opt(t, 2);
   check_f32(a, "img1"); check_f32(b, "img2"); check_bf16(out, "out");
@@ -1274,7 +1251,7 @@ static Launch make_prep(const TList& t, const IList& i, std::vector<at::Tensor>*
   } else {
     TORCH_CHECK(out.numel() >= 2LL * B * H * W * 8 && cs(out) == 8, "prep: output");
   }
-  if (keep) { keep->push_back(a); keep->push_back(b); keep->push_back(out); }
+  keep.push_back(a); keep.push_back(b); keep.push_back(out);
   const float* ap = a.data_ptr<float>();
   const float* bp = b.data_ptr<float>();
   void* op = out.data_ptr();
@@ -1283,21 +1260,21 @@ static Launch make_prep(const TList& t, const IList& i, std::vector<at::Tensor>*
 }
 
 // t = [coords], i = [B, h, w]
-static Launch make_init_coords(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_init_coords(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor c = opt(t, 0);
   check_f32(c, "coords");
   const int B = (int)i[0], h = (int)i[1], w = (int)i[2];
   TORCH_CHECK(c.numel() >= (int64_t)B * h * w * 2, "init_coords: size");
-  if (keep) keep->push_back(c);
+  keep.push_back(c);
   float* cp = c.data_ptr<float>();
   return [=](hipStream_t s, int) { return jr_init_coords(cp, B, h, w, s); };
 }
 
 // t = [x]
-static Launch make_memset(const TList& t, std::vector<at::Tensor>* keep) {
+static Launch make_memset(const TList& t, std::vector<at::Tensor>& keep) {
   at::Tensor x = opt(t, 0);
   TORCH_CHECK(x.defined() && x.is_cuda() && x.is_contiguous(), "memset: tensor");
-  if (keep) keep->push_back(x);
+  keep.push_back(x);
   void* p = x.data_ptr();
   const size_t bytes = x.numel() * x.element_size();
   TORCH_CHECK(((uintptr_t)p & 15) == 0 && bytes % 4 == 0, "memset: 16-B aligned, 4-B multiple tensors only");
@@ -1305,11 +1282,11 @@ static Launch make_memset(const TList& t, std::vector<at::Tensor>* keep) {
 }
 
 // t = [src, dst]
-static Launch make_copy(const TList& t, std::vector<at::Tensor>* keep) {
+static Launch make_copy(const TList& t, std::vector<at::Tensor>& keep) {
   at::Tensor a = opt(t, 0), b = opt(t, 1);
   TORCH_CHECK(a.defined() && b.defined() && a.is_contiguous() && b.is_contiguous(), "copy: tensors");
   TORCH_CHECK(a.numel() * a.element_size() == b.numel() * b.element_size(), "copy: byte size mismatch");
-  if (keep) { keep->push_back(a); keep->push_back(b); }
+  keep.push_back(a); keep.push_back(b);
   const void* ap = a.data_ptr();
   void* bp = b.data_ptr();
   const size_t bytes = a.numel() * a.element_size();
@@ -1317,13 +1294,13 @@ static Launch make_copy(const TList& t, std::vector<at::Tensor>* keep) {
 }
 
 // t = [src, dst], i = [s_coff, d_coff, M, C]
-static Launch make_copy_channels(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_copy_channels(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor a = opt(t, 0), b = opt(t, 1);
   check_bf16(a, "src"); check_bf16(b, "dst");
   const int so = (int)i[0], dof = (int)i[1], M = (int)i[2], C = (int)i[3];
   TORCH_CHECK(so + C <= cs(a) && dof + C <= cs(b) && a.numel() >= (int64_t)M * cs(a) && b.numel() >= (int64_t)M * cs(b),
               "copy_channels: shape");
-  if (keep) { keep->push_back(a); keep->push_back(b); }
+  keep.push_back(a); keep.push_back(b);
   const void* ap = a.data_ptr();
   void* bp = b.data_ptr();
   const int acs = cs(a), bcs = cs(b);
@@ -1331,7 +1308,7 @@ static Launch make_copy_channels(const TList& t, const IList& i, std::vector<at:
 }
 
 // t = [a (bf16 [T][M][Ca]), b (bf16 [T][M][Cb]), out (bf16 [M][Ca + Cb])], i = [T, M]
-static Launch make_sum_iters(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_sum_iters(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor a = opt(t, 0), b = opt(t, 1), o = opt(t, 2);
   check_bf16(a, "a"); check_bf16(b, "b"); check_bf16(o, "out");
   const int T = (int)i[0];
@@ -1340,14 +1317,14 @@ static Launch make_sum_iters(const TList& t, const IList& i, std::vector<at::Ten
   TORCH_CHECK(T >= 1 && a.numel() == T * M * Ca && b.numel() == T * M * Cb && o.numel() == M * (Ca + Cb) &&
                   Ca % 8 == 0 && Cb % 8 == 0,
               "sum_iters: shapes");
-  if (keep) for (auto& v : {a, b, o}) keep->push_back(v);
+  for (auto& v : {a, b, o}) keep.push_back(v);
   const void *ap = a.data_ptr(), *bp = b.data_ptr();
   void* op = o.data_ptr();
   return [=](hipStream_t s, int) { return jr_sum_iters(ap, bp, T, (long)M, Ca, Cb, op, s); };
 }
 
 // t = [coords, gout, dl0, dl1, dl2, dl3], i = [num_levels, B, h, w, radius]
-static Launch make_lookup_bwd(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_lookup_bwd(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor coords = opt(t, 0), g = opt(t, 1);
   check_f32(coords, "coords");
   TORCH_CHECK(g.defined() && g.is_cuda() && g.is_contiguous() &&
@@ -1364,10 +1341,10 @@ static Launch make_lookup_bwd(const TList& t, const IList& i, std::vector<at::Te
     check_f32(v, "dlevel");
     TORCH_CHECK(v.numel() >= (int64_t)B * nq * hl * wl, "lookup_bwd: dlevel size");
     lv[l] = v.data_ptr();
-    if (keep) keep->push_back(v);
+    keep.push_back(v);
     hl >>= 1; wl >>= 1;
   }
-  if (keep) { keep->push_back(coords); keep->push_back(g); }
+  keep.push_back(coords); keep.push_back(g);
   const float* cp = coords.data_ptr<float>();
   const void* gp = g.data_ptr();
   const int gcs = cs(g);
@@ -1376,7 +1353,7 @@ static Launch make_lookup_bwd(const TList& t, const IList& i, std::vector<at::Te
 }
 
 // t = [x, col], i = [N, H, W, x_coff, cin8, KH, KW, SH, SW, PH, PW]
-static Launch make_im2col(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_im2col(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor x = opt(t, 0), col = opt(t, 1);
   check_bf16(x, "x"); check_bf16(col, "col");
   const int N = (int)i[0], H = (int)i[1], W = (int)i[2], xoff = (int)i[3], cin8 = (int)i[4];
@@ -1386,7 +1363,7 @@ static Launch make_im2col(const TList& t, const IList& i, std::vector<at::Tensor
   TORCH_CHECK(cin8 % 8 == 0 && xoff % 8 == 0 && cs(x) % 8 == 0 && xoff + cin8 <= cs(x), "im2col: input slice");
   TORCH_CHECK(kpad % 8 == 0 && kpad >= KH * KW * cin8, "im2col: kpad");
   TORCH_CHECK(x.numel() >= (int64_t)N * H * W * cs(x) && col.numel() >= (int64_t)N * OH * OW * kpad, "im2col: sizes");
-  if (keep) { keep->push_back(x); keep->push_back(col); }
+  keep.push_back(x); keep.push_back(col);
   const void* xp = x.data_ptr();
   void* cp = col.data_ptr();
   const int xcs = cs(x);
@@ -1405,8 +1382,7 @@ static void check_f32_min(const at::Tensor& t, const char* name, int64_t n) {
 // t = [x, w ([cout][K] fp32), bias, y, y2, res, h32, zbuf, bmap]
 // i = [N, H, W, x_coff, cin4, KH, KW, SH, SW, PH, PW, cout, act, split, y_coff, y2_coff, res_coff, res_post,
 //      hidden, bmap_coff, epi, ksplit (0: automatic, n > 0: forced n-way split-K)]
-static Launch make_conv_f32(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>* keep) {
-  TORCH_CHECK(i.size() == 22, "conv_f32: expected 22 ints");
+static Launch make_conv_f32(const TList& t, const IList& i, double alpha, std::vector<at::Tensor>& keep) {
   at::Tensor x = opt(t, 0), w = opt(t, 1), bias = opt(t, 2), y = opt(t, 3), y2 = opt(t, 4), res = opt(t, 5);
   at::Tensor h32 = opt(t, 6), zbuf = opt(t, 7), bmap = opt(t, 8);
   ConvF32Params p{};
@@ -1468,19 +1444,15 @@ static Launch make_conv_f32(const TList& t, const IList& i, double alpha, std::v
     if (S > 1) {
       at::Tensor part = at::empty({(int64_t)S * p.M * ((p.cout + 3) / 4 * 4)}, x.options());
       p.part = part.data_ptr<float>();
-      if (keep) keep->push_back(part);
-      else {   // eager op: keep the workspace alive until the stream has used it
-        auto launch = [=](hipStream_t s, int) { return jr_conv_f32(&p, epi, s); };
-        return [launch, part](hipStream_t s, int it) { return launch(s, it); };
-      }
+      keep.push_back(part);
     }
   }
-  if (keep) for (auto& v : {x, w, bias, y, y2, res, h32, zbuf, bmap}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {x, w, bias, y, y2, res, h32, zbuf, bmap}) if (v.defined()) keep.push_back(v);
   return [=](hipStream_t s, int) { return jr_conv_f32(&p, epi, s); };
 }
 
 // t = [x, stats, partial?], i = [N, HW, C]
-static Launch make_stats_f32(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_stats_f32(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor x = opt(t, 0), st = opt(t, 1), part = opt(t, 2);
   const int N = (int)i[0], HW = (int)i[1], C = (int)i[2];
   check_f32(x, "x");
@@ -1489,7 +1461,7 @@ static Launch make_stats_f32(const TList& t, const IList& i, std::vector<at::Ten
   const int64_t need = (int64_t)jr_channel_stats_partials(N, HW, C) * C * 2;
   if (!part.defined()) part = at::empty({need}, st.options());
   check_f32_min(part, "partial", need);
-  if (keep) for (auto& v : {x, st, part}) keep->push_back(v);
+  for (auto& v : {x, st, part}) keep.push_back(v);
   const float* xp = x.data_ptr<float>();
   float* sp = st.data_ptr<float>();
   float* pp = part.data_ptr<float>();
@@ -1497,7 +1469,7 @@ static Launch make_stats_f32(const TList& t, const IList& i, std::vector<at::Ten
 }
 
 // t = [x, sx, res, sr, y], i = [mode_x, mode_r, N, HW, C, relu]
-static Launch make_norm_act_f32(const TList& t, const IList& i, double eps, std::vector<at::Tensor>* keep) {
+static Launch make_norm_act_f32(const TList& t, const IList& i, double eps, std::vector<at::Tensor>& keep) {
   at::Tensor x = opt(t, 0), sx = opt(t, 1), r = opt(t, 2), sr = opt(t, 3), y = opt(t, 4);
   const int mx = (int)i[0], mr = (int)i[1], N = (int)i[2], HW = (int)i[3], C = (int)i[4], relu = (int)i[5];
   const int64_t n = (int64_t)N * HW * C;
@@ -1509,7 +1481,7 @@ static Launch make_norm_act_f32(const TList& t, const IList& i, double eps, std:
     TORCH_CHECK(cs(r) == C, "norm_act_f32: residual channels");
     if (mr) check_f32_min(sr, "sr", (int64_t)N * C * 2);
   }
-  if (keep) for (auto& v : {x, sx, r, sr, y}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {x, sx, r, sr, y}) if (v.defined()) keep.push_back(v);
   auto fp = [](const at::Tensor& v) -> float* { return v.defined() ? v.data_ptr<float>() : nullptr; };
   const float *xp = fp(x), *sxp = fp(sx), *rp = fp(r), *srp = fp(sr);
   float* yp = fp(y);
@@ -1518,26 +1490,26 @@ static Launch make_norm_act_f32(const TList& t, const IList& i, double eps, std:
 }
 
 // t = [img1, img2, out ([2B][H][W][4])], i = [B, H, W]
-static Launch make_prep_f32(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_prep_f32(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor a = opt(t, 0), b = opt(t, 1), out = opt(t, 2);
   const int B = (int)i[0], H = (int)i[1], W = (int)i[2];
   check_f32(a, "img1"); check_f32(b, "img2"); check_f32(out, "out");
   TORCH_CHECK(a.numel() == (int64_t)B * H * W * 3 && b.numel() == a.numel(), "prep_f32: image shape");
   TORCH_CHECK(out.numel() >= 2LL * B * H * W * 4 && cs(out) == 4, "prep_f32: output");
-  if (keep) for (auto& v : {a, b, out}) keep->push_back(v);
+  for (auto& v : {a, b, out}) keep.push_back(v);
   const float *ap = a.data_ptr<float>(), *bp = b.data_ptr<float>();
   float* op = out.data_ptr<float>();
   return [=](hipStream_t s, int) { return jr_prep_images_f32(ap, bp, B, H, W, op, s); };
 }
 
 // t = [src, dst], i = [s_coff, d_coff, M, C]
-static Launch make_copy_channels_f32(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_copy_channels_f32(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor a = opt(t, 0), b = opt(t, 1);
   check_f32(a, "src"); check_f32(b, "dst");
   const int so = (int)i[0], dof = (int)i[1], M = (int)i[2], C = (int)i[3];
   TORCH_CHECK(so + C <= cs(a) && dof + C <= cs(b) && a.numel() >= (int64_t)M * cs(a) && b.numel() >= (int64_t)M * cs(b),
               "copy_channels_f32: shape");
-  if (keep) { keep->push_back(a); keep->push_back(b); }
+  keep.push_back(a); keep.push_back(b);
   const float* ap = a.data_ptr<float>();
   float* bp = b.data_ptr<float>();
   const int acs = cs(a), bcs = cs(b);
@@ -1545,7 +1517,7 @@ static Launch make_copy_channels_f32(const TList& t, const IList& i, std::vector
 }
 
 // t = [mask (fp32 [M][>=576]), flow, out, out_slot?], i = [B, h, w, out_iter_stride(, slot offset)]
-static Launch make_upsample_convex_f32(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_upsample_convex_f32(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor mask = opt(t, 0), flow = opt(t, 1), out = opt(t, 2), slot = opt(t, 3);
   const int B = (int)i[0], h = (int)i[1], w = (int)i[2];
   const int64_t stride = i[3], slot_off = i.size() > 4 ? i[4] : 0;
@@ -1555,7 +1527,7 @@ static Launch make_upsample_convex_f32(const TList& t, const IList& i, std::vect
   TORCH_CHECK(!slot.defined() || (slot.is_cuda() && slot.scalar_type() == at::kLong && slot.numel() == 1),
               "upsample_convex_f32: out_slot must be one device int64");
   const int64_t cap = check_flow_out(out, B, h, w);
-  if (keep) for (auto& v : {mask, flow, out, slot}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {mask, flow, out, slot}) if (v.defined()) keep.push_back(v);
   const float *mp = mask.data_ptr<float>(), *fp = flow.data_ptr<float>();
   float* op = out.data_ptr<float>();
   const void* sp = slot.defined() ? slot.data_ptr() : nullptr;
@@ -1568,20 +1540,20 @@ static Launch make_upsample_convex_f32(const TList& t, const IList& i, std::vect
 }
 
 // t = [src ([M][hl][wl]), dst ([M][hl/2][wl/2])], i = [M, hl, wl]
-static Launch make_corr_pool_f32(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_corr_pool_f32(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor a = opt(t, 0), b = opt(t, 1);
   const int64_t M = i[0];
   const int hl = (int)i[1], wl = (int)i[2];
   TORCH_CHECK(hl >= 2 && wl >= 2, "corr_pool_f32: level too small");
   check_f32_min(a, "src", M * hl * wl); check_f32_min(b, "dst", M * (hl / 2) * (wl / 2));
-  if (keep) { keep->push_back(a); keep->push_back(b); }
+  keep.push_back(a); keep.push_back(b);
   const float* ap = a.data_ptr<float>();
   float* bp = b.data_ptr<float>();
   return [=](hipStream_t s, int) { return jr_corr_pool_f32(ap, (long)M, hl, wl, bp, s); };
 }
 
 // t = [coords, out, l0, l1, l2, l3], i = [num_levels, B, h, w, radius(, nq: queries per image, default h*w)]
-static Launch make_lookup_f32(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_lookup_f32(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor coords = opt(t, 0), out = opt(t, 1);
   const int L = (int)i[0], B = (int)i[1], h = (int)i[2], w = (int)i[3], r = (int)i[4];
   const int nq = i.size() > 5 ? (int)i[5] : h * w;
@@ -1599,10 +1571,10 @@ static Launch make_lookup_f32(const TList& t, const IList& i, std::vector<at::Te
     TORCH_CHECK(hl >= 2 && wl >= 2, "lookup_f32: pyramid level too small");
     check_f32_min(v, "level", M * hl * wl);
     lv[l] = v.data_ptr<float>();
-    if (keep) keep->push_back(v);
+    keep.push_back(v);
     hl >>= 1; wl >>= 1;
   }
-  if (keep) { keep->push_back(coords); keep->push_back(out); }
+  keep.push_back(coords); keep.push_back(out);
   const float* cp = coords.data_ptr<float>();
   float* op = out.data_ptr<float>();
   const int ocs = cs(out);
@@ -1610,7 +1582,7 @@ static Launch make_lookup_f32(const TList& t, const IList& i, std::vector<at::Te
 }
 
 // t = [delta ([M][dcs]), coords, flow32, hx, qx?, flow4?], i = [N, h, w, hx_off, qx_off]
-static Launch make_flow_update_f32(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_flow_update_f32(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor d = opt(t, 0), coords = opt(t, 1), f32 = opt(t, 2), hx = opt(t, 3), qx = opt(t, 4), f4 = opt(t, 5);
   const int N = (int)i[0], h = (int)i[1], w = (int)i[2], hx_off = (int)i[3], qx_off = (int)i[4];
   const int64_t M = (int64_t)N * h * w;
@@ -1621,7 +1593,7 @@ static Launch make_flow_update_f32(const TList& t, const IList& i, std::vector<a
   TORCH_CHECK(hx_off + 2 <= cs(hx) && hx.numel() >= M * cs(hx), "flow_update_f32: hx");
   if (qx.defined()) { check_f32(qx, "qx"); TORCH_CHECK(qx_off + 2 <= cs(qx) && qx.numel() >= M * cs(qx), "flow_update_f32: qx"); }
   if (f4.defined()) { check_f32_min(f4, "flow4", 4 * M); TORCH_CHECK(cs(f4) == 4, "flow_update_f32: flow4 [M][4]"); }
-  if (keep) for (auto& v : {d, coords, f32, hx, qx, f4}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {d, coords, f32, hx, qx, f4}) if (v.defined()) keep.push_back(v);
   auto fp = [](const at::Tensor& v) -> float* { return v.defined() ? v.data_ptr<float>() : nullptr; };
   const float* dp = fp(d);
   float *cp = fp(coords), *fl = fp(f32), *hp = fp(hx), *qp = fp(qx), *f4p = fp(f4);
@@ -1635,9 +1607,8 @@ static Launch make_flow_update_f32(const TList& t, const IList& i, std::vector<a
 // (kernels warm.hip).  The seed of a warm plan, in place of init_coords:
 // t = [flow_init (fp32 [M][2]), coords, flow32, hx, qx?, flow8? (bf16) | flow4? (fp32 [M][4])],
 // i = [N, h, w, hx_off, qx_off]; f32: the fp32 engine's buffers (flow_update_f32's state)
-static Launch make_init_flow(const TList& t, const IList& i, bool f32, std::vector<at::Tensor>* keep) {
+static Launch make_init_flow(const TList& t, const IList& i, bool f32, std::vector<at::Tensor>& keep) {
   at::Tensor fi = opt(t, 0), coords = opt(t, 1), flow32 = opt(t, 2), hx = opt(t, 3), qx = opt(t, 4), fz = opt(t, 5);
-  TORCH_CHECK(i.size() == 5, "init_flow: expected 5 ints");
   const int N = (int)i[0], h = (int)i[1], w = (int)i[2], hx_off = (int)i[3], qx_off = (int)i[4];
   TORCH_CHECK(N >= 1 && h >= 1 && w >= 1 && hx_off >= 0 && qx_off >= 0, "init_flow: sizes / offsets");
   const int64_t M = (int64_t)N * h * w;
@@ -1652,7 +1623,7 @@ static Launch make_init_flow(const TList& t, const IList& i, bool f32, std::vect
     check(fz, f32 ? "flow4" : "flow8");
     TORCH_CHECK(fz.numel() >= M * cs(fz) && (f32 ? cs(fz) == 4 : cs(fz) >= 2), "init_flow: flow8 [M][>=2] / flow4 [M][4]");
   }
-  if (keep) for (auto& v : {fi, coords, flow32, hx, qx, fz}) if (v.defined()) keep->push_back(v);
+  for (auto& v : {fi, coords, flow32, hx, qx, fz}) if (v.defined()) keep.push_back(v);
   const float* fip = fi.data_ptr<float>();
   float* cp = coords.data_ptr<float>();
   float* flp = flow32.data_ptr<float>();
@@ -1671,9 +1642,8 @@ static Launch make_init_flow(const TList& t, const IList& i, bool f32, std::vect
 
 // t = [flow (fp32 [B][h][w][2]), keys (int64 [2*B*h*w + 2], all ones when allocated), out (like flow)],
 // i = [B, h, w, fill_radius]
-static Launch make_forward_project(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_forward_project(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor flow = opt(t, 0), keys = opt(t, 1), out = opt(t, 2);
-  TORCH_CHECK(i.size() == 4, "forward_project: expected 4 ints");
   const int B = (int)i[0], h = (int)i[1], w = (int)i[2], R = (int)i[3];
   TORCH_CHECK(B >= 1 && h >= 1 && w >= 1 && (int64_t)h * w <= INT32_MAX, "forward_project: sizes");
   TORCH_CHECK(R >= 0 && R <= 8, "forward_project: fill_radius must be in [0, 8]");
@@ -1686,14 +1656,12 @@ static Launch make_forward_project(const TList& t, const IList& i, std::vector<a
   TORCH_CHECK(keys.defined() && keys.is_cuda() && keys.scalar_type() == at::kLong && keys.is_contiguous() &&
                   keys.numel() == 2 * M + 2,
               "forward_project: keys must be a contiguous device int64 [2*B*h*w + 2]");
-  if (keep) { keep->push_back(flow); keep->push_back(keys); keep->push_back(out); }
+  keep.push_back(flow); keep.push_back(keys); keep.push_back(out);
   const float* fp = flow.data_ptr<float>();
   void* kp = keys.data_ptr();
   float* op = out.data_ptr<float>();
   return [=](hipStream_t s, int) { return jr_forward_project(fp, kp, op, B, h, w, R, s); };
 }
-
-static void run_now(const Launch& l) { JR_CHECK_OK(l(cur_stream(), 0)); }
 
 // ------------------------------------------------------------- sequence loss
 // t = [pred (fp32 [N][P][2]), gt (fp32 [P][2]), valid? (fp32 [P]), part (fp32 [blocks][37])], i = [P, N]
@@ -1726,58 +1694,18 @@ void seq_loss_bwd_op(const TList& t, IList i, double max_flow) {
                               valid.defined() ? valid.data_ptr<float>() : nullptr, P, N, (float)max_flow,
                               scale.data_ptr<float>(), grad.data_ptr<float>(), cur_stream()));
 }
-
-// ---------------------------------------------------------------- eager ops
-void conv_op(const TList& t, IList i, double alpha) { run_now(make_conv(t, i, alpha, nullptr)); }
-void conv_f32_op(const TList& t, IList i, double alpha) { run_now(make_conv_f32(t, i, alpha, nullptr)); }
-void stats_f32_op(const TList& t, IList i) { run_now(make_stats_f32(t, i, nullptr)); }
-void norm_act_f32_op(const TList& t, IList i, double eps) { run_now(make_norm_act_f32(t, i, eps, nullptr)); }
-void prep_f32_op(const TList& t, IList i) { run_now(make_prep_f32(t, i, nullptr)); }
-void copy_channels_f32_op(const TList& t, IList i) { run_now(make_copy_channels_f32(t, i, nullptr)); }
-void upsample_convex_f32_op(const TList& t, IList i) { run_now(make_upsample_convex_f32(t, i, nullptr)); }
-void corr_pool_f32_op(const TList& t, IList i) { run_now(make_corr_pool_f32(t, i, nullptr)); }
-void lookup_f32_op(const TList& t, IList i) { run_now(make_lookup_f32(t, i, nullptr)); }
-void flow_update_f32_op(const TList& t, IList i) { run_now(make_flow_update_f32(t, i, nullptr)); }
-void init_flow_op(const TList& t, IList i) { run_now(make_init_flow(t, i, false, nullptr)); }
-void init_flow_f32_op(const TList& t, IList i) { run_now(make_init_flow(t, i, true, nullptr)); }
-void forward_project_op(const TList& t, IList i) { run_now(make_forward_project(t, i, nullptr)); }
-
-void corr_op(const TList& t, IList i, double scale) { run_now(make_corr(t, i, scale, nullptr)); }
-// a stand-alone lookup applies its fused flow update when one is given (in a
-// plan the update is skipped in loop iteration 0, which has no previous taps)
-void lookup_op(const TList& t, IList i) { JR_CHECK_OK(make_lookup(t, i, nullptr)(cur_stream(), 1)); }
-void upsample_convex_op(const TList& t, IList i) { run_now(make_upsample_convex(t, i, nullptr)); }
-void convex_head_op(const TList& t, IList i, double alpha) { run_now(make_convex_head(t, i, alpha, nullptr)); }
-void upsample_bilinear_op(const TList& t, IList i) { run_now(make_upsample_bilinear(t, i, nullptr)); }
-void stats_op(const TList& t, IList i) {
-  std::vector<at::Tensor> keep;  // keeps an internally allocated workspace alive until the launch is queued
-  run_now(make_stats(t, i, &keep));
-}
-void norm_act_op(const TList& t, IList i, double eps) { run_now(make_norm_act(t, i, eps, nullptr)); }
-void prep_op(const TList& t, IList i) { run_now(make_prep(t, i, nullptr)); }
-void init_coords_op(const TList& t, IList i) { run_now(make_init_coords(t, i, nullptr)); }
-void copy_channels_op(const TList& t, IList i) { run_now(make_copy_channels(t, i, nullptr)); }
-void sum_iters_op(const TList& t, IList i) { run_now(make_sum_iters(t, i, nullptr)); }
-void lookup_bwd_op(const TList& t, IList i) { run_now(make_lookup_bwd(t, i, nullptr)); }
-void im2col_op(const TList& t, IList i) { run_now(make_im2col(t, i, nullptr)); }
-void flow_taps_op(const TList& t, IList i) { run_now(make_flow_taps(t, i, nullptr)); }
-void taps_gemm_op(const TList& t, IList i) { run_now(make_taps_gemm(t, i, nullptr)); }
-void gru_fused_op(const TList& t, IList i) { run_now(make_gru_fused(t, i, nullptr)); }
-void gru_halo_op(const TList& t, IList i) { run_now(make_gru_halo(t, i, nullptr)); }
 bool conv_halo_ok_op(int64_t cfg, int64_t cin8, int64_t cout) { return conv_halo_ok_cfg(cfg, cin8, cout); }
 // t = [part (fp32 [N][nb][C][2]), stats (fp32 [N][C][2])], i = [N, nb, C]
-static Launch make_stats_final(const TList& t, const IList& i, std::vector<at::Tensor>* keep) {
+static Launch make_stats_final(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor part = opt(t, 0), st = opt(t, 1);
   check_f32(part, "partials"); check_f32(st, "stats");
-  TORCH_CHECK(i.size() == 3, "stats_final: expected [N, nb, C]");
   const int N = (int)i[0], nb = (int)i[1], C = (int)i[2];
   TORCH_CHECK(part.numel() >= (int64_t)N * nb * C * 2 && st.numel() >= (int64_t)N * C * 2, "stats_final: sizes");
-  if (keep) { keep->push_back(part); keep->push_back(st); }
+  keep.push_back(part); keep.push_back(st);
   const float* pp = part.data_ptr<float>();
   float* sp = st.data_ptr<float>();
   return [=](hipStream_t s, int) { return jr_channel_stats_final(pp, N, nb, C, sp, s); };
 }
-void stats_final_op(const TList& t, IList i) { run_now(make_stats_final(t, i, nullptr)); }
 std::vector<int64_t> conv_halo_cfg_op(int64_t cfg) {
   int c[6];
   if (!jr_conv_halo_cfg((int)(cfg - kHaloCfg0), c)) return {};
@@ -1806,12 +1734,6 @@ void bgemm_op(const TList& t, IList i, double alpha) {
                        (int)a.size(0), (int)M, (int)N, (int)K, (float)alpha, f32 ? c.data_ptr<float>() : nullptr,
                        f32 ? nullptr : c.data_ptr(), (long)(M * N), (int)N, cur_stream()));
 }
-void conv1x1_op(const TList& t, IList i) { run_now(make_conv1x1(t, i, nullptr)); }
-void conv_direct_op(const TList& t, IList i) { run_now(make_conv_direct(t, i, nullptr)); }
-void conv_train_op(const TList& t, IList i, double alpha, const TList& tx, IList ix) {
-  run_now(make_conv(t, i, alpha, nullptr, &tx, &ix));
-}
-void upsample_convex_bwd_op(const TList& t, IList i, double alpha) { run_now(make_upsample_convex_bwd(t, i, alpha, nullptr)); }
 // t = [dc (bf16 [M][h][w]), g0, g1?, g2?, g3?], i = [L, M, h, w]
 void pyr_bwd_dc_op(const TList& t, IList i, double scale) {
   at::Tensor dc = opt(t, 0);
@@ -1831,592 +1753,169 @@ void pyr_bwd_dc_op(const TList& t, IList i, double scale) {
   }
   JR_CHECK_OK(jr_pyr_bwd_dc(g[0], g[1], g[2], g[3], L, M, h, w, (float)scale, dc.data_ptr(), cur_stream()));
 }
-void wgrad_op(const TList& t, IList i) {
-  std::vector<at::Tensor> keep;
-  run_now(make_wgrad(t, i, &keep));
-}
-void pack_op(const TList& t, IList i) {
-  std::vector<at::Tensor> keep;
-  run_now(make_pack(t, i, &keep));
-}
-void norm_bwd_op(const TList& t, IList i, double eps) {
-  std::vector<at::Tensor> keep;
-  run_now(make_norm_bwd(t, i, eps, &keep));
-}
-void flow_gather_bwd_op(const TList& t, IList i) { run_now(make_flow_gather_bwd(t, i, nullptr)); }
-void upsample_bilinear_bwd_op(const TList& t, IList i) { run_now(make_upsample_bilinear_bwd(t, i, nullptr)); }
 
-// --------------------------------------------------------------------- Plan
-// A Plan is the lowered RAFT forward: three segments (prologue, loop body run
-// n_iters times with the iteration index, epilogue) of launch closures.  Ops
-// are placed on "lanes": lane 0 is the caller's stream, lanes 1..kMaxLanes-1
-// are private non-blocking streams, and record/wait ops on numbered events
-// express the cross-lane dependencies of the model's DAG (independent
-// branches such as the context encoder vs. the feature encoder + correlation
-// pyramid, or the mask head + upsampling of iteration i vs. iteration i+1).
-// Every side lane is forked from lane 0 at the start of an enqueue and joined
-// back at its end, so run() is ordered like a single-stream launch and
-// capture() records one hipGraph whose parallel branches the runtime may
-// execute concurrently.  A wait on an event not yet recorded during the
-// current enqueue is skipped (e.g. the first iteration's wait on the previous
-// iteration's mask head), which also keeps graph capture self-contained.
-// Lane 0 runs on a private stream of the device's greatest priority (forked
-// from / joined to the caller's stream): the model's critical path (lookup ->
-// motion encoder -> GRU -> flow head) wins the dispatcher over the side lanes'
-// work, which only fills the CUs the critical path leaves idle.
-struct RangeGuard {
-  explicit RangeGuard(const char* name) { roctxRangePushA(name); }
-  ~RangeGuard() { roctxRangePop(); }
+// ----------------------------------------------------------------- op table
+// One row per launch op: its name, signature class, the int-list lengths it accepts and its
+// maker.  Both front-ends are generated from the row (register_ops): the eager op
+// torch.ops.jax_raft_amd.<name>, which runs the launch at once on the current stream, and
+// Plan.add_<name>, which records it under that name.  A new op is its maker plus one row.
+//   row_t   (Tensor?[] t)                  row_ti  (Tensor?[] t, int[] i)
+//   row_tia (Tensor?[] t, int[] i, float <alpha | eps | scale>)
+// min / max ints: one more than the highest i[k] a maker reads unconditionally / at all; checked
+// before the maker runs, so a maker may index up to min without a check of its own.  Makers that
+// accept only some lengths of the range (conv, flowin_dual, prep) check those themselves.
+using Keep = std::vector<at::Tensor>;
+enum Sig { SIG_T = 0, SIG_TI = 1, SIG_TIA = 2 };
+struct OpRow {
+  const char* name;
+  Sig sig;
+  const char* fname;   // TIA: the float's schema name
+  int min_ints, max_ints;
+  std::function<Launch(const TList&, const IList&, double, Keep&)> make;
+  int eager_it;        // the iteration index the eager op runs with
 };
+static OpRow row_t(const char* name, Launch (*f)(const TList&, Keep&)) {
+  return {name, SIG_T, nullptr, 0, 0, [f](const TList& t, const IList&, double, Keep& k) { return f(t, k); }, 0};
+}
+static OpRow row_ti(const char* name, int lo, int hi, Launch (*f)(const TList&, const IList&, Keep&), int eager_it = 0) {
+  return {name, SIG_TI, nullptr, lo, hi, [f](const TList& t, const IList& i, double, Keep& k) { return f(t, i, k); }, eager_it};
+}
+static OpRow row_tia(const char* name, const char* fname, int lo, int hi, Launch (*f)(const TList&, const IList&, double, Keep&)) {
+  return {name, SIG_TIA, fname, lo, hi, f, 0};
+}
+static Launch make_conv_fwd(const TList& t, const IList& i, double alpha, Keep& keep) { return make_conv(t, i, alpha, keep); }
+static Launch make_init_flow_bf16(const TList& t, const IList& i, Keep& keep) { return make_init_flow(t, i, false, keep); }
+static Launch make_init_flow_f32(const TList& t, const IList& i, Keep& keep) { return make_init_flow(t, i, true, keep); }
 
-class Plan : public torch::CustomClassHolder {
- public:
-  static constexpr int kMaxLanes = 8;
-  static constexpr int kMaxEvents = 64;
-  Plan() = default;
-  ~Plan() override {
-    reset_graph();
-    for (auto e : events_) if (e) (void)hipEventDestroy(e);
-    for (auto e : join_) if (e) (void)hipEventDestroy(e);
-    if (fork_) (void)hipEventDestroy(fork_);
-    for (auto st : lanes_) if (st) (void)hipStreamDestroy(st);
-    if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
-  }
-
-  // Segment 3 is the second half of the loop body (enqueued right after segment 1 in
-  // every iteration): a context-parallel engine runs the two halves separately, with
-  // the all-gather of the correlation features in between (run_segment).
-  void set_segment(int64_t s) {
-    TORCH_CHECK(s >= 0 && s <= 3, "segment must be 0 (prologue), 1 (loop), 2 (epilogue) or 3 (loop, second half)");
-    seg_ = (int)s;
-    defer_ = 0;
-    reset_graph();
-  }
-  // Deferred ops (set_defer 1, loop body / epilogue): the work of the PREVIOUS
-  // iteration -- skipped in loop iteration 0 and called with iteration index
-  // it - 1; in the epilogue (called with n_iters) they finish the last
-  // iteration.  Used when iteration i's flow update is fused into iteration
-  // i+1's lookup, so iteration i's mask head / upsampling run one iteration later.
-  void set_defer(int64_t d) {
-    TORCH_CHECK(d == 0 || d == 1, "defer must be 0 or 1");
-    TORCH_CHECK(d == 0 || seg_ != 0, "deferred ops belong to the loop body or the epilogue");
-    defer_ = (int)d;
-  }
-  void set_lane(int64_t l) {
-    TORCH_CHECK(l >= 0 && l < kMaxLanes, "lane must be in [0, ", kMaxLanes, ")");
-    lane_ = (int)l;
-    used_lanes_ = std::max(used_lanes_, lane_ + 1);
-  }
-  void add_record(int64_t ev) { push_sync(OP_RECORD, ev, "record"); }
-  void add_wait(int64_t ev) { push_sync(OP_WAIT, ev, "wait"); }
-  void add_conv(TList t, IList i, double alpha) { push(make_conv(t, i, alpha, &keep_), "conv"); }
-  void add_conv_alt(TList t, IList i, double alpha, at::Tensor x_alt) {
-    push(make_conv_alt(t, i, alpha, x_alt, &keep_), "conv");
-  }
-  void add_conv_group(TList t1, IList i1, double a1, TList t2, IList i2, double a2) {
-    push(make_conv_group(t1, i1, a1, t2, i2, a2, &keep_), "conv_group");
-  }
-  void add_corr(TList t, IList i, double scale) { push(make_corr(t, i, scale, &keep_), "corr"); }
-  void add_lookup(TList t, IList i) { push(make_lookup(t, i, &keep_), "lookup"); }
-  void add_upsample_convex(TList t, IList i) { push(make_upsample_convex(t, i, &keep_), "upsample_convex"); }
-  void add_convex_head(TList t, IList i, double alpha) { push(make_convex_head(t, i, alpha, &keep_), "convex_head"); }
-  void add_upsample_bilinear(TList t, IList i) { push(make_upsample_bilinear(t, i, &keep_), "upsample_bilinear"); }
-  void add_stats(TList t, IList i) { push(make_stats(t, i, &keep_), "stats"); }
-  void add_norm_act(TList t, IList i, double eps) { push(make_norm_act(t, i, eps, &keep_), "norm_act"); }
-  void add_prep(TList t, IList i) { push(make_prep(t, i, &keep_), "prep"); }
-  void add_init_coords(TList t, IList i) { push(make_init_coords(t, i, &keep_), "init_coords"); }
-  void add_init_flow(TList t, IList i) { push(make_init_flow(t, i, false, &keep_), "init_flow"); }
-  void add_init_flow_f32(TList t, IList i) { push(make_init_flow(t, i, true, &keep_), "init_flow_f32"); }
-  void add_memset(TList t) { push(make_memset(t, &keep_), "memset"); }
-  void add_copy(TList t) { push(make_copy(t, &keep_), "copy"); }
-  void add_copy_channels(TList t, IList i) { push(make_copy_channels(t, i, &keep_), "copy_channels"); }
-  void add_flow_taps(TList t, IList i) { push(make_flow_taps(t, i, &keep_), "flow_taps"); }
-  void add_taps_gemm(TList t, IList i) { push(make_taps_gemm(t, i, &keep_), "taps_gemm"); }
-  void add_gru_fused(TList t, IList i) { push(make_gru_fused(t, i, &keep_), "gru_fused"); }
-  void add_gru_halo(TList t, IList i) { push(make_gru_halo(t, i, &keep_), "gru_halo"); }
-  void add_stats_final(TList t, IList i) { push(make_stats_final(t, i, &keep_), "stats_final"); }
-  void add_conv1x1(TList t, IList i) { push(make_conv1x1(t, i, &keep_), "conv1x1"); }
-  void add_conv_direct(TList t, IList i) { push(make_conv_direct(t, i, &keep_), "conv_direct"); }
-  void add_flowin_dual(TList t, IList i, double alpha) { push(make_flowin_dual(t, i, alpha, &keep_), "flowin_dual"); }
-  void add_conv_train(TList t, IList i, double alpha, TList tx, IList ix) {
-    push(make_conv(t, i, alpha, &keep_, &tx, &ix), "conv_train");
-  }
-  void add_upsample_convex_bwd(TList t, IList i, double alpha) {
-    push(make_upsample_convex_bwd(t, i, alpha, &keep_), "upsample_convex_bwd");
-  }
-  void add_bn_table(TList t, IList i) { push(make_bn_table(t, i, &keep_), "bn_table"); }
-  void add_wgrad(TList t, IList i) { push(make_wgrad(t, i, &keep_), "wgrad"); }
-  void add_pack(TList t, IList i) { push(make_pack(t, i, &keep_), "pack"); }
-  void add_norm_bwd(TList t, IList i, double eps) { push(make_norm_bwd(t, i, eps, &keep_), "norm_bwd"); }
-  void add_flow_gather_bwd(TList t, IList i) { push(make_flow_gather_bwd(t, i, &keep_), "flow_gather_bwd"); }
-  void add_upsample_bilinear_bwd(TList t, IList i) { push(make_upsample_bilinear_bwd(t, i, &keep_), "upsample_bilinear_bwd"); }
-  void add_lookup_bwd(TList t, IList i) { push(make_lookup_bwd(t, i, &keep_), "lookup_bwd"); }
-  void add_im2col(TList t, IList i) { push(make_im2col(t, i, &keep_), "im2col"); }
-  void add_conv_f32(TList t, IList i, double alpha) { push(make_conv_f32(t, i, alpha, &keep_), "conv_f32"); }
-  void add_stats_f32(TList t, IList i) { push(make_stats_f32(t, i, &keep_), "stats_f32"); }
-  void add_norm_act_f32(TList t, IList i, double eps) { push(make_norm_act_f32(t, i, eps, &keep_), "norm_act_f32"); }
-  void add_prep_f32(TList t, IList i) { push(make_prep_f32(t, i, &keep_), "prep_f32"); }
-  void add_copy_channels_f32(TList t, IList i) { push(make_copy_channels_f32(t, i, &keep_), "copy_channels_f32"); }
-  void add_upsample_convex_f32(TList t, IList i) { push(make_upsample_convex_f32(t, i, &keep_), "upsample_convex_f32"); }
-  void add_corr_pool_f32(TList t, IList i) { push(make_corr_pool_f32(t, i, &keep_), "corr_pool_f32"); }
-  void add_lookup_f32(TList t, IList i) { push(make_lookup_f32(t, i, &keep_), "lookup_f32"); }
-  void add_flow_update_f32(TList t, IList i) { push(make_flow_update_f32(t, i, &keep_), "flow_update_f32"); }
-
-  int64_t num_ops(int64_t seg) const { return (int64_t)segs_[seg].size(); }
-  std::vector<std::string> op_names(int64_t seg) const {
-    std::vector<std::string> out;
-    for (const auto& o : segs_[seg]) out.push_back(o.name + (o.lane ? "@" + std::to_string(o.lane) : std::string()));
-    return out;
-  }
-  int64_t num_lanes() const { return used_lanes_; }
-
-  // Launch prologue, n_iters x loop body, epilogue (lane 0 = current stream).
-  void run(int64_t n_iters) { JR_CHECK_OK(enqueue(cur_stream(), (int)n_iters)); }
-  // Launch one segment alone with iteration index `it` (eager; host-driven loops
-  // that interleave collectives with the segments, runtime/engine.py context parallelism).
-  void run_segment(int64_t seg, int64_t it) {
-    TORCH_CHECK(seg >= 0 && seg <= 3, "segment must be 0..3");
-    JR_CHECK_OK(enqueue(cur_stream(), (int)it, false, -1, (int)seg));
-  }
-  // Enqueue into a stream that an outer capture is recording (e.g. a whole
-  // training step captured by torch.cuda.graph): lane 0 is the caller's stream
-  // itself, as in capture(), so the origin stream never holds only fork / join
-  // event nodes (which crashes hipStreamEndCapture on this ROCm); no per-op
-  // checks (no synchronisation inside a capture).
-  void run_inline(int64_t n_iters) { JR_CHECK_OK(enqueue(cur_stream(), (int)n_iters, true)); }
-
-  // Capture the same sequence into one hipGraph (on a private stream: the
-  // legacy default stream cannot be captured) and instantiate it.
-  void capture(int64_t n_iters) {
-    reset_graph();
-    capture_into(n_iters, -1, &graph_, &exec_);
-    captured_iters_ = n_iters;
-  }
-  // Capture one phase as its own hipGraph: part 0 = the prologue (encoders +
-  // correlation pyramid), part 1 = n_iters loop iterations + the epilogue.
-  // Replayed on different streams, the prologue of batch i+1 overlaps the
-  // refinement loop of batch i (cross-batch pipelining, runtime/engine.py).
-  void capture_part(int64_t part, int64_t n_iters) {
-    TORCH_CHECK(part == 0 || part == 1, "part must be 0 (prologue) or 1 (loop + epilogue)");
-    reset_part(part);
-    capture_into(n_iters, (int)part, &pgraph_[part], &pexec_[part]);
-    pcaptured_[part] = n_iters;
-  }
-  int64_t captured_part_iters(int64_t part) const { return pcaptured_[part & 1]; }
-  void replay_part(int64_t part) {
-    TORCH_CHECK((part == 0 || part == 1) && pexec_[part] != nullptr, "plan: part ", part, " not captured");
-    hipError_t e = hipGraphLaunch(pexec_[part], cur_stream());
-    TORCH_CHECK(e == hipSuccess, "graph launch failed: ", hipGetErrorString(e));
-  }
-
-  // Software-pipelined step: ONE hipGraph holding this plan's refinement loop
-  // + epilogue (batch i) and `next`'s prologue (encoders + correlation pyramid
-  // of batch i+1, a plan with its own buffers) as independent branches.  The
-  // loop is latency-bound (one workgroup per CU, ~220 of 256 CUs per kernel);
-  // the throughput-bound encoder convs fill the idle SIMD slots.  Two graphs
-  // launched on two streams serialise on this ROCm (measured 196 pairs/s,
-  // engine.submit), the branches of one graph do not.  The loop branch is
-  // enqueued first, so its nodes come first in the graph's launch order.
-  void capture_pipelined(c10::intrusive_ptr<Plan> next, int64_t n_iters) {
-    TORCH_CHECK(next.get() != this, "capture_pipelined: the next plan must have its own buffers");
-    reset_pipe();
-    // The two phases are captured on their own (capture_part) and their nodes
-    // copied, with their dependency edges, into one graph with no edge between
-    // the two: every lane of both stays a parallel branch.  (Enqueueing both
-    // into one stream capture -- the next plan's lanes forked from this one's
-    // capture stream -- crashed hipStreamEndCapture on this ROCm whenever both
-    // plans use several lanes (batch 4); a child-graph node runs its graph's
-    // nodes in order on one stream, i.e. without the lanes.)
-    if (pcaptured_[1] != n_iters) capture_part(1, n_iters);
-    if (next->pcaptured_[0] != n_iters) next->capture_part(0, n_iters);
-    debug_ = std::getenv("JR_PLAN_DEBUG") != nullptr;
-    hipGraph_t g = nullptr;
-    TORCH_CHECK(hipGraphCreate(&g, 0) == hipSuccess, "graph create");
-    pipe_graph_ = g;
-    // loop nodes first (the executor launches in creation order; the prologue's first
-    // measured batch 1 157 -> 78 pairs/s, the two phases then run one after the other).
-    // (The prologue as one child-graph node, i.e. its nodes in order on one stream,
-    // measured 264 vs 289 pairs/s at batch 4.)
-    // One empty root node ahead of both branches: the executor forks a node's successors
-    // onto parallel streams, but runs disconnected components in creation order on the
-    // launch stream (measured: 21.6 us of a 3.2 ms raft_small batch-1 step concurrent;
-    // with the root raft_small b1 12 it 788 vs 713 pairs/s, profiles/r5_pipeline_fork_ab.txt).
-    hipGraphNode_t root = nullptr;
-    TORCH_CHECK(hipGraphAddEmptyNode(&root, g, nullptr, 0) == hipSuccess, "graph root");
-    append_graph(g, pgraph_[1], root);
-    append_graph(g, next->pgraph_[0], root);
-    hipError_t e3 = hipGraphInstantiate(&pipe_exec_, g, nullptr, nullptr, 0);
-    if (debug_) fprintf(stderr, "[plan] pipelined instantiate %d\n", (int)e3);
-    TORCH_CHECK(e3 == hipSuccess, "graph instantiate failed: ", hipGetErrorString(e3));
-    pipe_iters_ = n_iters;
-    pipe_next_ = next.get();
-  }
-  // Copy every node of src (kernel / empty nodes: what a plan capture holds)
-  // into dst in dependency order, keeping src's edges.
-  static void append_graph(hipGraph_t dst, hipGraph_t src, hipGraphNode_t root = nullptr) {
-    size_t n = 0;
-    TORCH_CHECK(hipGraphGetNodes(src, nullptr, &n) == hipSuccess, "graph nodes");
-    std::vector<hipGraphNode_t> nodes(n);
-    TORCH_CHECK(hipGraphGetNodes(src, nodes.data(), &n) == hipSuccess, "graph nodes");
-    std::unordered_map<hipGraphNode_t, size_t> index;
-    for (size_t i = 0; i < n; ++i) index[nodes[i]] = i;
-    std::vector<std::vector<size_t>> deps(n), users(n);
-    std::vector<size_t> missing(n, 0);
-    for (size_t i = 0; i < n; ++i) {
-      size_t nd = 0;
-      TORCH_CHECK(hipGraphNodeGetDependencies(nodes[i], nullptr, &nd) == hipSuccess, "node deps");
-      std::vector<hipGraphNode_t> d(nd);
-      if (nd) TORCH_CHECK(hipGraphNodeGetDependencies(nodes[i], d.data(), &nd) == hipSuccess, "node deps");
-      for (auto x : d) {
-        const size_t j = index.at(x);
-        deps[i].push_back(j);
-        users[j].push_back(i);
-      }
-      missing[i] = deps[i].size();
-    }
-    std::vector<hipGraphNode_t> copy(n, nullptr);
-    // ready nodes are copied in src creation order: the executor maps a node's
-    // successors onto its streams in creation order, and a depth-first copy of
-    // the forward graph measured 6 % slower (profiles/r2_pipelined_graph_ab.txt)
-    std::vector<size_t> ready;
-    for (size_t i = 0; i < n; ++i) if (!missing[i]) ready.push_back(i);
-    size_t done = 0;
-    while (!ready.empty()) {
-      const auto it = std::min_element(ready.begin(), ready.end());
-      const size_t i = *it;
-      ready.erase(it);
-      std::vector<hipGraphNode_t> d;
-      for (size_t j : deps[i]) d.push_back(copy[j]);
-      if (d.empty() && root) d.push_back(root);
-      hipGraphNodeType type;
-      TORCH_CHECK(hipGraphNodeGetType(nodes[i], &type) == hipSuccess, "node type");
-      hipError_t e = hipSuccess;
-      if (type == hipGraphNodeTypeKernel) {
-        hipKernelNodeParams kp;
-        e = hipGraphKernelNodeGetParams(nodes[i], &kp);
-        if (e == hipSuccess) e = hipGraphAddKernelNode(&copy[i], dst, d.data(), d.size(), &kp);
-      } else if (type == hipGraphNodeTypeEmpty) {
-        e = hipGraphAddEmptyNode(&copy[i], dst, d.data(), d.size());
-      } else {
-        TORCH_CHECK(false, "capture_pipelined: unsupported graph node type ", (int)type);
-      }
-      TORCH_CHECK(e == hipSuccess, "capture_pipelined: node copy failed: ", hipGetErrorString(e));
-      ++done;
-      for (size_t u : users[i]) if (--missing[u] == 0) ready.push_back(u);
-    }
-    TORCH_CHECK(done == n, "capture_pipelined: cyclic graph");
-  }
-  // Batch parts as ONE graph: every part plan's full-forward capture (own
-  // buffers, own lanes) copied into a single graph with no edge between the
-  // parts, so their in-order chains interleave on the GPU without any
-  // cross-stream edge (separate graphs on separate streams serialise on this
-  // ROCm).  merge_reset(); merge_add(part) for every part; merge_finish(n);
-  // replay_pipelined().
-  void merge_reset() {
-    reset_pipe();
-    TORCH_CHECK(hipGraphCreate(&pipe_graph_, 0) == hipSuccess, "graph create");
-    // one root: the parts fork (capture_pipelined)
-    TORCH_CHECK(hipGraphAddEmptyNode(&pipe_root_, pipe_graph_, nullptr, 0) == hipSuccess, "graph root");
-  }
-  void merge_add(c10::intrusive_ptr<Plan> part, int64_t n_iters) {
-    TORCH_CHECK(pipe_graph_ != nullptr && pipe_exec_ == nullptr, "merge_add: call merge_reset() first");
-    if (part->captured_iters_ != n_iters) {
-      // capture() resets this plan's graphs, the merge in progress included
-      hipGraph_t merging = pipe_graph_;
-      pipe_graph_ = nullptr;
-      part->capture(n_iters);
-      pipe_graph_ = merging;
-    }
-    append_graph(pipe_graph_, part->graph_, pipe_root_);
-  }
-  void merge_finish(int64_t n_iters) {
-    TORCH_CHECK(pipe_graph_ != nullptr && pipe_exec_ == nullptr, "merge_finish: call merge_reset() first");
-    hipError_t e = hipGraphInstantiate(&pipe_exec_, pipe_graph_, nullptr, nullptr, 0);
-    TORCH_CHECK(e == hipSuccess, "graph instantiate failed: ", hipGetErrorString(e));
-    pipe_iters_ = n_iters;
-    pipe_next_ = this;
-  }
-  int64_t merged_iters() const { return pipe_next_ == this ? pipe_iters_ : -1; }
-
-  // n_iters of the pipelined graph if it was captured with `next`, else -1.
-  int64_t pipelined_iters(c10::intrusive_ptr<Plan> next) const {
-    return pipe_next_ == next.get() ? pipe_iters_ : -1;
-  }
-  void replay_pipelined() {
-    TORCH_CHECK(pipe_exec_ != nullptr, "plan: no pipelined graph captured");
-    hipError_t e = hipGraphLaunch(pipe_exec_, cur_stream());
-    TORCH_CHECK(e == hipSuccess, "graph launch failed: ", hipGetErrorString(e));
-  }
-
- private:
-  void reset_pipe() {
-    if (pipe_exec_) { (void)hipGraphExecDestroy(pipe_exec_); pipe_exec_ = nullptr; }
-    if (pipe_graph_) { (void)hipGraphDestroy(pipe_graph_); pipe_graph_ = nullptr; }
-    pipe_root_ = nullptr;
-    pipe_iters_ = -1;
-    pipe_next_ = nullptr;
-  }
-  hipStream_t ensure_cap_stream() {
-    if (!cap_stream_) {
-      int least = 0, greatest = 0;
-      TORCH_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess, "priority range");
-      TORCH_CHECK(hipStreamCreateWithPriority(&cap_stream_, hipStreamNonBlocking, greatest) == hipSuccess, "stream");
-    }
-    return cap_stream_;
-  }
-  void reset_part(int64_t part) {
-    if (pexec_[part]) { (void)hipGraphExecDestroy(pexec_[part]); pexec_[part] = nullptr; }
-    if (pgraph_[part]) { (void)hipGraphDestroy(pgraph_[part]); pgraph_[part] = nullptr; }
-    pcaptured_[part] = -1;
-  }
-  void capture_into(int64_t n_iters, int part, hipGraph_t* graph_out, hipGraphExec_t* exec_out) {
-    hipStream_t s = ensure_cap_stream();
-    debug_ = std::getenv("JR_PLAN_DEBUG") != nullptr;
-    // order the capture after work already queued on the current stream
-    TORCH_CHECK(hipStreamSynchronize(cur_stream()) == hipSuccess, "sync");
-    TORCH_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess, "begin capture");
-    int err = enqueue(s, (int)n_iters, true, part);
-    if (debug_) fprintf(stderr, "[plan] enqueue done err=%d\n", err);
-    hipGraph_t g = nullptr;
-    hipError_t e2 = hipStreamEndCapture(s, &g);
-    if (debug_) fprintf(stderr, "[plan] end capture %d\n", (int)e2);
-    TORCH_CHECK(err == 0, "launch failed during capture: ", hipGetErrorString((hipError_t)err));
-    TORCH_CHECK(e2 == hipSuccess && g != nullptr, "end capture failed: ", hipGetErrorString(e2));
-    *graph_out = g;
-    hipError_t e3 = hipGraphInstantiate(exec_out, g, nullptr, nullptr, 0);
-    if (debug_) fprintf(stderr, "[plan] instantiate %d\n", (int)e3);
-    TORCH_CHECK(e3 == hipSuccess, "graph instantiate failed: ", hipGetErrorString(e3));
-  }
-
- public:
-  int64_t captured_iters() const { return captured_iters_; }
-  void replay() {
-    TORCH_CHECK(exec_ != nullptr, "plan: no captured graph");
-    hipError_t e = hipGraphLaunch(exec_, cur_stream());
-    TORCH_CHECK(e == hipSuccess, "graph launch failed: ", hipGetErrorString(e));
-  }
-  void reset_graph() {
-    if (exec_) { (void)hipGraphExecDestroy(exec_); exec_ = nullptr; }
-    if (graph_) { (void)hipGraphDestroy(graph_); graph_ = nullptr; }
-    captured_iters_ = -1;
-    reset_part(0);
-    reset_part(1);
-    reset_pipe();
-  }
-
- private:
-  enum OpKind { OP_LAUNCH = 0, OP_RECORD = 1, OP_WAIT = 2 };
-  struct Op {
-    Launch l;
-    int lane;
-    int kind;
-    int ev;
-    std::string name;
-    int defer;   // 1: previous iteration's work (see set_defer)
+static const std::vector<OpRow>& op_table() {
+  static const std::vector<OpRow> rows = {
+      row_tia("conv", "alpha", 22, 29, make_conv_fwd),   // 22 | 26 | 27; the halo kernel's input norm: 29
+      row_tia("corr", "scale", 5, 7, make_corr),
+      // a stand-alone lookup applies its fused flow update when one is given (in a plan the
+      // update is skipped in loop iteration 0, which has no previous taps): eager iteration 1
+      row_ti("lookup", 5, 9, make_lookup, 1),
+      row_ti("upsample_convex", 4, 4, make_upsample_convex),
+      row_tia("convex_head", "alpha", 5, 7, make_convex_head),
+      row_ti("upsample_bilinear", 4, 5, make_upsample_bilinear),
+      row_ti("stats", 3, 3, make_stats),
+      row_ti("stats_final", 3, 3, make_stats_final),
+      row_tia("norm_act", "eps", 6, 6, make_norm_act),
+      row_ti("prep", 3, 8, make_prep),                   // float frames 3 (4: s2d flag), uint8 frames 8
+      row_ti("init_coords", 3, 3, make_init_coords),
+      row_ti("init_flow", 5, 5, make_init_flow_bf16),
+      row_ti("init_flow_f32", 5, 5, make_init_flow_f32),
+      row_ti("forward_project", 4, 4, make_forward_project),
+      row_t("memset", make_memset),
+      row_t("copy", make_copy),
+      row_ti("copy_channels", 4, 4, make_copy_channels),
+      row_ti("sum_iters", 2, 2, make_sum_iters),
+      row_ti("im2col", 11, 11, make_im2col),
+      row_ti("flow_taps", 5, 5, make_flow_taps),
+      row_ti("taps_gemm", 3, 3, make_taps_gemm),
+      row_ti("gru_fused", 4, 5, make_gru_fused),
+      row_ti("gru_halo", 9, 9, make_gru_halo),
+      row_ti("conv1x1", 6, 6, make_conv1x1),
+      row_ti("conv_direct", 11, 11, make_conv_direct),
+      row_tia("flowin_dual", "alpha", 15, 21, make_flowin_dual),   // 15 | 21
+      // training
+      row_tia("upsample_convex_bwd", "alpha", 3, 3, make_upsample_convex_bwd),
+      row_ti("upsample_bilinear_bwd", 3, 3, make_upsample_bilinear_bwd),
+      row_ti("flow_gather_bwd", 3, 3, make_flow_gather_bwd),
+      row_ti("lookup_bwd", 5, 6, make_lookup_bwd),
+      row_tia("norm_bwd", "eps", 5, 5, make_norm_bwd),
+      row_ti("pack", 2, 2, make_pack),
+      row_ti("wgrad", 16, 16, make_wgrad),
+      row_ti("bn_table", 2, 2, make_bn_table),
+      // fp32 parity mode
+      row_tia("conv_f32", "alpha", 22, 22, make_conv_f32),
+      row_ti("stats_f32", 3, 3, make_stats_f32),
+      row_tia("norm_act_f32", "eps", 6, 6, make_norm_act_f32),
+      row_ti("prep_f32", 3, 3, make_prep_f32),
+      row_ti("copy_channels_f32", 4, 4, make_copy_channels_f32),
+      row_ti("upsample_convex_f32", 4, 5, make_upsample_convex_f32),
+      row_ti("corr_pool_f32", 3, 3, make_corr_pool_f32),
+      row_ti("lookup_f32", 5, 6, make_lookup_f32),
+      row_ti("flow_update_f32", 5, 5, make_flow_update_f32),
   };
-  void push(Launch l, const char* name) {
-    segs_[seg_].push_back(Op{std::move(l), lane_, OP_LAUNCH, -1, name, defer_});
-    reset_graph();
-  }
-  void push_sync(int kind, int64_t ev, const char* name) {
-    TORCH_CHECK(ev >= 0 && ev < kMaxEvents, "event id out of range");
-    segs_[seg_].push_back(Op{Launch(), lane_, kind, (int)ev, std::string(name) + std::to_string(ev), defer_});
-    reset_graph();
-  }
-  static int create_event(hipEvent_t* e) {
-    return (int)hipEventCreateWithFlags(e, hipEventDisableTiming);
-  }
-  int ensure_resources() {
-    if (events_.empty()) {
-      events_.assign(kMaxEvents, nullptr);
-      for (auto& e : events_) if (int r = create_event(&e)) return r;
-    }
-    if (!fork_) if (int r = create_event(&fork_)) return r;
-    int least = 0, greatest = 0;
-    if (int r = (int)hipDeviceGetStreamPriorityRange(&least, &greatest)) return r;
-    if (!lanes_[0]) if (int r = (int)hipStreamCreateWithPriority(&lanes_[0], hipStreamNonBlocking, greatest)) return r;
-    if (!join_[0]) if (int r = create_event(&join_[0])) return r;
-    for (int l = 1; l < used_lanes_; ++l) {
-      if (!lanes_[l]) if (int r = (int)hipStreamCreateWithPriority(&lanes_[l], hipStreamNonBlocking, least)) return r;
-      if (!join_[l]) if (int r = create_event(&join_[l])) return r;
-    }
-    return 0;
-  }
-  // recorded[ev] = 1 + lane of the event's latest record in this enqueue (0: not recorded).
-  // A wait on an event last recorded on the same lane is already satisfied by stream
-  // order and is skipped (a same-stream record/wait pair on a forked capture stream
-  // also crashes hipStreamEndCapture on this ROCm).
-  int exec_op(const Op& o, hipStream_t* st, int it, std::vector<char>& recorded) {
-    if (o.defer) {
-      if (it == 0) return 0;
-      --it;
-    }
-    hipStream_t s = st[o.lane];
-    if (debug_) fprintf(stderr, "[plan] it=%d lane=%d %s stream=%p\n", it, o.lane, o.name.c_str(), (void*)s);
-    switch (o.kind) {
-      case OP_LAUNCH: {
-        const int r = o.l(s, it);
-        // JR_PLAN_CHECK=1 (eager run only): synchronise after every launch so an asynchronous
-        // fault or launch error is attributed to the op that caused it (fault localisation,
-        // SURVEY.md 5.2); the failing op's segment index, lane, iteration and name are reported.
-        if (check_ && !capturing_) {
-          hipError_t e = r ? (hipError_t)r : hipStreamSynchronize(s);
-          if (e == hipSuccess) e = hipGetLastError();
-          if (e != hipSuccess) {
-            fprintf(stderr, "[plan check] op '%s' (lane %d, iteration %d) failed: %s\n", o.name.c_str(), o.lane, it,
-                    hipGetErrorString(e));
-            return (int)e;
-          }
-        }
-        return r;
-      }
-      case OP_RECORD: recorded[o.ev] = (char)(1 + o.lane); return (int)hipEventRecord(events_[o.ev], s);
-      default:
-        if (!recorded[o.ev] || recorded[o.ev] == 1 + o.lane) return 0;
-        return (int)hipStreamWaitEvent(s, events_[o.ev], 0);
+  return rows;
+}
+
+// [sig, min_ints, max_ints] of a table op, empty for any other name (for the tests)
+std::vector<int64_t> op_arity(std::string name) {
+  for (const OpRow& r : op_table())
+    if (name == r.name) return {r.sig, r.min_ints, r.max_ints};
+  return {};
+}
+
+// The arity check comes first: the maker then reads i[0 .. min_ints) unchecked.
+static Launch make_checked(const OpRow& r, const TList& t, const IList& i, double a, Keep& keep) {
+  const int64_t n = (int64_t)i.size();
+  TORCH_CHECK(n >= r.min_ints && n <= r.max_ints, r.name, ": expected ", r.min_ints,
+              r.min_ints == r.max_ints ? std::string() : ".." + std::to_string(r.max_ints), " ints, got ", n);
+  return r.make(t, i, a, keep);
+}
+static void run_eager(const OpRow& r, const TList& t, const IList& i, double a) {
+  Keep keep;   // the operands and any workspace a maker allocates live until the launch is queued
+  JR_CHECK_OK(make_checked(r, t, i, a, keep)(cur_stream(), r.eager_it));
+}
+static void plan_add(const OpRow& r, Plan& p, const TList& t, const IList& i, double a) {
+  p.add(make_checked(r, t, i, a, p.keep()), r.name);
+}
+
+using PlanPtr = c10::intrusive_ptr<Plan>;
+
+static void register_ops(torch::Library& m, torch::class_<Plan>& plan) {
+  for (const OpRow& row : op_table()) {
+    const OpRow* r = &row;
+    const std::string name = r->name, add = "add_" + name;
+    switch (r->sig) {
+      case SIG_T:
+        m.def((name + "(Tensor?[] t) -> ()").c_str(), [r](const TList& t) { run_eager(*r, t, {}, 0.0); });
+        plan.def(add, [r](const PlanPtr& p, TList t) { plan_add(*r, *p, t, {}, 0.0); });
+        break;
+      case SIG_TI:
+        m.def((name + "(Tensor?[] t, int[] i) -> ()").c_str(), [r](const TList& t, IList i) { run_eager(*r, t, i, 0.0); });
+        plan.def(add, [r](const PlanPtr& p, TList t, IList i) { plan_add(*r, *p, t, i, 0.0); });
+        break;
+      case SIG_TIA:
+        m.def((name + "(Tensor?[] t, int[] i, float " + r->fname + ") -> ()").c_str(),
+              [r](const TList& t, IList i, double a) { run_eager(*r, t, i, a); });
+        plan.def(add, [r](const PlanPtr& p, TList t, IList i, double a) { plan_add(*r, *p, t, i, a); });
+        break;
     }
   }
-  // part: -1 = the whole forward, 0 = prologue only, 1 = loop + epilogue only.
-  // only_seg >= 0: just that segment, with iteration index n_iters.
-  int enqueue(hipStream_t s, int n_iters, bool capturing = false, int part = -1, int only_seg = -1) {
-    if (int r = ensure_resources()) return r;
-    check_ = std::getenv("JR_PLAN_CHECK") != nullptr && std::getenv("JR_PLAN_CHECK")[0] == '1';
-    capturing_ = capturing;
-    // Eager: lane 0 is the private high-priority stream, forked from the caller's.
-    // Capture: lane 0 is the capture stream itself (created with the greatest
-    // priority); a capture whose origin stream holds only the fork/join event
-    // nodes crashes hipStreamEndCapture on this ROCm.
-    const int l0 = capturing ? 1 : 0;
-    hipStream_t st[kMaxLanes] = {};
-    st[0] = s;
-    // fork / join only the lanes that hold ops in the enqueued segments: a forked
-    // capture stream holding nothing but the fork wait and the join record
-    // crashes hipStreamEndCapture on this ROCm (e.g. the context-encoder lane in
-    // a loop-only capture, capture_part(1))
-    bool used[kMaxLanes] = {};
-    used[0] = true;
-    for (int sg = 0; sg < 4; ++sg) {
-      if ((sg == 0 && part == 1) || (sg != 0 && part == 0)) continue;
-      if (only_seg >= 0 && sg != only_seg) continue;
-      for (const auto& o : segs_[sg]) used[o.lane] = true;
-    }
-    if (int r = (int)hipEventRecord(fork_, s)) return r;
-    for (int l = l0; l < used_lanes_; ++l) {
-      if (!used[l]) continue;
-      st[l] = lanes_[l];
-      if (int r = (int)hipStreamWaitEvent(st[l], fork_, 0)) return r;
-    }
-    std::vector<char> recorded(kMaxEvents, 0);
-    // roctx ranges (visible in rocprofv3 --marker-trace) bracket the host-side
-    // enqueue of each phase: encoders + correlation pyramid, every refinement
-    // iteration, the epilogue.
-    RangeGuard all("raft.plan");
-    if (only_seg >= 0) {
-      RangeGuard r("raft.segment");
-      for (auto& o : segs_[only_seg]) if (int e = exec_op(o, st, n_iters, recorded)) return e;
-    } else {
-    if (part != 1) {
-      RangeGuard r("raft.prologue");
-      for (auto& o : segs_[0]) if (int e = exec_op(o, st, 0, recorded)) return e;
-    }
-    for (int it = 0; part != 0 && it < n_iters; ++it) {
-      RangeGuard r("raft.iteration");
-      for (auto& o : segs_[1]) if (int e = exec_op(o, st, it, recorded)) return e;
-      for (auto& o : segs_[3]) if (int e = exec_op(o, st, it, recorded)) return e;
-    }
-    if (part != 0) {
-      RangeGuard r("raft.epilogue");
-      for (auto& o : segs_[2]) if (int e = exec_op(o, st, n_iters, recorded)) return e;
-    }
-    }
-    for (int l = l0; l < used_lanes_; ++l) {
-      if (!used[l]) continue;
-      if (int r = (int)hipEventRecord(join_[l], st[l])) return r;
-      if (int r = (int)hipStreamWaitEvent(s, join_[l], 0)) return r;
-    }
-    return 0;
-  }
-  std::vector<Op> segs_[4];
-  std::vector<at::Tensor> keep_;
-  int seg_ = 0;
-  int lane_ = 0;
-  int defer_ = 0;
-  int used_lanes_ = 1;
-  std::vector<hipEvent_t> events_;
-  hipEvent_t fork_ = nullptr;
-  hipEvent_t join_[kMaxLanes] = {};
-  hipStream_t lanes_[kMaxLanes] = {};
-  hipStream_t cap_stream_ = nullptr;
-  hipGraph_t graph_ = nullptr;
-  hipGraphExec_t exec_ = nullptr;
-  int64_t captured_iters_ = -1;
-  hipGraph_t pgraph_[2] = {};
-  hipGraphExec_t pexec_[2] = {};
-  int64_t pcaptured_[2] = {-1, -1};
-  hipGraph_t pipe_graph_ = nullptr;
-  hipGraphNode_t pipe_root_ = nullptr;
-  hipGraphExec_t pipe_exec_ = nullptr;
-  int64_t pipe_iters_ = -1;
-  const Plan* pipe_next_ = nullptr;
-  bool debug_ = false;
-  bool check_ = false;
-  bool capturing_ = false;
-};
+  // ---- launch ops whose arguments fit no table signature (build_conv checks their int lists)
+  m.def("conv_train(Tensor?[] t, int[] i, float alpha, Tensor?[] tx, int[] ix) -> ()",
+        [](const TList& t, IList i, double alpha, const TList& tx, IList ix) {
+          Keep keep;
+          JR_CHECK_OK(make_conv(t, i, alpha, keep, &tx, &ix)(cur_stream(), 0));
+        });
+  plan.def("add_conv_train", [](const PlanPtr& p, TList t, IList i, double alpha, TList tx, IList ix) {
+    p->add(make_conv(t, i, alpha, p->keep(), &tx, &ix), "conv_train");
+  });
+  plan.def("add_conv_alt", [](const PlanPtr& p, TList t, IList i, double alpha, at::Tensor x_alt) {
+    p->add(make_conv_alt(t, i, alpha, x_alt, p->keep()), "conv");
+  });
+  plan.def("add_conv_group", [](const PlanPtr& p, TList t1, IList i1, double a1, TList t2, IList i2, double a2) {
+    p->add(make_conv_group(t1, i1, a1, t2, i2, a2, p->keep()), "conv_group");
+  });
+}
 
 }  // namespace jr
 
 TORCH_LIBRARY(jax_raft_amd, m) {
-  m.def("conv(Tensor?[] t, int[] i, float alpha) -> ()", &jr::conv_op);
-  m.def("corr(Tensor?[] t, int[] i, float scale) -> ()", &jr::corr_op);
-  m.def("lookup(Tensor?[] t, int[] i) -> ()", &jr::lookup_op);
-  m.def("upsample_convex(Tensor?[] t, int[] i) -> ()", &jr::upsample_convex_op);
-  m.def("convex_head(Tensor?[] t, int[] i, float alpha) -> ()", &jr::convex_head_op);
-  m.def("upsample_bilinear(Tensor?[] t, int[] i) -> ()", &jr::upsample_bilinear_op);
-  m.def("stats(Tensor?[] t, int[] i) -> ()", &jr::stats_op);
-  m.def("norm_act(Tensor?[] t, int[] i, float eps) -> ()", &jr::norm_act_op);
-  m.def("prep(Tensor?[] t, int[] i) -> ()", &jr::prep_op);
-  m.def("init_coords(Tensor?[] t, int[] i) -> ()", &jr::init_coords_op);
-  m.def("copy_channels(Tensor?[] t, int[] i) -> ()", &jr::copy_channels_op);
-  m.def("sum_iters(Tensor?[] t, int[] i) -> ()", &jr::sum_iters_op);
-  m.def("lookup_bwd(Tensor?[] t, int[] i) -> ()", &jr::lookup_bwd_op);
-  m.def("im2col(Tensor?[] t, int[] i) -> ()", &jr::im2col_op);
-  m.def("flow_taps(Tensor?[] t, int[] i) -> ()", &jr::flow_taps_op);
-  m.def("taps_gemm(Tensor?[] t, int[] i) -> ()", &jr::taps_gemm_op);
-  m.def("gru_fused(Tensor?[] t, int[] i) -> ()", &jr::gru_fused_op);
+  m.def("op_arity(str name) -> int[]", &jr::op_arity);
   m.def("bgemm(Tensor?[] t, int[] i, float alpha) -> ()", &jr::bgemm_op);
   m.def("conv_grouped_ok(int cfg) -> bool", &jr::conv_grouped_ok_op);
   m.def("gru_fused_fits(int H, int W, int vertical) -> bool", &jr::gru_fused_fits);
-  m.def("gru_halo(Tensor?[] t, int[] i) -> ()", &jr::gru_halo_op);
   m.def("conv_halo_ok(int cfg, int cin8, int cout) -> bool", &jr::conv_halo_ok_op);
-  m.def("stats_final(Tensor?[] t, int[] i) -> ()", &jr::stats_final_op);
   m.def("conv_halo_cfg(int cfg) -> int[]", &jr::conv_halo_cfg_op);
   m.def("gru_halo_geom_ok(int hd, int mode, int TR, int TC, int nb1, int nb2) -> bool", &jr::gru_halo_geom_ok);
-  m.def("conv1x1(Tensor?[] t, int[] i) -> ()", &jr::conv1x1_op);
-  m.def("conv_direct(Tensor?[] t, int[] i) -> ()", &jr::conv_direct_op);
-  m.def("conv_train(Tensor?[] t, int[] i, float alpha, Tensor?[] tx, int[] ix) -> ()", &jr::conv_train_op);
-  m.def("upsample_convex_bwd(Tensor?[] t, int[] i, float alpha) -> ()", &jr::upsample_convex_bwd_op);
-  m.def("flow_gather_bwd(Tensor?[] t, int[] i) -> ()", &jr::flow_gather_bwd_op);
-  m.def("norm_bwd(Tensor?[] t, int[] i, float eps) -> ()", &jr::norm_bwd_op);
-  m.def("pack(Tensor?[] t, int[] i) -> ()", &jr::pack_op);
-  m.def("wgrad(Tensor?[] t, int[] i) -> ()", &jr::wgrad_op);
   m.def("pyr_bwd_dc(Tensor?[] t, int[] i, float scale) -> ()", &jr::pyr_bwd_dc_op);
-  m.def("upsample_bilinear_bwd(Tensor?[] t, int[] i) -> ()", &jr::upsample_bilinear_bwd_op);
   m.def("seq_loss(Tensor?[] t, int[] i, float max_flow) -> ()", &jr::seq_loss_op);
   m.def("seq_loss_blocks(int P) -> int", &jr::seq_loss_blocks_op);
   m.def("seq_loss_bwd(Tensor?[] t, int[] i, float max_flow) -> ()", &jr::seq_loss_bwd_op);
-  m.def("conv_f32(Tensor?[] t, int[] i, float alpha) -> ()", &jr::conv_f32_op);
-  m.def("stats_f32(Tensor?[] t, int[] i) -> ()", &jr::stats_f32_op);
-  m.def("norm_act_f32(Tensor?[] t, int[] i, float eps) -> ()", &jr::norm_act_f32_op);
-  m.def("prep_f32(Tensor?[] t, int[] i) -> ()", &jr::prep_f32_op);
-  m.def("copy_channels_f32(Tensor?[] t, int[] i) -> ()", &jr::copy_channels_f32_op);
-  m.def("upsample_convex_f32(Tensor?[] t, int[] i) -> ()", &jr::upsample_convex_f32_op);
-  m.def("corr_pool_f32(Tensor?[] t, int[] i) -> ()", &jr::corr_pool_f32_op);
-  m.def("lookup_f32(Tensor?[] t, int[] i) -> ()", &jr::lookup_f32_op);
-  m.def("flow_update_f32(Tensor?[] t, int[] i) -> ()", &jr::flow_update_f32_op);
-  m.def("init_flow(Tensor?[] t, int[] i) -> ()", &jr::init_flow_op);
-  m.def("init_flow_f32(Tensor?[] t, int[] i) -> ()", &jr::init_flow_f32_op);
-  m.def("forward_project(Tensor?[] t, int[] i) -> ()", &jr::forward_project_op);
-  m.class_<jr::Plan>("Plan")
+  auto plan = m.class_<jr::Plan>("Plan")
       .def(torch::init<>())
       .def("set_segment", &jr::Plan::set_segment)
       .def("capture_pipelined", &jr::Plan::capture_pipelined)
@@ -2431,50 +1930,6 @@ TORCH_LIBRARY(jax_raft_amd, m) {
       .def("add_record", &jr::Plan::add_record)
       .def("add_wait", &jr::Plan::add_wait)
       .def("num_lanes", &jr::Plan::num_lanes)
-      .def("add_conv", &jr::Plan::add_conv)
-      .def("add_conv_alt", &jr::Plan::add_conv_alt)
-      .def("add_corr", &jr::Plan::add_corr)
-      .def("add_lookup", &jr::Plan::add_lookup)
-      .def("add_upsample_convex", &jr::Plan::add_upsample_convex)
-      .def("add_convex_head", &jr::Plan::add_convex_head)
-      .def("add_upsample_bilinear", &jr::Plan::add_upsample_bilinear)
-      .def("add_stats", &jr::Plan::add_stats)
-      .def("add_norm_act", &jr::Plan::add_norm_act)
-      .def("add_prep", &jr::Plan::add_prep)
-      .def("add_init_coords", &jr::Plan::add_init_coords)
-      .def("add_init_flow", &jr::Plan::add_init_flow)
-      .def("add_init_flow_f32", &jr::Plan::add_init_flow_f32)
-      .def("add_memset", &jr::Plan::add_memset)
-      .def("add_copy", &jr::Plan::add_copy)
-      .def("add_copy_channels", &jr::Plan::add_copy_channels)
-      .def("add_flow_taps", &jr::Plan::add_flow_taps)
-      .def("add_taps_gemm", &jr::Plan::add_taps_gemm)
-      .def("add_gru_fused", &jr::Plan::add_gru_fused)
-      .def("add_gru_halo", &jr::Plan::add_gru_halo)
-      .def("add_stats_final", &jr::Plan::add_stats_final)
-      .def("add_flowin_dual", &jr::Plan::add_flowin_dual)
-      .def("add_conv_group", &jr::Plan::add_conv_group)
-      .def("add_conv1x1", &jr::Plan::add_conv1x1)
-      .def("add_conv_direct", &jr::Plan::add_conv_direct)
-      .def("add_conv_train", &jr::Plan::add_conv_train)
-      .def("add_upsample_convex_bwd", &jr::Plan::add_upsample_convex_bwd)
-      .def("add_flow_gather_bwd", &jr::Plan::add_flow_gather_bwd)
-      .def("add_norm_bwd", &jr::Plan::add_norm_bwd)
-      .def("add_pack", &jr::Plan::add_pack)
-      .def("add_wgrad", &jr::Plan::add_wgrad)
-      .def("add_bn_table", &jr::Plan::add_bn_table)
-      .def("add_upsample_bilinear_bwd", &jr::Plan::add_upsample_bilinear_bwd)
-      .def("add_lookup_bwd", &jr::Plan::add_lookup_bwd)
-      .def("add_im2col", &jr::Plan::add_im2col)
-      .def("add_conv_f32", &jr::Plan::add_conv_f32)
-      .def("add_stats_f32", &jr::Plan::add_stats_f32)
-      .def("add_norm_act_f32", &jr::Plan::add_norm_act_f32)
-      .def("add_prep_f32", &jr::Plan::add_prep_f32)
-      .def("add_copy_channels_f32", &jr::Plan::add_copy_channels_f32)
-      .def("add_upsample_convex_f32", &jr::Plan::add_upsample_convex_f32)
-      .def("add_corr_pool_f32", &jr::Plan::add_corr_pool_f32)
-      .def("add_lookup_f32", &jr::Plan::add_lookup_f32)
-      .def("add_flow_update_f32", &jr::Plan::add_flow_update_f32)
       .def("num_ops", &jr::Plan::num_ops)
       .def("op_names", &jr::Plan::op_names)
       .def("run", &jr::Plan::run)
@@ -2487,4 +1942,5 @@ TORCH_LIBRARY(jax_raft_amd, m) {
       .def("captured_part_iters", &jr::Plan::captured_part_iters)
       .def("replay_part", &jr::Plan::replay_part)
       .def("reset_graph", &jr::Plan::reset_graph);
+  jr::register_ops(m, plan);
 }

@@ -4,6 +4,10 @@ The library is built in-tree by :mod:`jax_raft_amd._build`.  On a GPU machine
 the native path is the only GPU implementation: if the library cannot be
 loaded, GPU execution fails loudly instead of silently falling back to
 PyTorch ops.
+
+Every launch op is one row of the op table in ``csrc/runtime/binding.cpp``; the eager op
+``ops().<name>`` and the recording ``new_plan().add_<name>`` are generated from it, and both check
+the int list's length against the row (``ops().op_arity(name)``) before anything else.
 """
 from __future__ import annotations
 

@@ -1,7 +1,8 @@
 """Native MI355X inference engine: lowers a :class:`~jax_raft_amd.models.raft.RAFT`
 onto the gfx950 kernels as one :class:`Plan` (prologue = encoders + correlation
 pyramid, loop body = one refinement iteration) and runs it eagerly from C++
-or as a single captured hipGraph.
+or as a single captured hipGraph.  The plan executor is ``csrc/runtime/plan.h``; the
+``add_<op>`` methods used here are generated from the op table of ``csrc/runtime/binding.cpp``.
 
 Mapping to the reference forward (``jax_raft/model.py:557-605``):
 
