@@ -294,6 +294,15 @@ int jr_init_flow_f32(const float* flow_init, int N, int h, int w, float* coords,
 // every call (two launches: atomic-min splat, resolve + hole fill); 0 <= fill_radius <= 8.
 int jr_forward_project(const float* flow, void* keys, float* out, int B, int h, int w, int fill_radius,
                        hipStream_t stream);
+// Forward-backward consistency check (fbcheck.hip; models/reference.py:fb_consistency, bitwise):
+// the occlusion masks of both directions in one launch.  flow_fw / flow_bw fp32 [B][H][W][2], or
+// (slot: a device int64 holding a base address, read at run time) the two flows at float offsets
+// off_fw / off_bw from it.  occ uint8 [2][B][H][W] (0 = fw, 1 = bw; 1 = occluded), err (optional)
+// fp32 alike, thr fp32 [2] = (alpha, beta) on the device.  (H0, W0, top, left): the frame's
+// rectangle inside the map.  W % 4 == 0; flows, occ, err 16-byte aligned.
+int jr_fb_check(const float* flow_fw, const float* flow_bw, const void* slot, long off_fw, long off_bw,
+                const float* thr, void* occ, float* err, int B, int H, int W, int H0, int W0, int top, int left,
+                hipStream_t stream);
 // Conv of a 2-channel input (the flow branch's 7x7 / 3x3): x bf16 NHWC
 // [N][H][W][x_cstride] (channels 0, 1 used), stride 1, output H x W; w bf16
 // MFMA A fragments [cout/16][NKC][64 lanes][8] (jax_raft_amd/ops/native.py:

@@ -1663,6 +1663,65 @@ static Launch make_forward_project(const TList& t, const IList& i, std::vector<a
   return [=](hipStream_t s, int) { return jr_forward_project(fp, kp, op, B, h, w, R, s); };
 }
 
+// ------------------------------------------------ forward-backward consistency
+// (kernel fbcheck.hip).  t = [flow_fw?, flow_bw? (fp32 [B][H][W][2]), occ (uint8 [2][B][H][W]), err? (fp32, like occ),
+// thr (fp32 [2] = alpha, beta), out_slot?], i = [B, H, W, H0, W0, top, left(, off_fw, off_bw)].
+// With out_slot (a plan: device int64 holding the output base address at run time, see make_convex_head)
+// the flows are read at float offsets off_fw / off_bw from that address and t[0], t[1] stay empty.
+static Launch make_fb_check(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  at::Tensor fw = opt(t, 0), bw = opt(t, 1), occ = opt(t, 2), err = opt(t, 3), thr = opt(t, 4), slot = opt(t, 5);
+  const int B = (int)i[0], H = (int)i[1], W = (int)i[2], H0 = (int)i[3], W0 = (int)i[4], top = (int)i[5], left = (int)i[6];
+  TORCH_CHECK(B >= 1 && H >= 1 && W >= 4 && W % 4 == 0 && (int64_t)H * W <= 0x3fffffff, "fb_check: sizes (W % 4 == 0)");
+  TORCH_CHECK(H0 >= 1 && W0 >= 1 && top >= 0 && left >= 0 && top + H0 <= H && left + W0 <= W,
+              "fb_check: the window (H0, W0, top, left) must lie inside the map");
+  const int64_t M = (int64_t)B * H * W;
+  auto aligned = [](const at::Tensor& v) { return reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0; };
+  auto overlap = [](const at::Tensor& a, const at::Tensor& b) {
+    const char *a0 = (const char*)a.data_ptr(), *b0 = (const char*)b.data_ptr();
+    return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
+  };
+  TORCH_CHECK(occ.defined() && occ.is_cuda() && occ.scalar_type() == at::kByte && occ.is_contiguous() &&
+                  occ.numel() == 2 * M && aligned(occ), "fb_check: occ must be a contiguous device uint8 [2][B][H][W], 16-byte aligned");
+  if (err.defined()) {
+    check_f32(err, "fb_check: err");
+    TORCH_CHECK(err.numel() == 2 * M && aligned(err), "fb_check: err [2][B][H][W], 16-byte aligned");
+    TORCH_CHECK(!overlap(err, occ), "fb_check: err aliases occ");
+  }
+  check_f32(thr, "fb_check: thr");
+  TORCH_CHECK(thr.numel() == 2, "fb_check: thr must hold [alpha, beta]");
+  int64_t off_fw = 0, off_bw = 0;
+  if (slot.defined()) {
+    TORCH_CHECK(slot.is_cuda() && slot.scalar_type() == at::kLong && slot.numel() == 1,
+                "fb_check: out_slot must be one device int64");
+    TORCH_CHECK(!fw.defined() && !bw.defined() && i.size() == 9, "fb_check: out_slot takes [.., off_fw, off_bw] and no flow tensors");
+    off_fw = i[7]; off_bw = i[8];
+    TORCH_CHECK(off_fw >= 0 && off_bw >= 0 && off_fw % 4 == 0 && off_bw % 4 == 0 &&
+                    (off_fw + 2 * M <= off_bw || off_bw + 2 * M <= off_fw), "fb_check: flow offsets (16-byte aligned, disjoint)");
+    keep.push_back(slot);
+  } else {
+    TORCH_CHECK(i.size() == 7, "fb_check: expected [B, H, W, H0, W0, top, left] with flow tensors");
+    check_f32(fw, "fb_check: flow_fw"); check_f32(bw, "fb_check: flow_bw");
+    TORCH_CHECK(fw.numel() == 2 * M && bw.numel() == 2 * M, "fb_check: flows [B][H][W][2]");
+    TORCH_CHECK(aligned(fw) && aligned(bw), "fb_check: flows 16-byte aligned");
+    for (const at::Tensor* f : {&fw, &bw}) {
+      TORCH_CHECK(!overlap(occ, *f), "fb_check: occ aliases a flow");
+      TORCH_CHECK(!err.defined() || !overlap(err, *f), "fb_check: err aliases a flow");
+    }
+    keep.push_back(fw); keep.push_back(bw);
+  }
+  keep.push_back(occ); keep.push_back(thr);
+  if (err.defined()) keep.push_back(err);
+  const float* fp = fw.defined() ? fw.data_ptr<float>() : nullptr;
+  const float* bp = bw.defined() ? bw.data_ptr<float>() : nullptr;
+  const void* sp = slot.defined() ? slot.data_ptr() : nullptr;
+  const float* tp = thr.data_ptr<float>();
+  void* op = occ.data_ptr();
+  float* ep = err.defined() ? err.data_ptr<float>() : nullptr;
+  return [=](hipStream_t s, int) {
+    return jr_fb_check(fp, bp, sp, (long)off_fw, (long)off_bw, tp, op, ep, B, H, W, H0, W0, top, left, s);
+  };
+}
+
 // ------------------------------------------------------------- sequence loss
 // t = [pred (fp32 [N][P][2]), gt (fp32 [P][2]), valid? (fp32 [P]), part (fp32 [blocks][37])], i = [P, N]
 void seq_loss_op(const TList& t, IList i, double max_flow) {
@@ -1805,6 +1864,7 @@ static const std::vector<OpRow>& op_table() {
       row_ti("init_flow", 5, 5, make_init_flow_bf16),
       row_ti("init_flow_f32", 5, 5, make_init_flow_f32),
       row_ti("forward_project", 4, 4, make_forward_project),
+      row_ti("fb_check", 7, 9, make_fb_check),           // flow tensors 7, a plan's output slot 9
       row_t("memset", make_memset),
       row_t("copy", make_copy),
       row_ti("copy_channels", 4, 4, make_copy_channels),

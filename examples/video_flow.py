@@ -4,13 +4,20 @@
 previous pair's refinement loop and this pair's encoders + correlation
 pyramid, and returns the previous pair's flow; ``flush()`` drains the last.
 
-  python examples/video_flow.py frame_0000.png frame_0001.png ... [--arch raft_small] [--iters 12] [--warm-start]
+  python examples/video_flow.py frame_0000.png frame_0001.png ... [--arch raft_small] [--iters 12] [--warm-start | --bidirectional]
 
 ``--warm-start`` runs the synchronous path instead (``RaftEngine.forward``) and
 starts every pair after the first from the previous pair's flow, projected
 forward in time on the GPU (``flow_init="previous"``); ``--iters`` applies as
 given.  (A pipelined step cannot warm-start: it runs the next pair's prologue
 next to the previous pair's loop.)
+
+``--bidirectional`` also runs the synchronous path: every pair yields the flows in both
+directions and the two forward-backward occlusion masks from one engine call
+(``forward(bidirectional=True)``); the backward flows and the masks are kept next to the
+forward flows.  This path feeds the raw uint8 frames: the engine pads them on the GPU, crops
+the flows and the masks back, and its check treats the frame -- not the padded map -- as the
+image, so a landing point in the padding counts as outside.
 
 Without frames a synthetic drifting sequence is used.  Needs an MI355X (the
 native engine); prints the pairs/s of the steady state.
@@ -29,15 +36,17 @@ from jax_raft_amd import raft_large, raft_small  # noqa: E402
 from jax_raft_amd.utils.flow_io import InputPadder, normalize_image, read_image  # noqa: E402
 
 
-def frames(paths, n_synth=16):
+def frames(paths, n_synth=16, raw=False):
+    """Float NHWC frames in [-1, 1]; ``raw``: the uint8 frames themselves, (1, H, W, 3)."""
+    prep = (lambda a: torch.from_numpy(np.ascontiguousarray(a))[None]) if raw else normalize_image
     if paths:
         for p in paths:
-            yield normalize_image(read_image(p))
+            yield prep(read_image(p))
         return
     rng = np.random.default_rng(0)
     base = rng.integers(0, 255, (440 + 8 * n_synth, 1024 + 8 * n_synth, 3), dtype=np.uint8)
     for k in range(n_synth):
-        yield normalize_image(base[3 * k:3 * k + 436, 2 * k:2 * k + 1024])
+        yield prep(base[3 * k:3 * k + 436, 2 * k:2 * k + 1024])
 
 
 def main():
@@ -48,7 +57,10 @@ def main():
     ap.add_argument("--iters", type=int, default=32)
     ap.add_argument("--warm-start", action="store_true",
                     help="synchronous forwards, each pair after the first started from the previous pair's flow")
+    ap.add_argument("--bidirectional", action="store_true",
+                    help="synchronous forwards that return both directions' flows and the occlusion masks")
     args = ap.parse_args()
+    assert not (args.warm_start and args.bidirectional), "--warm-start and --bidirectional exclude each other"
     assert torch.cuda.is_available(), "the pipelined engine runs on the GPU"
     factory = raft_large if args.arch == "raft_large" else raft_small
     model, _ = factory(weights=args.weights) if args.weights else factory()
@@ -57,8 +69,24 @@ def main():
     eng = model.engine(dev)
 
     flows, prev, padder = [], None, None
+    flows_bw, occ_fw, occ_bw = [], [], []
     t0, n_pairs = None, 0
-    for img in frames(args.frames):
+    for img in frames(args.frames, raw=args.bidirectional):
+        if args.bidirectional:   # raw frames: padded, cropped and windowed by the engine
+            cur = img.to(dev)
+            if prev is not None:
+                res = eng.forward(prev, cur, args.iters, return_all_iters=False, bidirectional=True)
+                flows.append(res.flows_fw[-1])
+                flows_bw.append(res.flows_bw[-1])
+                occ_fw.append(res.occ_fw)
+                occ_bw.append(res.occ_bw)
+                if t0 is None:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                else:
+                    n_pairs += 1
+            prev = cur
+            continue
         if padder is None:
             padder = InputPadder(img.shape, channels_last=True)
         (cur,) = padder.pad(img)
@@ -86,6 +114,10 @@ def main():
         flows.append(padder.unpad(last[-1]))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0 if t0 is not None else 0.0
+    if occ_fw:
+        frac = [float(torch.stack(m).float().mean()) for m in (occ_fw, occ_bw)]
+        print(f"{len(flows_bw)} backward flow fields, {len(occ_fw)} mask pairs {tuple(occ_fw[0].shape)}; "
+              f"occluded 1->2 {100 * frac[0]:.1f} %, 2->1 {100 * frac[1]:.1f} %")
     print(f"{len(flows)} flow fields {tuple(flows[0].shape) if flows else ()}; "
           f"steady state {n_pairs / dt if dt > 0 and n_pairs else float('nan'):.1f} pairs/s")
 

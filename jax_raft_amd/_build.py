@@ -49,6 +49,7 @@ KERNEL_SOURCES = [
     CSRC / "kernels" / "merged.hip",
     CSRC / "kernels" / "conv_fam_grp.hip",
     CSRC / "kernels" / "warm.hip",
+    CSRC / "kernels" / "fbcheck.hip",
 ]
 HOST_SOURCES = [CSRC / "runtime" / "binding.cpp"]
 # every header of csrc/ is a dependency of every object (a missed header left stale objects in

@@ -77,7 +77,8 @@ class RAFT(nn.Module):
         return ckpt.variables_from_module(self)
 
     def forward(self, image1, image2, train: bool = False, num_flow_updates: int = 12, return_all_iters: bool = True,
-                flow_init=None, return_flow_low: bool = False, **engine_kw):
+                flow_init=None, return_flow_low: bool = False, bidirectional: bool = False, fb_alpha: float = 0.01,
+                fb_beta: float = 0.5, **engine_kw):
         """Upsampled flows of every refinement iteration, (num_flow_updates, B, H, W, 2)
         (reference semantics, ``model.py:605``).  ``return_all_iters=False`` (inference
         serving mode) upsamples and returns only the final flow, shape (1, B, H, W, 2).
@@ -90,8 +91,24 @@ class RAFT(nn.Module):
         ``return_flow_low=True`` returns ``(flows, flow_low)``, ``flow_low`` (B, H/8, W/8, 2) the
         final ``coords1 - coords0``.  For uint8 frames of any size both are at the *padded*
         size divided by 8 (``runtime/engine.py:sintel_pad``), not at the frame size.  Inference
-        only: with ``train=True`` / ``autograd=True`` they raise ``NotImplementedError``."""
+        only: with ``train=True`` / ``autograd=True`` they raise ``NotImplementedError``.
+
+        Bidirectional flow (video): ``bidirectional=True`` returns
+        :class:`~jax_raft_amd.models.reference.BidirectionalFlow` ``(flows_fw, flows_bw, occ_fw,
+        occ_bw)`` -- the flows 1 -> 2 and 2 -> 1 and the (B, H, W) bool occlusion masks of their
+        forward-backward consistency check (:func:`reference.fb_consistency`, UnFlow's criterion
+        with ``fb_alpha``, ``fb_beta``) -- from one call: one plan of the native engine, or two
+        golden passes plus the golden check elsewhere.  For uint8 frames everything is cropped to
+        the frame.  Inference only, and not together with ``flow_init`` / ``return_flow_low``."""
         image1, image2 = _as_tensor(image1), _as_tensor(image2)
+        if bidirectional:
+            if train or engine_kw.get("autograd"):
+                raise NotImplementedError("bidirectional: inference only (not with train / autograd)")
+            if flow_init is not None or return_flow_low:
+                raise NotImplementedError("bidirectional: not with flow_init / return_flow_low (the warm seed and "
+                                          "the low-resolution output are lowered for one direction)")
+            return self._forward_bidirectional(image1, image2, num_flow_updates, return_all_iters, fb_alpha, fb_beta,
+                                               engine_kw)
         B, H, W, _ = image1.shape
         assert (H, W) == tuple(image2.shape[-3:-1]), "input images should have the same shape"
         warm = dict(flow_init=flow_init, return_flow_low=return_flow_low)
@@ -122,6 +139,27 @@ class RAFT(nn.Module):
             with torch.no_grad():
                 return self.forward_reference(image1, image2, False, num_flow_updates, return_all_iters, **warm)
         return self.forward_reference(image1, image2, train, num_flow_updates, return_all_iters, **warm)
+
+    def _forward_bidirectional(self, image1, image2, num_flow_updates, return_all_iters, alpha, beta, engine_kw):
+        """``forward(bidirectional=True)``: the native engine's bidirectional plan for a model on
+        the GPU it can lower (float or uint8 frames); everywhere else two passes of
+        :meth:`forward` and the golden check of their final flows."""
+        dev = self._param_device()
+        if dev.type == "cuda" and self._lowering_error is None:
+            eng = self._try_engine(dev, {k: v for k, v in engine_kw.items() if k not in ("autograd", "fused")})
+            if eng is not None:
+                if image1.dtype != torch.uint8:
+                    assert image1.shape[1] % 8 == 0 and image1.shape[2] % 8 == 0, \
+                        "input image H and W should be divisible by 8"
+                if not image1.is_cuda and image1.dtype != torch.uint8:
+                    image1, image2 = image1.to(dev), image2.to(dev)
+                return eng.forward(image1, image2, num_flow_updates, return_all_iters=return_all_iters,
+                                   bidirectional=True, fb_alpha=alpha, fb_beta=beta)
+        with torch.no_grad():
+            fw = self.forward(image1, image2, False, num_flow_updates, return_all_iters, **engine_kw)
+            bw = self.forward(image2, image1, False, num_flow_updates, return_all_iters, **engine_kw)
+            occ_fw, occ_bw = R.fb_consistency(fw[-1].contiguous(), bw[-1].contiguous(), alpha, beta)
+        return R.BidirectionalFlow(fw, bw, occ_fw, occ_bw)
 
     def _forward_u8(self, image1, image2, train, num_flow_updates, return_all_iters, engine_kw, warm):
         """Raw uint8 NHWC frames of any size: the reference's input protocol
@@ -172,7 +210,8 @@ class RAFT(nn.Module):
     def apply(self, variables: Mapping[str, Any], image1, image2, train: bool = False, num_flow_updates: int = 12,
               mutable=False, **kw):
         """Flax-style ``model.apply(variables, image1, image2, train, num_flow_updates)``
-        (``flow_init=`` / ``return_flow_low=`` pass through to :meth:`forward`).
+        (``flow_init=`` / ``return_flow_low=`` / ``bidirectional=`` / ``fb_alpha=`` / ``fb_beta=`` pass
+        through to :meth:`forward`).
 
         With ``mutable=['batch_stats']`` (and ``train=True``) returns
         ``(flows, {'batch_stats': updated})`` like Flax."""

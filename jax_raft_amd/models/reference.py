@@ -13,7 +13,7 @@ All tensors are channels-last (NHWC), like the reference.
 from __future__ import annotations
 
 import math
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -32,6 +32,8 @@ __all__ = [
     "neighborhood_offsets",
     "forward_project",
     "fill_offsets",
+    "fb_consistency",
+    "BidirectionalFlow",
 ]
 
 
@@ -418,3 +420,95 @@ def forward_project(flow: torch.Tensor, fill_radius: int = 4) -> torch.Tensor:
         out = torch.where(take.unsqueeze(-1), splat_p[:, R + dy:R + dy + h, R + dx:R + dx + w], out)
         done = done | take
     return out
+
+
+class BidirectionalFlow(NamedTuple):
+    """What a ``bidirectional=True`` forward returns: the flows 1 -> 2 and 2 -> 1, each
+    (N or 1, B, H, W, 2), and the (B, H, W) bool occlusion masks (True = occluded) of the
+    forward-backward check of the two final flows (:func:`fb_consistency`)."""
+    flows_fw: torch.Tensor
+    flows_bw: torch.Tensor
+    occ_fw: torch.Tensor
+    occ_bw: torch.Tensor
+
+
+def _fb_one(a: torch.Tensor, b: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor):
+    """One direction of :func:`fb_consistency` on whole (B, H, W, 2) maps: (occluded, err)."""
+    B, H, W, _ = a.shape
+    grid = make_coords_grid(1, H, W, device=a.device)
+    fx, fy = a[..., 0], a[..., 1]
+    px = grid[..., 0] + fx
+    py = grid[..., 1] + fy
+    inside = (px >= 0) & (px <= W - 1) & (py >= 0) & (py <= H - 1)   # NaN fails
+    zero = torch.zeros((), dtype=torch.float32, device=a.device)
+    pxs = torch.where(inside, px, zero)
+    pys = torch.where(inside, py, zero)
+    x0f, y0f = torch.floor(pxs), torch.floor(pys)
+    wx, wy = (pxs - x0f).unsqueeze(-1), (pys - y0f).unsqueeze(-1)
+    x0, y0 = x0f.long(), y0f.long()
+    x1, y1 = torch.clamp(x0 + 1, max=W - 1), torch.clamp(y0 + 1, max=H - 1)
+    bf = b.reshape(B, H * W, 2)
+
+    def tap(yy, xx):
+        idx = (yy * W + xx).reshape(B, H * W, 1).expand(-1, -1, 2)
+        return torch.gather(bf, 1, idx).view(B, H, W, 2)
+
+    b00, b01, b10, b11 = tap(y0, x0), tap(y0, x1), tap(y1, x0), tap(y1, x1)
+    top = b00 + wx * (b01 - b00)
+    bot = b10 + wx * (b11 - b10)
+    g = top + wy * (bot - top)
+    d = a + g
+    err = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]
+    mag = (fx * fx + fy * fy) + (g[..., 0] * g[..., 0] + g[..., 1] * g[..., 1])
+    thr = alpha * mag + beta
+    occ = ~inside | ~(err <= thr)
+    return occ, torch.where(inside, err, torch.full((), float("inf"), device=a.device))
+
+
+def fb_consistency(flow_fw: torch.Tensor, flow_bw: torch.Tensor, alpha: float = 0.01, beta: float = 0.5,
+                   window: Optional[Tuple[int, int, int, int]] = None, return_err: bool = False):
+    """Forward-backward consistency check (UnFlow, Meister et al. 2018): the occlusion masks of
+    a flow pair.  flow_fw (1 -> 2), flow_bw (2 -> 1): (B, H, W, 2) fp32, channel 0 = x, in
+    pixels; returns ``(occ_fw, occ_bw)``, (B, H, W) bool, True = occluded; with
+    ``return_err`` also the two fp32 error maps ``(occ_fw, occ_bw, err_fw, err_bw)``.
+
+    ``window = (H0, W0, top, left)``: the frame is that rectangle of the map (uint8 frames that
+    were padded); coordinates are relative to it, pixels outside it get False (err 0).
+
+    A fixed sequence of fp32 operations, every product and sum rounded on its own (the kernel
+    csrc/kernels/fbcheck.hip equals it bit for bit).  For a frame pixel (y, x) with flow
+    ``f = a[y, x]`` (``a`` this direction's flow, ``b`` the opposite one):
+
+    1. ``px = float(x) + f.x``, ``py = float(y) + f.y``; ``inside`` iff ``0 <= px <= W0-1`` and
+       ``0 <= py <= H0-1`` (NaN fails).
+    2. ``x0 = floor(px)``, ``x1 = min(x0+1, W0-1)``, ``wx = px - float(x0)``; y likewise.
+    3. Bilinear per channel: ``top = b00 + wx*(b01 - b00)``, ``bot = b10 + wx*(b11 - b10)``,
+       ``g = top + wy*(bot - top)``.
+    4. ``d = f + g``, ``err = d.x*d.x + d.y*d.y``,
+       ``mag = (f.x*f.x + f.y*f.y) + (g.x*g.x + g.y*g.y)``, ``thr = alpha*mag + beta``.
+    5. ``occluded = !inside || !(err <= thr)``; the err map holds ``err``, ``inf`` where ``!inside``.
+
+    ``alpha = 0.01``, ``beta = 0.5`` are UnFlow's published defaults."""
+    for f in (flow_fw, flow_bw):
+        assert f.ndim == 4 and f.shape[-1] == 2 and f.dtype == torch.float32, "flows: (B, H, W, 2) fp32"
+    assert flow_fw.shape == flow_bw.shape, "flow_fw and flow_bw must have the same shape"
+    B, H, W, _ = flow_fw.shape
+    H0, W0, top, left = (H, W, 0, 0) if window is None else map(int, window)
+    assert H0 >= 1 and W0 >= 1 and top >= 0 and left >= 0 and top + H0 <= H and left + W0 <= W, \
+        "window (H0, W0, top, left) must lie inside the map"
+    dev = flow_fw.device
+    al = torch.tensor(alpha, dtype=torch.float32, device=dev)
+    be = torch.tensor(beta, dtype=torch.float32, device=dev)
+    fw = flow_fw[:, top:top + H0, left:left + W0]
+    bw = flow_bw[:, top:top + H0, left:left + W0]
+    res = []
+    for a, b in ((fw, bw), (bw, fw)):
+        o, e = _fb_one(a, b, al, be)
+        occ = torch.zeros((B, H, W), dtype=torch.bool, device=dev)
+        err = torch.zeros((B, H, W), dtype=torch.float32, device=dev)
+        occ[:, top:top + H0, left:left + W0] = o
+        err[:, top:top + H0, left:left + W0] = e
+        res.append((occ, err))
+    if return_err:
+        return res[0][0], res[1][0], res[0][1], res[1][1]
+    return res[0][0], res[1][0]

@@ -585,6 +585,51 @@ def forward_project(flow: torch.Tensor, fill_radius: int = 4, keys: Optional[tor
     return out
 
 
+def fb_check(flow_fw: torch.Tensor, flow_bw: torch.Tensor, alpha: float = 0.01, beta: float = 0.5,
+             window: Optional[Tuple[int, int, int, int]] = None, return_err: bool = False,
+             thr: Optional[torch.Tensor] = None):
+    """Forward-backward occlusion masks ``(occ_fw, occ_bw)`` of a (B, H, W, 2) fp32 flow pair
+    (+ the fp32 error maps with ``return_err``): ``models/reference.py:fb_consistency`` -- that
+    golden op itself on CPU tensors, the HIP kernel (bitwise equal, one launch for both
+    directions) on GPU tensors.  ``window = (H0, W0, top, left)``: the frame's rectangle inside
+    the map (default: the whole map).
+
+    This stand-alone front-end uploads ``[alpha, beta]`` from the host on every call; pass
+    ``thr``, a 2-element fp32 device tensor that already holds them (``alpha`` / ``beta`` are then
+    ignored), to avoid that copy.  A width that is no multiple of 4 costs a padded copy of both
+    flows.  (In a bidirectional plan the thresholds are written only when they change.)"""
+    if not flow_fw.is_cuda:
+        from ..models.reference import fb_consistency
+
+        return fb_consistency(flow_fw, flow_bw, alpha, beta, window, return_err)
+    for f in (flow_fw, flow_bw):
+        if f.ndim != 4 or f.shape[-1] != 2 or f.dtype != torch.float32:
+            raise ValueError(f"fb_check: flows must be (B, H, W, 2) fp32, got {tuple(f.shape)} {f.dtype}")
+    if flow_fw.shape != flow_bw.shape:
+        raise ValueError("fb_check: flow_fw and flow_bw must have the same shape")
+    B, H, W, _ = flow_fw.shape
+    win = [H, W, 0, 0] if window is None else [int(v) for v in window]
+    Wp = round_up(W, 4)
+    if Wp != W:   # the kernel takes 4 pixels per thread: zero columns outside the frame window
+        flow_fw = torch.nn.functional.pad(flow_fw, (0, 0, 0, Wp - W))
+        flow_bw = torch.nn.functional.pad(flow_bw, (0, 0, 0, Wp - W))
+    dev = flow_fw.device
+    occ = torch.empty((2, B, H, Wp), dtype=torch.uint8, device=dev)
+    err = torch.empty((2, B, H, Wp), dtype=torch.float32, device=dev) if return_err else None
+    if thr is None:
+        thr = torch.tensor([alpha, beta], dtype=torch.float32, device=dev)
+
+    def vec(f):   # the kernel's 16-byte loads: a view at an odd pixel offset is copied
+        f = f.contiguous()
+        return f.clone() if f.data_ptr() % 16 else f
+
+    ops().fb_check([vec(flow_fw), vec(flow_bw), occ, err, thr], [B, H, Wp] + win)
+    occ = occ[..., :W].bool()
+    if return_err:
+        return occ[0], occ[1], err[0, ..., :W], err[1, ..., :W]
+    return occ[0], occ[1]
+
+
 def conv2d(spec: ConvSpec, x: torch.Tensor, act: int = ACT_NONE, out_dtype=torch.bfloat16, alpha: float = 1.0,
            res: Optional[torch.Tensor] = None, res_post: int = 0, cfg: Optional[int] = None) -> torch.Tensor:
     """Eager NHWC conv of a contiguous bf16 tensor [N, H, W, C] (C == cin8)."""

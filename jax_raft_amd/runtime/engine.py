@@ -39,6 +39,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from ..models.reference import BidirectionalFlow
 from ..models.layers import (
     NORM_BATCH,
     NORM_CUSTOM,
@@ -156,6 +157,11 @@ class _PlanState:
     flow_init: Optional[torch.Tensor] = None
     keys: Optional[torch.Tensor] = None
     flow_out: List[tuple] = field(default_factory=list)
+    # bidirectional plans: the forward-backward check's mask buffer (2, B, H, W) uint8 (0 = 1 -> 2),
+    # its device-side thresholds [alpha, beta] and the values they currently hold
+    occ: Optional[torch.Tensor] = None
+    thr: Optional[torch.Tensor] = None
+    thr_vals: Optional[Tuple[float, float]] = None
 
 
 _VERSION = operator.attrgetter("_version")
@@ -367,8 +373,10 @@ class RaftEngine:
         return (B, H, W, n_iters, bool(all_iters))
 
     def _build_key(self, key: tuple) -> _PlanState:
-        """Key layout: (B, H, W, n, all)[ + ("u8", H0, W0, pt, pl)][ + ("warm",)][ + ("pslot", slot)]."""
+        """Key layout: (B, H, W, n, all)[ + ("u8", H0, W0, pt, pl)][ + ("warm",) | ("bidir",)][ + ("pslot", slot)]."""
         src = tuple(key[6:10]) if len(key) >= 10 and key[5] == "u8" else None
+        if "bidir" in key[5:]:
+            return self._build_bidir(*key[:5], src)
         return self._build(*key[:5], src=src, warm="warm" in key[5:])
 
     @staticmethod
@@ -1096,18 +1104,31 @@ class RaftEngine:
                src: Optional[Tuple[int, int, int, int]] = None, warm: bool = False) -> _PlanState:
         if warm and self.cp:
             raise NotImplementedError("warm start (flow_init) is not lowered under context parallelism")
-        on = self.uses_lanes(B, all_iters)
+        parts = self.split if (self.split > 1 and B % self.split == 0 and not self.cp) else 1
+        nb = B // parts
+        st, lanes = self._new_state(B, H, W, n_iters, all_iters, src, self.uses_lanes(B, all_iters), parts, B)
+        if warm:
+            st.flow_init = torch.zeros((B, H // 8, W // 8, 2), dtype=F32, device=self.device)
+        for part, plan in enumerate(st.plans):
+            self._build_part(st, plan, part * nb, nb, H, W, n_iters, f"p{part}.", lanes, 0, all_iters, warm)
+            plan.set_lane(0)
+            plan.set_segment(2)
+        return st
+
+    def _new_state(self, B: int, H: int, W: int, n_iters: int, all_iters: bool,
+                   src: Optional[Tuple[int, int, int, int]], on: bool, parts: int, out_batch: int):
+        """What every plan of this engine starts from, cold, warm or bidirectional: the size guard
+        of the correlation pyramid, the lane decision ``on`` taken over, ``parts`` empty native
+        plans, the input buffers of ``B`` image pairs and the output of ``out_batch`` flows per
+        iteration with its slot.  Returns ``(state, (main, side, side2) lanes)``."""
         self.streams = on
         self.mask_head = "split" if on else "fused"
         h, w = H // 8, W // 8
-        L = self.num_levels
-        min_sz = 2 * (2 ** (L - 1))
+        min_sz = 2 * (2 ** (self.num_levels - 1))
         assert h >= min_sz and w >= min_sz, (
             f"Feature maps are too small to be down-sampled by the correlation pyramid: need >= {min_sz}, got {(h, w)}; "
             f"input images should be at least {8 * min_sz}.")
         dev = self.device
-        parts = self.split if (self.split > 1 and B % self.split == 0 and not self.cp) else 1
-        nb = B // parts
         # Each part is an independent forward with its own Plan; with use_graph
         # their captures are copied into ONE hipGraph (Plan.merge_*), so the
         # parts' kernels fill each other's idle CUs.
@@ -1119,24 +1140,58 @@ class RaftEngine:
         else:
             st.inp1 = torch.zeros((B, H, W, 3), dtype=F32, device=dev)
             st.inp2 = torch.zeros((B, H, W, 3), dtype=F32, device=dev)
-        st.out = torch.zeros((n_iters if all_iters else 1, B, H, W, 2), dtype=F32, device=dev)
+        st.out = torch.zeros((n_iters if all_iters else 1, out_batch, H, W, 2), dtype=F32, device=dev)
         st.slot_ptr = st.out.data_ptr()
         st.out_slot = torch.tensor([st.slot_ptr], dtype=torch.int64, device=dev)
-        if warm:
-            st.flow_init = torch.zeros((B, h, w, 2), dtype=F32, device=dev)
-        lanes = (0, 1, 2) if on else (0, 0, 0)
-        for part, plan in enumerate(plans):
-            self._build_part(st, plan, part * nb, nb, H, W, n_iters, f"p{part}.", lanes, 0, all_iters, warm)
-            plan.set_lane(0)
-            plan.set_segment(2)
+        return st, ((0, 1, 2) if on else (0, 0, 0))
+
+    def _build_bidir(self, B: int, H: int, W: int, n_iters: int, all_iters: bool,
+                     src: Optional[Tuple[int, int, int, int]]) -> _PlanState:
+        """The plan of ``forward(bidirectional=True)``: one part whose loop runs both directions at
+        batch 2B (:meth:`_build_part` with ``bidir``), so the lane decision, the ConvGRU lowering
+        and every tile choice are those of loop batch 2B; ``out`` is (N, 2B, H, W, 2) with 1 -> 2
+        in ``[:, :B]`` and 2 -> 1 in ``[:, B:]``.  The epilogue ends with the forward-backward
+        check (fbcheck.hip) of the final iteration's two flows, on lane 0 after the last
+        upsampling; it reads them through the output slot, where that replay wrote them."""
+        if self.cp:
+            raise NotImplementedError("bidirectional flow is not lowered under context parallelism")
+        saved, self.split = self.split, 1   # one part (``split`` lays ``out`` by part)
+        try:
+            on = self.uses_lanes(2 * B, all_iters)
+        finally:
+            self.split = saved
+        st, lanes = self._new_state(B, H, W, n_iters, all_iters, src, on, 1, 2 * B)
+        plan = st.plan
+        st.occ = torch.zeros((2, B, H, W), dtype=torch.uint8, device=self.device)
+        st.thr = torch.zeros(2, dtype=F32, device=self.device)
+        self._build_part(st, plan, 0, B, H, W, n_iters, "p0.", lanes, 0, all_iters, bidir=True)
+        plan.set_lane(0)
+        plan.set_segment(2)
+        # the final iteration's flows: the last slice of ``out``, its two batch halves
+        last = st.out[-1]
+        window = [H, W, 0, 0] if src is None else list(src)
+        if st.slot_ok:
+            off = (last.data_ptr() - st.out.data_ptr()) // 4
+            plan.add_fb_check([None, None, st.occ, None, st.thr, st.out_slot],
+                              [B, H, W] + window + [off, off + B * H * W * 2])
+        else:   # a generic mask head writes the captured buffer itself
+            plan.add_fb_check([last[:B], last[B:], st.occ, None, st.thr], [B, H, W] + window)
         return st
 
     def _build_part(self, st: _PlanState, plan, b0: int, B: int, H: int, W: int, n_iters: int, pt: str,
-                    lanes: Tuple[int, int, int], ev0: int, all_iters: bool = True, warm: bool = False):
+                    lanes: Tuple[int, int, int], ev0: int, all_iters: bool = True, warm: bool = False,
+                    bidir: bool = False):
         """Lower one forward over images [b0, b0 + B) onto ``plan`` using lanes
         (main, side, side2) and events ev0 .. ev0 + 8.  ``warm``: the loop starts from the
         plan's ``flow_init`` slice instead of zero flow (``init_flow`` in place of
         ``init_coords``; everything else, and every cold plan, is unchanged).
+
+        ``bidir``: both directions in one loop of batch 2B -- samples [0, B) refine the flow
+        1 -> 2, samples [B, 2B) the flow 2 -> 1.  ``prep`` and the feature encoder are the cold
+        plan's (``fmap`` already holds both frames' features); the context encoder, the GRU
+        context biases and ``init_coords`` run over all 2B images of ``x0``, a second ``corr``
+        launch with the ``fmap`` halves swapped fills the second half of every pyramid level,
+        and everything from the loop body on runs at the loop batch 2B.
 
         Three loop schedules (``model.py:495-510`` per iteration):
 
@@ -1161,6 +1216,10 @@ class RaftEngine:
         bufs = st.bufs
         sp = self._specs
         h, w = H // 8, W // 8
+        Bi = B                 # image pairs: prep, the feature encoder, each correlation launch
+        if bidir:
+            assert b0 == 0 and not warm and not self.cp, "bidirectional plans: one part, cold, no context parallelism"
+            B = 2 * B          # the loop batch: context encoder, pyramid rows, loop body, upsampling
         M = B * h * w
         L = self.num_levels
 
@@ -1169,8 +1228,8 @@ class RaftEngine:
             bufs[pt + name] = t
             return t
 
-        inp1 = st.inp1[b0:b0 + B]
-        inp2 = st.inp2[b0:b0 + B]
+        inp1 = st.inp1[b0:b0 + Bi]
+        inp2 = st.inp2[b0:b0 + Bi]
         out = st.out[:, b0:b0 + B]
         out_off = (out.data_ptr() - st.out.data_ptr()) // 4   # in floats, from the slot's base
 
@@ -1191,13 +1250,13 @@ class RaftEngine:
         # PRO_LANES = "off": never, "on": always (per-image feature-encoder lanes at batch 1 too).
         pl = self.PRO_LANES
         assert pl in ("auto", "on", "off"), pl
-        pro_on = pl == "on" or (pl == "auto" and B * h * w <= 4 * 55 * 128)
+        pro_on = pl == "on" or (pl == "auto" and Bi * h * w <= 4 * 55 * 128)
         p_main, p_side, p_side2 = lanes if lanes_on or self.cp or not pro_on else (main, 1, 2)
         p_on = p_main != p_side
         # the per-image feature-encoder split (lane 2) -- never at batch 1 under "auto", also not in
         # a pipelined slot's multi-lane plan, so that its kernels (tile configs of the batch-2
         # chain) and results equal the synchronous forward's bit for bit
-        fe_split = p_on and not (pl == "auto" and B == 1)
+        fe_split = p_on and not (pl == "auto" and Bi == 1)
 
         def lane(l):
             plan.set_lane(l)
@@ -1216,19 +1275,21 @@ class RaftEngine:
         for t in (hx, qx, flow8, flow32):
             plan.add_memset([t])
         s2d = "fe.stem_s2d" in sp and "ce.stem_s2d" in sp and H % 2 == 0 and W % 2 == 0
-        x0 = alloc("x0", (2 * B, H // 2, W // 2, 16) if s2d else (2 * B, H, W, 8))
+        x0 = alloc("x0", (2 * Bi, H // 2, W // 2, 16) if s2d else (2 * Bi, H, W, 8))
         if st.src is not None:   # uint8 frames: normalise + replicate pad + layout in one kernel (K14)
             H0, W0, pad_t, pad_l = st.src   # (pt is this part's buffer prefix)
-            plan.add_prep([inp1, inp2, x0, u8_table(dev)], [B, H, W, int(s2d), H0, W0, pad_t, pad_l])
+            plan.add_prep([inp1, inp2, x0, u8_table(dev)], [Bi, H, W, int(s2d), H0, W0, pad_t, pad_l])
         elif s2d:   # 2x2 space-to-depth images for the 4x4 form of the 7x7 / stride-2 stems
-            plan.add_prep([inp1, inp2, x0], [B, H, W, 1])
+            plan.add_prep([inp1, inp2, x0], [Bi, H, W, 1])
         else:
-            plan.add_prep([inp1, inp2, x0], [B, H, W])
+            plan.add_prep([inp1, inp2, x0], [Bi, H, W])
         plan.add_record(E_PREP)
 
         lane(p_side)
         plan.add_wait(E_PREP)
-        ctxf, ch_, cw_ = self._encoder(st, plan, "ce", m.context_encoder, x0[:B], B, H, W, bt=pt)
+        # the context of the loop's first frames: image 1 of every pair; bidirectional: both frames
+        ctx_in = x0 if bidir else x0[:Bi]
+        ctxf, ch_, cw_ = self._encoder(st, plan, "ce", m.context_encoder, ctx_in, B, H, W, bt=pt)
         assert (ch_, cw_) == (h, w), "The context encoder should downsample H and W by 8"
         # [tanh(h) | relu(context)] (model.py:582-584); h also as fp32 state
         ce_out = alloc("ce_out", (M, round_up(self.hidden + self.ctx_ch, 8)))
@@ -1255,7 +1316,7 @@ class RaftEngine:
             plan.add_init_coords([coords], [B, h, w])
         plan.add_record(E_CTX)
 
-        fmap = alloc("fmap", (2 * B, h, w, self.fmap_ch))
+        fmap = alloc("fmap", (2 * Bi, h, w, self.fmap_ch))
         if self.fe_external:
             lane(p_main)   # fmap is written before each replay (RaftEngineMixed._pre_launch)
         elif fe_split:
@@ -1265,19 +1326,19 @@ class RaftEngine:
             # pyramid is half as long
             lane(p_side2)
             plan.add_wait(E_PREP)
-            featb, _, _ = self._encoder(st, plan, "fe", m.feature_encoder, x0[B:], B, H, W, bt=pt + "fe2.")
-            self._conv(plan, sp["fe.conv"], featb, B, h, w, fmap[B:])
+            featb, _, _ = self._encoder(st, plan, "fe", m.feature_encoder, x0[Bi:], Bi, H, W, bt=pt + "fe2.")
+            self._conv(plan, sp["fe.conv"], featb, Bi, h, w, fmap[Bi:])
             plan.add_record(E_FE2)
             lane(p_main)
-            feat, fh_, fw_ = self._encoder(st, plan, "fe", m.feature_encoder, x0[:B], B, H, W, bt=pt)
+            feat, fh_, fw_ = self._encoder(st, plan, "fe", m.feature_encoder, x0[:Bi], Bi, H, W, bt=pt)
             assert (fh_, fw_) == (h, w), "The feature encoder should downsample H and W by 8"
-            self._conv(plan, sp["fe.conv"], feat, B, h, w, fmap[:B])
+            self._conv(plan, sp["fe.conv"], feat, Bi, h, w, fmap[:Bi])
             plan.add_wait(E_FE2)
         else:
             lane(p_main)
-            feat, fh_, fw_ = self._encoder(st, plan, "fe", m.feature_encoder, x0, 2 * B, H, W, bt=pt)
+            feat, fh_, fw_ = self._encoder(st, plan, "fe", m.feature_encoder, x0, 2 * Bi, H, W, bt=pt)
             assert (fh_, fw_) == (h, w), "The feature encoder should downsample H and W by 8"
-            self._conv(plan, sp["fe.conv"], feat, 2 * B, h, w, fmap)
+            self._conv(plan, sp["fe.conv"], feat, 2 * Bi, h, w, fmap)
         # bf16 levels of /16-wide maps: levels 0 / 1 in the blocked layout (one
         # pyramid tile per block: whole-line writes, 2 x 2 blocks per lookup window)
         blocked = int(self.corr_dtype == BF16 and w % 16 == 0 and (h * w) % 8 == 0 and not self.cp)
@@ -1303,8 +1364,11 @@ class RaftEngine:
             # pipelined slot, whose graph runs it next to the previous pair's loop (there the
             # short-lived tiles interleave better: b1 stream 227 vs 200-204 FPS, round 4)
             bl = 2 if (blocked and self.CORR_PERSIST_B1 and not getattr(self, "_slot_build", False)) else blocked
-            plan.add_corr([fmap[:B], fmap[B:]] + levels + [None] * (4 - L), [B, h, w, self.fmap_ch, L, h * w, bl],
+            plan.add_corr([fmap[:Bi], fmap[Bi:]] + levels + [None] * (4 - L), [Bi, h, w, self.fmap_ch, L, h * w, bl],
                           scale)
+            if bidir:   # 2 -> 1: the halves swapped, into the second B*h*w query rows of every level
+                plan.add_corr([fmap[Bi:], fmap[:Bi]] + [v[Bi * h * w:] for v in levels] + [None] * (4 - L),
+                              [Bi, h, w, self.fmap_ch, L, h * w, bl], scale)
         plan.add_wait(E_CTX)
 
         # ---------------- loop body: one refinement iteration (model.py:495-510)
@@ -1601,9 +1665,19 @@ class RaftEngine:
     # --------------------------------------------------------------- forward
     @torch.no_grad()
     def forward(self, image1: torch.Tensor, image2: torch.Tensor, num_flow_updates: int = 12,
-                return_all_iters: bool = True, flow_init=None, return_flow_low: bool = False):
+                return_all_iters: bool = True, flow_init=None, return_flow_low: bool = False,
+                bidirectional: bool = False, fb_alpha: float = 0.01, fb_beta: float = 0.5):
         """All ``num_flow_updates`` upsampled flows (N, B, H, W, 2), as the reference
         returns; ``return_all_iters=False`` returns only the final one, (1, B, H, W, 2).
+
+        ``bidirectional=True`` returns :class:`BidirectionalFlow` ``(flows_fw, flows_bw, occ_fw,
+        occ_bw)``: the flows 1 -> 2 and 2 -> 1, each (N or 1, B, H, W, 2), and the (B, H, W) bool
+        occlusion masks of the forward-backward check of the two final flows
+        (``models/reference.py:fb_consistency`` with ``fb_alpha``, ``fb_beta``), from one replay
+        of a plan of its own (plan key + "bidir", :meth:`_build_bidir`).  The thresholds live in
+        a device tensor, so changing them builds no new plan.  Not with ``flow_init`` /
+        ``return_flow_low``, :meth:`pipelined`, context parallelism or the fp32 / mixed engines
+        (``NotImplementedError``); such a call forgets the engine's "previous" flow.
 
         Warm start (video): ``flow_init`` -- a (B, h, w, 2) fp32 tensor in 1/8-resolution
         pixels, channel 0 = x (h, w = the plan's size / 8: the *padded* size for uint8 frames)
@@ -1627,6 +1701,9 @@ class RaftEngine:
             self._last = None
         if self.cp and flow_init is not None:
             raise NotImplementedError("forward(flow_init=...): not with context parallelism (cp_group)")
+        if bidirectional:
+            return self._forward_bidir(image1, image2, num_flow_updates, return_all_iters, flow_init,
+                                       return_flow_low, fb_alpha, fb_beta)
         if image1.dtype == torch.uint8 and not self._native_u8:
             a, b, src = self._host_u8(image1, image2)
             res = self.forward(a, b, num_flow_updates, return_all_iters, flow_init, return_flow_low)
@@ -1688,6 +1765,40 @@ class RaftEngine:
             return res, self._flow_low(st.flow_out, num_flow_updates, h, w)
         return res
 
+    def _forward_bidir(self, image1, image2, n_iters: int, all_iters: bool, flow_init, return_flow_low: bool,
+                       alpha: float, beta: float) -> BidirectionalFlow:
+        """``forward(bidirectional=True)`` (weights already repacked where stale)."""
+        if flow_init is not None or return_flow_low:
+            raise NotImplementedError("forward(bidirectional=True): not with flow_init / return_flow_low (the warm "
+                                      "seed and the low-resolution output are lowered for one direction)")
+        if self.cp:
+            raise NotImplementedError("forward(bidirectional=True): not with context parallelism (its host-driven "
+                                      "loop is not lowered for the swapped correlation halves)")
+        if self.precision != "bf16":
+            raise NotImplementedError(f"forward(bidirectional=True): not with precision={self.precision!r} (the "
+                                      "bidirectional plan is lowered for the bf16 engine only)")
+        # a later flow_init="previous" must not seed from this call's half-batch
+        self._last = None
+        key = self._key(image1, image2, n_iters, all_iters) + ("bidir",)
+        st = self._plan_state(key, lambda: self._build_key(key))
+        st.inp1.copy_(image1)
+        st.inp2.copy_(image2)
+        if st.thr_vals != (float(alpha), float(beta)):   # stream-ordered, before the replay
+            st.thr.copy_(torch.tensor([alpha, beta], dtype=F32))
+            st.thr_vals = (float(alpha), float(beta))
+        self._pre_launch(st)
+        fresh = self.copy_output and st.slot_ok
+        out = torch.empty_like(st.out) if fresh else st.out
+        self._point_slot(st, out)
+        self._gate(n_iters)
+        self._launch(st.plan, n_iters)
+        self._mark()
+        res = self._crop(st, out) if fresh else self._crop(st, st.out.clone() if self.copy_output else st.out)
+        occ = st.occ if st.src is None else st.occ[:, :, st.src[2]:st.src[2] + st.src[0], st.src[3]:st.src[3] + st.src[1]]
+        occ = occ.bool()   # a fresh tensor either way (the plan's buffer is uint8)
+        B = key[0]
+        return BidirectionalFlow(res[:, :B], res[:, B:], occ[0], occ[1])
+
     @staticmethod
     def _flow_low(flow_out, n_iters: int, h: int, w: int, copy: bool = True) -> torch.Tensor:
         """The final 1/8-resolution flow (B, h, w, 2) of a plan that ran ``n_iters`` iterations,
@@ -1739,7 +1850,7 @@ class RaftEngine:
 
     @torch.no_grad()
     def pipelined(self, image1: torch.Tensor, image2: torch.Tensor, num_flow_updates: int = 12,
-                  return_all_iters: bool = True, flow_init=None) -> Optional[torch.Tensor]:
+                  return_all_iters: bool = True, flow_init=None, bidirectional: bool = False) -> Optional[torch.Tensor]:
         """Software-pipelined forward for throughput (batch inference, serving):
         returns the flows of the PREVIOUS call's images (``None`` on the first
         call); :meth:`flush` returns the last pending batch's flows.
@@ -1762,6 +1873,9 @@ class RaftEngine:
         if flow_init is not None:
             raise NotImplementedError("pipelined(flow_init=...): warm start needs the previous pair's final flow, "
                                       "which a pipelined slot's prologue runs concurrently with; use forward()")
+        if bidirectional:
+            raise NotImplementedError("pipelined(bidirectional=True): the bidirectional plan (its second correlation "
+                                      "launch and epilogue check) is not lowered for pipelined slots; use forward()")
         if self._stale():
             self._last = None
             if self._pp is not None and self._pp["pending"] is not None:
