@@ -1,0 +1,227 @@
+// RAFT's dense flow augmentation (photometric jitter, eraser, scale + stretch, flips, crop) as
+// ONE gather over the uint8 frames as they were uploaded, writing the fp32 NHWC tensors the
+// training step consumes.  The semantics are the golden op's (train/augment.py:augment_pairs)
+// and the kernels equal it bit for bit: the same fp32 operations in the same order, every
+// product and sum rounded on its own (contraction is off for this file, below), no operation
+// that is not correctly rounded on both sides (the host supplies every ratio, reciprocal and
+// the hue matrix; the only division is the IEEE x / 255).
+// Two launches, no LDS in the gather, no float atomics:
+//   1. colour sums: per image and channel the integer sum of the source frame (wave reductions,
+//      one integer atomic add per block and channel: order-independent, bitwise repeatable);
+//   2. the gather: grid (runs of a row, rows, samples) -- the sample's 48-word record is
+//      wave-uniform; one thread per 4 consecutive pixels of a row, 16-byte stores.
+#include "common.h"
+#include "kernels.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+// record layout (train/augment.py)
+constexpr int REC_WORDS = 48, I_HR = 0, I_WR = 1, I_Y0 = 2, I_X0 = 3, I_HFLIP = 4, I_VFLIP = 5, I_NRECT = 6, I_RECT = 8;
+constexpr int F_BASE = 16, F_SX = 0, F_SY = 1, F_ISX = 2, F_ISY = 3, F_COL1 = 4, F_COL2 = 16;
+constexpr int SUM_PIX = 16;   // pixels per thread of the sums kernel
+
+// sums int32 [2][B][3] (image 1 frames, then image 2 frames); grid (blocks per frame, 2 * B)
+__global__ __launch_bounds__(256) void augment_sums_kernel(const unsigned char* __restrict__ i1,
+                                                           const unsigned char* __restrict__ i2, int B, int npix,
+                                                           int* __restrict__ sums) {
+  __shared__ int part[4][3];
+  const int n = blockIdx.y;
+  const unsigned char* img = (n < B ? i1 + (long)n * npix * 3 : i2 + (long)(n - B) * npix * 3);
+  const int base = blockIdx.x * (256 * SUM_PIX) + threadIdx.x;
+  int s[3] = {0, 0, 0};
+#pragma unroll 4
+  for (int k = 0; k < SUM_PIX; ++k) {
+    const int p = base + k * 256;
+    if (p < npix) {
+      const unsigned char* px = img + (long)p * 3;
+      s[0] += px[0]; s[1] += px[1]; s[2] += px[2];
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s[c] += __shfl_down(s[c], off, 64);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { part[wave][0] = s[0]; part[wave][1] = s[1]; part[wave][2] = s[2]; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int c = threadIdx.x;
+    atomicAdd(sums + n * 3 + c, (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]));
+  }
+}
+
+struct Colour {
+  float b, k, s, m[9], mean[3], cm;   // cm: the contrast pivot min(255, b * luma(mean))
+};
+
+JR_DEVICE float clamp255(float v) { return fminf(fmaxf(v, 0.f), 255.f); }
+JR_DEVICE float luma(float r, float g, float b) { return (0.299f * r + 0.587f * g) + 0.114f * b; }
+
+JR_DEVICE Colour load_colour(const float* __restrict__ f, const int* __restrict__ sum, int npix) {
+  Colour c;
+  c.b = f[0]; c.k = f[1]; c.s = f[2];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) c.m[j] = f[3 + j];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) c.mean[j] = (float)(((unsigned)sum[j] + (unsigned)(npix / 2)) / (unsigned)npix);
+  c.cm = fminf(c.b * luma(c.mean[0], c.mean[1], c.mean[2]), 255.f);
+  return c;
+}
+
+// brightness, contrast, saturation, hue of one texel, clamped to [0, 255] after every step
+JR_DEVICE void texel(float& r, float& g, float& b, const Colour& c) {
+  r = clamp255(r * c.b); g = clamp255(g * c.b); b = clamp255(b * c.b);
+  if (c.k != 1.f) {
+    r = clamp255((r - c.cm) * c.k + c.cm); g = clamp255((g - c.cm) * c.k + c.cm); b = clamp255((b - c.cm) * c.k + c.cm);
+  }
+  if (c.s != 1.f) {
+    const float l = luma(r, g, b);
+    r = clamp255((r - l) * c.s + l); g = clamp255((g - l) * c.s + l); b = clamp255((b - l) * c.s + l);
+  }
+  const float hr = clamp255((r * c.m[0] + g * c.m[1]) + b * c.m[2]);
+  const float hg = clamp255((r * c.m[3] + g * c.m[4]) + b * c.m[5]);
+  const float hb = clamp255((r * c.m[6] + g * c.m[7]) + b * c.m[8]);
+  r = hr; g = hg; b = hb;
+}
+
+JR_DEVICE float blend(float t00, float t01, float t10, float t11, float wx, float wy) {
+  const float top = t00 + wx * (t01 - t00);
+  const float bot = t10 + wx * (t11 - t10);
+  return top + wy * (bot - top);
+}
+
+// source position of resized coordinate u: taps lo / hi in [0, size - 1] and the weight of hi
+JR_DEVICE void source_pos(int u, float ratio, int size, int& lo, int& hi, float& wgt) {
+  const float s = fminf(fmaxf(((float)u + 0.5f) * ratio - 0.5f, 0.f), (float)(size - 1));
+  const float f = floorf(s);
+  wgt = s - f;
+  lo = min(max((int)f, 0), size - 1);   // clamped whatever the record says: never an out-of-bounds read
+  hi = min(lo + 1, size - 1);
+}
+
+// grid: (ceil(ceil(w / 4) / 64), ceil(h / 4), B), block (64, 4): thread = 4 pixels of one row
+__global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __restrict__ i1,
+                                                      const unsigned char* __restrict__ i2,
+                                                      const float* __restrict__ flow, const int* __restrict__ params,
+                                                      const int* __restrict__ sums, float* __restrict__ o1,
+                                                      float* __restrict__ o2, float* __restrict__ oflow,
+                                                      float* __restrict__ ovalid, int B, int Hs, int Ws, int h, int w) {
+  const int n = blockIdx.z;
+  const int y = blockIdx.y * 4 + threadIdx.y;
+  const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4;
+  if (y >= h || x4 >= w) return;
+  const int* rec = params + n * REC_WORDS;                  // wave-uniform: scalar loads
+  const float* recf = (const float*)(rec + F_BASE);
+  const int npix = Hs * Ws;
+  const int Hr = rec[I_HR], Wr = rec[I_WR], y0 = rec[I_Y0], x0 = rec[I_X0];
+  const bool hflip = rec[I_HFLIP] != 0, vflip = rec[I_VFLIP] != 0;
+  const int nrect = rec[I_NRECT];
+  const float sx = recf[F_SX], sy = recf[F_SY], isx = recf[F_ISX], isy = recf[F_ISY];
+  const Colour c1 = load_colour(recf + F_COL1, sums + n * 3, npix);
+  const Colour c2 = load_colour(recf + F_COL2, sums + (B + n) * 3, npix);
+
+  int v = y + y0, y_lo, y_hi;
+  if (vflip) v = Hr - 1 - v;
+  float wy;
+  source_pos(v, sy, Hs, y_lo, y_hi, wy);
+  const long frame = (long)n * npix;
+  const unsigned char* p1 = i1 + frame * 3;
+  const unsigned char* p2 = i2 + frame * 3;
+  const float* pf = flow + frame * 2;
+
+  float a1[12], a2[12], fl[8], va[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int x = min(x4 + k, w - 1);   // the tail of a width that is no multiple of 4 repeats its last pixel (not stored)
+    int u = x + x0, x_lo, x_hi;
+    if (hflip) u = Wr - 1 - u;
+    float wx;
+    source_pos(u, sx, Ws, x_lo, x_hi, wx);
+    const int ty[4] = {y_lo, y_lo, y_hi, y_hi}, tx[4] = {x_lo, x_hi, x_lo, x_hi};
+    float t1[4][3], t2[4][3], tf[4][2];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const long o = (long)ty[q] * Ws + tx[q];
+      t1[q][0] = (float)p1[o * 3]; t1[q][1] = (float)p1[o * 3 + 1]; t1[q][2] = (float)p1[o * 3 + 2];
+      texel(t1[q][0], t1[q][1], t1[q][2], c1);
+      bool erased = false;
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        erased |= j < nrect && tx[q] >= rec[I_RECT + 4 * j] && tx[q] < rec[I_RECT + 4 * j + 2] &&
+                  ty[q] >= rec[I_RECT + 4 * j + 1] && ty[q] < rec[I_RECT + 4 * j + 3];
+      t2[q][0] = erased ? c2.mean[0] : (float)p2[o * 3];
+      t2[q][1] = erased ? c2.mean[1] : (float)p2[o * 3 + 1];
+      t2[q][2] = erased ? c2.mean[2] : (float)p2[o * 3 + 2];
+      texel(t2[q][0], t2[q][1], t2[q][2], c2);
+      const float2 f = *(const float2*)(pf + o * 2);
+      tf[q][0] = f.x; tf[q][1] = f.y;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      a1[3 * k + c] = blend(t1[0][c], t1[1][c], t1[2][c], t1[3][c], wx, wy) / 255.0f * 2.0f - 1.0f;
+      a2[3 * k + c] = blend(t2[0][c], t2[1][c], t2[2][c], t2[3][c], wx, wy) / 255.0f * 2.0f - 1.0f;
+    }
+    float fx = blend(tf[0][0], tf[1][0], tf[2][0], tf[3][0], wx, wy) * isx;
+    float fy = blend(tf[0][1], tf[1][1], tf[2][1], tf[3][1], wx, wy) * isy;
+    if (hflip) fx = -fx;
+    if (vflip) fy = -fy;
+    const bool ok = fabsf(fx) < 1000.f && fabsf(fy) < 1000.f;   // false for NaN
+    fl[2 * k] = ok ? fx : 0.f;
+    fl[2 * k + 1] = ok ? fy : 0.f;
+    va[k] = ok ? 1.f : 0.f;
+  }
+
+  const long px = ((long)n * h + y) * w + x4;   // first output pixel of the run
+  if ((w & 3) == 0) {                           // every run starts at a multiple of 4 pixels: 16-byte stores
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      *(float4*)(o1 + px * 3 + 4 * j) = make_float4(a1[4 * j], a1[4 * j + 1], a1[4 * j + 2], a1[4 * j + 3]);
+      *(float4*)(o2 + px * 3 + 4 * j) = make_float4(a2[4 * j], a2[4 * j + 1], a2[4 * j + 2], a2[4 * j + 3]);
+    }
+    *(float4*)(oflow + px * 2) = make_float4(fl[0], fl[1], fl[2], fl[3]);
+    *(float4*)(oflow + px * 2 + 4) = make_float4(fl[4], fl[5], fl[6], fl[7]);
+    *(float4*)(ovalid + px) = make_float4(va[0], va[1], va[2], va[3]);
+  } else {                                      // rows start at any pixel: scalar stores, the tail cut off
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (x4 + k < w) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { o1[(px + k) * 3 + c] = a1[3 * k + c]; o2[(px + k) * 3 + c] = a2[3 * k + c]; }
+        oflow[(px + k) * 2] = fl[2 * k];
+        oflow[(px + k) * 2 + 1] = fl[2 * k + 1];
+        ovalid[px + k] = va[k];
+      }
+  }
+}
+
+}  // namespace
+
+extern "C" int jr_augment_sums(const void* img1, const void* img2, int B, int Hs, int Ws, int* sums,
+                               hipStream_t stream) {
+  // a frame's sum plus the rounding term of the mean must fit an int32
+  if (B < 1 || B > 32767 || Hs < 1 || Ws < 1 || (long)Hs * Ws * 255 + (long)Hs * Ws / 2 > 0x7fffffffL || !img1 || !img2 ||
+      !sums)
+    return (int)hipErrorInvalidValue;
+  const int npix = Hs * Ws;
+  hipError_t e = hipMemsetAsync(sums, 0, sizeof(int) * 6 * (size_t)B, stream);   // ordered before the adds
+  if (e != hipSuccess) return (int)e;
+  const dim3 grid((unsigned)((npix + 256 * SUM_PIX - 1) / (256 * SUM_PIX)), (unsigned)(2 * B));
+  hipLaunchKernelGGL(augment_sums_kernel, grid, dim3(256), 0, stream, (const unsigned char*)img1,
+                     (const unsigned char*)img2, B, npix, sums);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jr_augment(const void* img1, const void* img2, const float* flow, const int* params, const int* sums,
+                          float* out1, float* out2, float* out_flow, float* valid, int B, int Hs, int Ws, int h, int w,
+                          hipStream_t stream) {
+  if (B < 1 || B > 65535 || Hs < 1 || Ws < 1 || h < 1 || w < 1 || h > 65535 * 4 || (long)Hs * Ws > 0x7fffffffL / 256 ||
+      (long)h * w > 0x3fffffffL || !img1 || !img2 || !flow || !params || !sums || !out1 || !out2 || !out_flow || !valid)
+    return (int)hipErrorInvalidValue;
+  const int runs = (w + 3) / 4;
+  const dim3 grid((unsigned)((runs + 63) / 64), (unsigned)((h + 3) / 4), (unsigned)B);
+  hipLaunchKernelGGL(augment_kernel, grid, dim3(64, 4), 0, stream, (const unsigned char*)img1,
+                     (const unsigned char*)img2, flow, params, sums, out1, out2, out_flow, valid, B, Hs, Ws, h, w);
+  return (int)hipGetLastError();
+}

@@ -303,6 +303,16 @@ int jr_forward_project(const float* flow, void* keys, float* out, int B, int h, 
 int jr_fb_check(const float* flow_fw, const float* flow_bw, const void* slot, long off_fw, long off_bw,
                 const float* thr, void* occ, float* err, int B, int H, int W, int H0, int W0, int top, int left,
                 hipStream_t stream);
+// Training-data augmentation (augment.hip; train/augment.py:augment_pairs, bitwise).  img1 / img2 uint8
+// [B][Hs][Ws][3], flow fp32 [B][Hs][Ws][2], params int32 [B][48] (the sampler's records), sums int32
+// [2][B][3].  jr_augment_sums clears sums (a memset in the stream) and adds up every frame's channels
+// (Hs * Ws * 255.5 must fit an int32); jr_augment reads them and writes out1 / out2 fp32 [B][h][w][3] in
+// [-1, 1], out_flow fp32 [B][h][w][2] and valid fp32 [B][h][w], all 16-byte aligned.  Source taps are
+// clamped into the frame whatever a record says.
+int jr_augment_sums(const void* img1, const void* img2, int B, int Hs, int Ws, int* sums, hipStream_t stream);
+int jr_augment(const void* img1, const void* img2, const float* flow, const int* params, const int* sums,
+               float* out1, float* out2, float* out_flow, float* valid, int B, int Hs, int Ws, int h, int w,
+               hipStream_t stream);
 // Conv of a 2-channel input (the flow branch's 7x7 / 3x3): x bf16 NHWC
 // [N][H][W][x_cstride] (channels 0, 1 used), stride 1, output H x W; w bf16
 // MFMA A fragments [cout/16][NKC][64 lanes][8] (jax_raft_amd/ops/native.py:

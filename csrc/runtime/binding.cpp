@@ -1722,6 +1722,70 @@ static Launch make_fb_check(const TList& t, const IList& i, std::vector<at::Tens
   };
 }
 
+// -------------------------------------------------------- training-data augmentation
+// (kernels augment.hip).  The frames as uploaded: img1 / img2 uint8 [B][Hs][Ws][3]; sums int32 [2][B][3].
+static void check_augment_frames(const at::Tensor& a, const at::Tensor& b, int64_t B, int64_t Hs, int64_t Ws, const char* op) {
+  TORCH_CHECK(B >= 1 && B <= 32767 && Hs >= 1 && Ws >= 1 && Hs * Ws * 255 + Hs * Ws / 2 <= INT32_MAX, op,
+              ": sizes (a frame's channel sum must fit an int32)");
+  for (const at::Tensor* v : {&a, &b})
+    TORCH_CHECK(v->defined() && v->is_cuda() && v->scalar_type() == at::kByte && v->is_contiguous() &&
+                    v->numel() == B * Hs * Ws * 3, op, ": images must be contiguous device uint8 [B][Hs][Ws][3]");
+}
+static void check_augment_sums(const at::Tensor& sums, int64_t B, const char* op) {
+  TORCH_CHECK(sums.defined() && sums.is_cuda() && sums.scalar_type() == at::kInt && sums.is_contiguous() &&
+                  sums.numel() == 6 * B, op, ": sums must be a contiguous device int32 [2][B][3]");
+}
+static bool augment_overlap(const at::Tensor& a, const at::Tensor& b) {
+  const char *a0 = (const char*)a.data_ptr(), *b0 = (const char*)b.data_ptr();
+  return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
+}
+// t = [img1, img2, sums], i = [B, Hs, Ws]
+static Launch make_augment_sums(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  at::Tensor a = opt(t, 0), b = opt(t, 1), sums = opt(t, 2);
+  const int64_t B = i[0], Hs = i[1], Ws = i[2];
+  check_augment_frames(a, b, B, Hs, Ws, "augment_sums");
+  check_augment_sums(sums, B, "augment_sums");
+  TORCH_CHECK(!augment_overlap(sums, a) && !augment_overlap(sums, b), "augment_sums: sums aliases an image");
+  keep.push_back(a); keep.push_back(b); keep.push_back(sums);
+  const void *ap = a.data_ptr(), *bp = b.data_ptr();
+  int* sp = sums.data_ptr<int>();
+  return [=](hipStream_t s, int) { return jr_augment_sums(ap, bp, (int)B, (int)Hs, (int)Ws, sp, s); };
+}
+// t = [img1, img2, flow (fp32 [B][Hs][Ws][2]), params (int32 [B][48]), sums, out1, out2 (fp32 [B][h][w][3]),
+// out_flow (fp32 [B][h][w][2]), valid (fp32 [B][h][w])], i = [B, Hs, Ws, h, w]
+static Launch make_augment(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  at::Tensor a = opt(t, 0), b = opt(t, 1), flow = opt(t, 2), params = opt(t, 3), sums = opt(t, 4);
+  at::Tensor o1 = opt(t, 5), o2 = opt(t, 6), of = opt(t, 7), ov = opt(t, 8);
+  const int64_t B = i[0], Hs = i[1], Ws = i[2], h = i[3], w = i[4];
+  check_augment_frames(a, b, B, Hs, Ws, "augment");
+  check_augment_sums(sums, B, "augment");
+  TORCH_CHECK(h >= 1 && w >= 1 && h <= 65535 * 4 && h * w <= 0x3fffffff, "augment: crop size");
+  check_f32(flow, "augment: flow");
+  TORCH_CHECK(flow.numel() == B * Hs * Ws * 2 && reinterpret_cast<uintptr_t>(flow.data_ptr()) % 16 == 0,
+              "augment: flow [B][Hs][Ws][2], 16-byte aligned");
+  TORCH_CHECK(params.defined() && params.is_cuda() && params.scalar_type() == at::kInt && params.is_contiguous() &&
+                  params.numel() == 48 * B, "augment: params must be a contiguous device int32 [B][48]");
+  const at::Tensor* outs[4] = {&o1, &o2, &of, &ov};
+  const int64_t ch[4] = {3, 3, 2, 1};
+  const char* names[4] = {"augment: image1 out", "augment: image2 out", "augment: flow out", "augment: valid out"};
+  for (int k = 0; k < 4; ++k) {
+    check_f32(*outs[k], names[k]);
+    TORCH_CHECK(outs[k]->numel() == B * h * w * ch[k] && reinterpret_cast<uintptr_t>(outs[k]->data_ptr()) % 16 == 0,
+                names[k], " must be [B][h][w][", ch[k], "], 16-byte aligned");
+    for (const at::Tensor* in : {&a, &b, &flow, &params, &sums})
+      TORCH_CHECK(!augment_overlap(*outs[k], *in), names[k], " aliases an input");
+    for (int j = 0; j < k; ++j) TORCH_CHECK(!augment_overlap(*outs[k], *outs[j]), names[k], " aliases another output");
+  }
+  for (auto& v : {a, b, flow, params, sums, o1, o2, of, ov}) keep.push_back(v);
+  const void *ap = a.data_ptr(), *bp = b.data_ptr();
+  const float* fp = flow.data_ptr<float>();
+  const int *pp = params.data_ptr<int>(), *sp = sums.data_ptr<int>();
+  float *p1 = o1.data_ptr<float>(), *p2 = o2.data_ptr<float>(), *pf = of.data_ptr<float>(), *pv = ov.data_ptr<float>();
+  return [=](hipStream_t s, int) {
+    return jr_augment(ap, bp, fp, pp, sp, p1, p2, pf, pv, (int)B, (int)Hs, (int)Ws, (int)h, (int)w, s);
+  };
+}
+
 // ------------------------------------------------------------- sequence loss
 // t = [pred (fp32 [N][P][2]), gt (fp32 [P][2]), valid? (fp32 [P]), part (fp32 [blocks][37])], i = [P, N]
 void seq_loss_op(const TList& t, IList i, double max_flow) {
@@ -1886,6 +1950,8 @@ static const std::vector<OpRow>& op_table() {
       row_ti("pack", 2, 2, make_pack),
       row_ti("wgrad", 16, 16, make_wgrad),
       row_ti("bn_table", 2, 2, make_bn_table),
+      row_ti("augment_sums", 3, 3, make_augment_sums),
+      row_ti("augment", 5, 5, make_augment),
       // fp32 parity mode
       row_tia("conv_f32", "alpha", 22, 22, make_conv_f32),
       row_ti("stats_f32", 3, 3, make_stats_f32),

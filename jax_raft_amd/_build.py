@@ -50,6 +50,7 @@ KERNEL_SOURCES = [
     CSRC / "kernels" / "conv_fam_grp.hip",
     CSRC / "kernels" / "warm.hip",
     CSRC / "kernels" / "fbcheck.hip",
+    CSRC / "kernels" / "augment.hip",
 ]
 HOST_SOURCES = [CSRC / "runtime" / "binding.cpp"]
 # every header of csrc/ is a dependency of every object (a missed header left stale objects in

@@ -630,6 +630,49 @@ def fb_check(flow_fw: torch.Tensor, flow_bw: torch.Tensor, alpha: float = 0.01, 
     return occ[0], occ[1]
 
 
+def augment_sums(img1_u8: torch.Tensor, img2_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Exact per-channel integer sums of two batches of (B, Hs, Ws, 3) uint8 GPU frames ->
+    int32 (2, B, 3) (launch 1 of :func:`augment_pairs`; the kernel clears ``out`` itself)."""
+    B, Hs, Ws, _ = img1_u8.shape
+    if out is None:
+        out = torch.empty((2, B, 3), dtype=torch.int32, device=img1_u8.device)
+    ops().augment_sums([img1_u8, img2_u8, out], [B, Hs, Ws])
+    return out
+
+
+def augment_pairs(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tensor, params,
+                  crop: Tuple[int, int]):
+    """RAFT's dense augmentation of a batch of frame pairs as they were uploaded ->
+    ``(image1, image2, flow, valid)`` at the crop size, the format the training step takes:
+    ``train/augment.py:augment_pairs`` -- that golden op itself on CPU tensors, the HIP kernels
+    (bitwise equal; two launches and the upload of the records, no host synchronisation) on
+    GPU tensors.  ``params``: the batch's :class:`~jax_raft_amd.train.augment.AugmentParams`,
+    validated here on the host before anything is uploaded or launched."""
+    from ..train import augment as A
+
+    if not img1_u8.is_cuda:
+        return A.augment_pairs(img1_u8, img2_u8, flow, params, crop)
+    if (img1_u8.ndim != 4 or img1_u8.shape[-1] != 3 or img1_u8.shape != img2_u8.shape
+            or img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8):
+        raise ValueError("augment_pairs: images must be (B, Hs, Ws, 3) uint8 of one size")
+    B, Hs, Ws, _ = img1_u8.shape
+    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, Hs, Ws, 2):
+        raise ValueError(f"augment_pairs: flow must be ({B}, {Hs}, {Ws}, 2) fp32, got {tuple(flow.shape)} {flow.dtype}")
+    if len(params) != B:
+        raise ValueError(f"augment_pairs: {len(params)} records for a batch of {B}")
+    h, w = int(crop[0]), int(crop[1])
+    params.validate((Hs, Ws), (h, w))
+    dev = img1_u8.device
+    rec = params.packed(pin=True).to(dev, non_blocking=True)
+    sums = augment_sums(img1_u8, img2_u8)
+    out1 = torch.empty((B, h, w, 3), dtype=torch.float32, device=dev)
+    out2 = torch.empty_like(out1)
+    oflow = torch.empty((B, h, w, 2), dtype=torch.float32, device=dev)
+    valid = torch.empty((B, h, w), dtype=torch.float32, device=dev)
+    ops().augment([img1_u8, img2_u8, flow, rec, sums, out1, out2, oflow, valid], [B, Hs, Ws, h, w])
+    return out1, out2, oflow, valid
+
+
 def conv2d(spec: ConvSpec, x: torch.Tensor, act: int = ACT_NONE, out_dtype=torch.bfloat16, alpha: float = 1.0,
            res: Optional[torch.Tensor] = None, res_post: int = 0, cfg: Optional[int] = None) -> torch.Tensor:
     """Eager NHWC conv of a contiguous bf16 tensor [N, H, W, C] (C == cin8)."""

@@ -1,0 +1,310 @@
+"""RAFT's dense flow augmentation as one gather: the golden op and its host-side sampler.
+
+``augment_pairs`` is this project's own definition of the dense ``FlowAugmentor`` of the
+original RAFT recipe (photometric jitter, an eraser occlusion on image 2, random scale and
+stretch, flips, a random crop), written as ONE gather over the uint8 source frames: every
+output pixel is computed from 4 source taps, nothing is resized or cropped in between.  The
+semantics are fixed here as a sequence of fp32 operations, each product and sum rounded on its
+own; ``csrc/kernels/augment.hip`` equals this op bit for bit (``ops/native.py:augment_pairs``
+runs this op on CPU tensors and the kernels on GPU tensors).
+
+Per sample the host draws one record (:class:`AugmentParams`): the resized size (Hr, Wr), the
+fp32 ratios Ws/Wr, Hs/Hr and their inverses, the crop origin (y0, x0) in the resized image, the
+flip flags, per image brightness b, contrast k, saturation s and a 3x3 hue matrix (the YIQ
+rotation, rounded to fp32), and up to two eraser rectangles in source pixels of image 2.  The
+host computes every ratio, reciprocal and matrix once: golden and kernel only add, multiply,
+compare, floor and divide by 255.
+
+Per output pixel (y, x) of sample n:
+
+1. u = x + x0, mirrored to Wr - 1 - u on an h-flip; src_x = (u + 0.5) * (Ws/Wr) - 0.5 clamped
+   to [0, Ws - 1]; x_lo = floor(src_x), x_hi = min(x_lo + 1, Ws - 1), wx = src_x - x_lo.  The
+   same in y.  Tap coordinates are clamped whatever the record says.
+2. Each of the 4 taps of each image is transformed as a texel (r, g, b) in [0, 255], clamped to
+   [0, 255] after every step: eraser (image 2: a tap whose integer source coordinate lies in a
+   rectangle becomes the image's mean colour, ``(sum + N // 2) // N`` per channel from the
+   exact integer sums), brightness ``c * b``, contrast ``(c - m) * k + m`` with
+   ``m = min(255, b * L)`` and L the luma of that image's mean colour, saturation
+   ``(c - g) * s + g`` with g the texel's own luma, hue ``M c``.  Luma is
+   ``(0.299 r + 0.587 g) + 0.114 b``; a matrix row is ``(M0 r + M1 g) + M2 b``.
+   A contrast or saturation factor of exactly 1 leaves the texel as it is (``(c - m) + m`` is
+   not c in fp32): that is what makes the identity record a plain crop.
+3. The image value is the bilinear blend ``top = t00 + wx (t01 - t00)``, ``bot`` alike,
+   ``top + wy (bot - top)``, then ``v / 255 * 2 - 1`` (``utils/flow_io.py:normalize_image``).
+4. The flow is the same blend of the 4 flow taps, times (Wr/Ws, Hr/Hs), negated on a flipped
+   axis; valid = 1 iff |fx| < 1000 and |fy| < 1000 (false for NaN), and the flow written where
+   valid = 0 is 0 (the sequence loss multiplies by the mask, and 0 * NaN would poison it).
+
+An identity record (Hr, Wr = Hs, Ws, no flips, factors 1, identity hue, no rectangles) is a
+plain crop plus normalisation: the ``augment=False`` path is this op with such records.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+# record layout (one sample: 16 int32 words + 32 fp32 words; csrc/kernels/augment.hip reads the same)
+N_INTS, N_FLOATS = 16, 32
+I_HR, I_WR, I_Y0, I_X0, I_HFLIP, I_VFLIP, I_NRECT, I_RECT = 0, 1, 2, 3, 4, 5, 6, 8   # rect: (x0, y0, x1, y1) x 2
+F_SX, F_SY, F_ISX, F_ISY, F_COL1, F_COL2 = 0, 1, 2, 3, 4, 16                         # colour: b, k, s, M[9]
+MAX_RESIZED = 1 << 16
+MAX_FLOW = 1000.0
+
+
+@dataclass(frozen=True)
+class Stage:
+    min_scale: float
+    max_scale: float
+    crop: Tuple[int, int]
+
+
+# RAFT's dense-augmentor presets per training stage
+STAGES = {
+    "chairs": Stage(-0.1, 1.0, (368, 496)),
+    "things": Stage(-0.4, 0.8, (400, 720)),
+    "sintel": Stage(-0.2, 0.6, (368, 768)),
+}
+
+_YIQ = np.array([[0.299, 0.587, 0.114], [0.596, -0.274, -0.322], [0.211, -0.523, 0.312]], dtype=np.float64)
+_YIQ_INV = np.linalg.inv(_YIQ)
+
+
+def hue_matrix(theta: float) -> np.ndarray:
+    """The RGB matrix of a rotation by ``theta`` radians in the IQ plane of YIQ, rounded to fp32."""
+    if theta == 0.0:
+        return np.eye(3, dtype=np.float32)
+    c, s = math.cos(theta), math.sin(theta)
+    rot = np.array([[1.0, 0.0, 0.0], [0.0, c, -s], [0.0, s, c]], dtype=np.float64)
+    return (_YIQ_INV @ rot @ _YIQ).astype(np.float32)
+
+
+def _colour_words(colour) -> np.ndarray:
+    b, k, s, theta = (1.0, 1.0, 1.0, 0.0) if colour is None else colour
+    return np.concatenate([np.array([b, k, s], dtype=np.float32), hue_matrix(float(theta)).reshape(9)])
+
+
+class AugmentParams:
+    """The records of one batch, on the host: ``ints`` (B, 16) int32 and ``floats`` (B, 32) fp32."""
+
+    def __init__(self, ints: np.ndarray, floats: np.ndarray):
+        self.ints = np.ascontiguousarray(ints, dtype=np.int32).reshape(-1, N_INTS)
+        self.floats = np.ascontiguousarray(floats, dtype=np.float32).reshape(-1, N_FLOATS)
+        if len(self.ints) != len(self.floats):
+            raise ValueError("AugmentParams: ints and floats of different batch sizes")
+
+    def __len__(self) -> int:
+        return len(self.ints)
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, AugmentParams) and np.array_equal(self.ints, other.ints)
+                and np.array_equal(self.floats.view(np.int32), other.floats.view(np.int32)))
+
+    # ------------------------------------------------------------ construction
+    @classmethod
+    def record(cls, src: Tuple[int, int], resized: Optional[Tuple[int, int]] = None, origin: Tuple[int, int] = (0, 0),
+               hflip: bool = False, vflip: bool = False, colour1=None, colour2=None,
+               rects: Sequence[Tuple[int, int, int, int]] = ()) -> "AugmentParams":
+        """One record.  ``colour``: (b, k, s, hue angle in radians) or None for none;
+        ``rects``: up to two (x0, y0, x1, y1), upper bounds exclusive, in source pixels."""
+        Hs, Ws = src
+        Hr, Wr = resized or src
+        if len(rects) > 2:
+            raise ValueError("AugmentParams: at most two eraser rectangles")
+        ints = np.zeros(N_INTS, dtype=np.int32)
+        ints[[I_HR, I_WR, I_Y0, I_X0, I_HFLIP, I_VFLIP, I_NRECT]] = [Hr, Wr, origin[0], origin[1], bool(hflip),
+                                                                    bool(vflip), len(rects)]
+        for j, r in enumerate(rects):
+            ints[I_RECT + 4 * j:I_RECT + 4 * j + 4] = r
+        floats = np.zeros(N_FLOATS, dtype=np.float32)
+        floats[[F_SX, F_SY, F_ISX, F_ISY]] = [Ws / Wr, Hs / Hr, Wr / Ws, Hr / Hs]
+        floats[F_COL1:F_COL1 + 12] = _colour_words(colour1)
+        floats[F_COL2:F_COL2 + 12] = _colour_words(colour2)
+        return cls(ints[None], floats[None])
+
+    @classmethod
+    def cat(cls, records: Sequence["AugmentParams"]) -> "AugmentParams":
+        return cls(np.concatenate([r.ints for r in records]), np.concatenate([r.floats for r in records]))
+
+    @classmethod
+    def identity(cls, batch: int, src: Tuple[int, int], origin: Tuple[int, int] = (0, 0)) -> "AugmentParams":
+        return cls.cat([cls.record(src, origin=origin)] * batch)
+
+    @classmethod
+    def sample(cls, batch: int, src: Tuple[int, int], stage: str = "chairs", crop: Optional[Tuple[int, int]] = None,
+               seed: int = 0, step: int = 0, rank: int = 0, augment: bool = True) -> "AugmentParams":
+        """``batch`` records drawn from RAFT's dense-augmentor distributions, a pure function of
+        (seed, step, rank, sample index).  ``augment=False``: identity records with a random crop."""
+        if stage not in STAGES:
+            raise ValueError(f"unknown augmentation stage {stage!r} (one of {sorted(STAGES)})")
+        st = STAGES[stage]
+        h, w = crop or st.crop
+        Hs, Ws = src
+        if Hs < h or Ws < w:
+            raise ValueError(f"source {Hs}x{Ws} is smaller than the crop {h}x{w}")
+        out = []
+        for n in range(batch):
+            g = np.random.default_rng([int(seed), int(step), int(rank), n])
+            sx = sy = 1.0
+            if augment and g.random() < 0.8:            # spatial augmentation
+                floor_ = max((h + 8) / Hs, (w + 8) / Ws)
+                sx = sy = 2.0 ** g.uniform(st.min_scale, st.max_scale)
+                if g.random() < 0.8:                    # stretch
+                    sx *= 2.0 ** g.uniform(-0.2, 0.2)
+                    sy *= 2.0 ** g.uniform(-0.2, 0.2)
+                sx, sy = max(sx, floor_), max(sy, floor_)
+            Hr, Wr = max(h, int(round(Hs * sy))), max(w, int(round(Ws * sx)))
+            hflip = bool(augment and g.random() < 0.5)
+            vflip = bool(augment and g.random() < 0.1)
+            y0, x0 = int(g.integers(0, Hr - h + 1)), int(g.integers(0, Wr - w + 1))
+            c1 = c2 = None
+            rects = []
+            if augment:
+                def colour():
+                    b, k, s = g.uniform(0.6, 1.4, 3)
+                    return float(b), float(k), float(s), 2.0 * math.pi * g.uniform(-0.5 / 3.14, 0.5 / 3.14)
+                c1 = colour()
+                c2 = colour() if g.random() < 0.2 else c1          # asymmetric
+                if g.random() < 0.5:                               # eraser
+                    for _ in range(int(g.integers(1, 3))):
+                        rx, ry = int(g.integers(0, Ws)), int(g.integers(0, Hs))
+                        dx, dy = int(g.integers(50, 101)), int(g.integers(50, 101))
+                        rects.append((rx, ry, rx + dx, ry + dy))
+            out.append(cls.record(src, (Hr, Wr), (y0, x0), hflip, vflip, c1, c2, rects))
+        return cls.cat(out)
+
+    # -------------------------------------------------------------- validation
+    def validate(self, src: Tuple[int, int], crop: Tuple[int, int]) -> None:
+        """Host-side check of every record before it is uploaded; ``ValueError`` on the first bad one."""
+        Hs, Ws = src
+        h, w = crop
+        if h < 1 or w < 1 or Hs < 1 or Ws < 1:
+            raise ValueError("augment: empty source or crop")
+        if Hs < h or Ws < w:
+            raise ValueError(f"augment: source {Hs}x{Ws} is smaller than the crop {h}x{w}")
+        i, f = self.ints.astype(np.int64), self.floats
+        Hr, Wr, y0, x0 = i[:, I_HR], i[:, I_WR], i[:, I_Y0], i[:, I_X0]
+        checks = (
+            ("the crop is larger than the resized size", (Hr < h) | (Wr < w)),
+            ("the resized size is out of range", (Hr > MAX_RESIZED) | (Wr > MAX_RESIZED)),
+            ("the crop origin lies outside the resized image", (y0 < 0) | (x0 < 0) | (y0 > Hr - h) | (x0 > Wr - w)),
+            ("flip flags must be 0 or 1", (i[:, I_HFLIP] & ~1 != 0) | (i[:, I_VFLIP] & ~1 != 0)),
+            ("0..2 eraser rectangles", (i[:, I_NRECT] < 0) | (i[:, I_NRECT] > 2)),
+            ("non-finite parameter", ~np.isfinite(f).all(axis=1)),
+            ("negative colour factor", (f[:, F_COL1:F_COL1 + 3] < 0).any(axis=1) | (f[:, F_COL2:F_COL2 + 3] < 0).any(axis=1)),
+            ("the ratios do not belong to the resized size",
+             (f[:, F_SX] != (Ws / Wr).astype(np.float32)) | (f[:, F_SY] != (Hs / Hr).astype(np.float32))
+             | (f[:, F_ISX] != (Wr / Ws).astype(np.float32)) | (f[:, F_ISY] != (Hr / Hs).astype(np.float32))),
+        )
+        for what, bad in checks:
+            if bad.any():
+                raise ValueError(f"augment: record {int(np.argmax(bad))}: {what}")
+
+    def packed(self, pin: bool = False) -> torch.Tensor:
+        """(B, 48) int32 words (the fp32 words bit-cast), the form the kernel reads."""
+        words = torch.from_numpy(np.concatenate([self.ints, self.floats.view(np.int32)], axis=1))
+        if pin:
+            buf = torch.empty(words.shape, dtype=torch.int32, pin_memory=True)
+            buf.copy_(words)
+            return buf
+        return words
+
+
+# ---------------------------------------------------------------------- golden
+def colour_sums(img_u8: torch.Tensor) -> torch.Tensor:
+    """Exact per-channel integer sums of (B, Hs, Ws, 3) uint8 frames -> (B, 3) int64."""
+    return img_u8.to(torch.int64).sum((1, 2))
+
+
+def _luma(r, g, b):
+    return (r * 0.299 + g * 0.587) + b * 0.114
+
+
+def _clamp(c):
+    return c.clamp(0.0, 255.0)
+
+
+def _texel(c, col, m):
+    """Brightness, contrast, saturation, hue of texels c = (r, g, b); col (B, 12) fp32, m (B,) fp32."""
+    v = lambda j: col[:, j].view(-1, 1, 1)
+    b_, k_, s_ = v(0), v(1), v(2)
+    m = m.view(-1, 1, 1)
+    c = [_clamp(x * b_) for x in c]
+    c = [_clamp(torch.where(k_ == 1.0, x, (x - m) * k_ + m)) for x in c]
+    g = _luma(*c)
+    c = [_clamp(torch.where(s_ == 1.0, x, (x - g) * s_ + g)) for x in c]
+    return [_clamp((c[0] * v(3 + 3 * j) + c[1] * v(4 + 3 * j)) + c[2] * v(5 + 3 * j)) for j in range(3)]
+
+
+def _blend(t00, t01, t10, t11, wx, wy):
+    top = t00 + wx * (t01 - t00)
+    bot = t10 + wx * (t11 - t10)
+    return top + wy * (bot - top)
+
+
+@torch.no_grad()
+def augment_pairs(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tensor, params: AugmentParams,
+                  crop: Tuple[int, int]):
+    """The golden op (module docstring): (B, Hs, Ws, 3) uint8 x 2, (B, Hs, Ws, 2) fp32 flow ->
+    image1, image2 (B, h, w, 3) fp32 in [-1, 1], flow (B, h, w, 2) fp32, valid (B, h, w) fp32."""
+    B, Hs, Ws, _ = img1_u8.shape
+    h, w = crop
+    if (img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8 or img1_u8.shape != img2_u8.shape
+            or img1_u8.shape[-1] != 3):
+        raise ValueError("augment_pairs: images must be (B, Hs, Ws, 3) uint8 of one size")
+    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, Hs, Ws, 2):
+        raise ValueError("augment_pairs: flow must be (B, Hs, Ws, 2) fp32")
+    if len(params) != B:
+        raise ValueError(f"augment_pairs: {len(params)} records for a batch of {B}")
+    params.validate((Hs, Ws), (h, w))
+    dev = img1_u8.device
+    pi = torch.from_numpy(params.ints).to(dev).long()
+    pf = torch.from_numpy(params.floats).to(dev)
+    icol = lambda j: pi[:, j].view(B, 1, 1)
+    fcol = lambda j: pf[:, j].view(B, 1, 1)
+
+    def axis(n, o, size_r, flip, ratio, size_s, shape):
+        u = torch.arange(n, device=dev).view(shape) + o
+        u = torch.where(flip != 0, size_r - 1 - u, u)
+        s = ((u.float() + 0.5) * ratio - 0.5).clamp(0.0, float(size_s - 1))
+        lo = s.floor()
+        wgt = s - lo
+        lo = lo.long().clamp(0, size_s - 1)
+        return lo, (lo + 1).clamp(max=size_s - 1), wgt
+
+    x_lo, x_hi, wx = axis(w, icol(I_X0), icol(I_WR), icol(I_HFLIP), fcol(F_SX), Ws, (1, 1, w))
+    y_lo, y_hi, wy = axis(h, icol(I_Y0), icol(I_HR), icol(I_VFLIP), fcol(F_SY), Hs, (1, h, 1))
+    bidx = torch.arange(B, device=dev).view(B, 1, 1)
+    taps = ((y_lo, x_lo), (y_lo, x_hi), (y_hi, x_lo), (y_hi, x_hi))
+    N = Hs * Ws
+
+    images = []
+    for k, img in enumerate((img1_u8, img2_u8)):
+        mean = ((colour_sums(img) + N // 2) // N).float()                    # (B, 3), integers 0..255
+        col = pf[:, (F_COL1, F_COL2)[k]:(F_COL1, F_COL2)[k] + 12]
+        m = (col[:, 0] * _luma(mean[:, 0], mean[:, 1], mean[:, 2])).clamp(max=255.0)
+        tex = []
+        for yi, xi in taps:
+            t = img[bidx, yi, xi].float()                                    # (B, h, w, 3)
+            if k == 1:
+                inside = torch.zeros((B, h, w), dtype=torch.bool, device=dev)
+                for j in range(2):
+                    r = [icol(I_RECT + 4 * j + q) for q in range(4)]
+                    inside |= (icol(I_NRECT) > j) & (xi >= r[0]) & (xi < r[2]) & (yi >= r[1]) & (yi < r[3])
+                t = torch.where(inside[..., None], mean.view(B, 1, 1, 3), t)
+            tex.append(_texel([t[..., 0], t[..., 1], t[..., 2]], col, m))
+        chans = [_blend(tex[0][c], tex[1][c], tex[2][c], tex[3][c], wx, wy) / 255.0 * 2.0 - 1.0 for c in range(3)]
+        images.append(torch.stack(chans, dim=-1).contiguous())
+
+    ft = [flow[bidx, yi, xi] for yi, xi in taps]
+    fx = _blend(*[t[..., 0] for t in ft], wx, wy) * fcol(F_ISX)
+    fy = _blend(*[t[..., 1] for t in ft], wx, wy) * fcol(F_ISY)
+    fx = torch.where(icol(I_HFLIP) != 0, -fx, fx)
+    fy = torch.where(icol(I_VFLIP) != 0, -fy, fy)
+    valid = (fx.abs() < MAX_FLOW) & (fy.abs() < MAX_FLOW)
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    out_flow = torch.stack([torch.where(valid, fx, zero), torch.where(valid, fy, zero)], dim=-1).contiguous()
+    return images[0], images[1], out_flow, valid.float()

@@ -9,6 +9,11 @@ Run (one process per GPU)::
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m jax_raft_amd.train.trainer \\
         --arch raft_large --steps 1000 --batch 6 --iters 12
 
+Without ``--data`` the batches are ``SyntheticFlow``.  ``--data <root> [--dataset chairs |
+sintel-clean | sintel-final] [--stage chairs | things | sintel] [--no-augment]`` trains on files:
+the raw frames are uploaded as they are and cropped + augmented in one gather on the device
+(train/datasets.py, train/augment.py); every batch is a pure function of (seed, step, rank).
+
 Checkpoints: ``<dir>/step_<n>.msgpack`` (Flax-format weights, loadable with
 ``raft_large(weights=...)``) + ``step_<n>.opt.pt`` (optimizer / scheduler
 state, tensors only) + ``latest.json``; ``--resume`` continues from latest.
@@ -62,6 +67,20 @@ class TrainConfig:
     # one ~2000-node graph), so off by default.
     graph_step: bool = False
     graph_warmup: int = 3          # eager steps before the capture (plan build, autotune, allocator warm-up)
+    # Real data (train/datasets.py, train/augment.py).  data=None: SyntheticFlow, as ever.
+    data: Optional[str] = None     # dataset root
+    dataset: str = "chairs"        # chairs | sintel-clean | sintel-final
+    stage: str = "chairs"          # augmentation preset (chairs | things | sintel); sets size when size is left at its default
+    augment: bool = True           # False: identity records, i.e. a random crop + normalisation only
+
+    def __post_init__(self):
+        if self.data is not None:
+            from .augment import STAGES
+
+            if self.stage not in STAGES:
+                raise ValueError(f"unknown stage {self.stage!r} (one of {sorted(STAGES)})")
+            if tuple(self.size) == tuple(type(self).__dataclass_fields__["size"].default):
+                self.size = STAGES[self.stage].crop
 
 
 def _adamw(params, cfg: TrainConfig, device, capturable: bool = False):
@@ -110,6 +129,14 @@ class Trainer:
             self.opt, cfg.lr, total_steps=cfg.steps + 100, pct_start=0.05, cycle_momentum=False,
             anneal_strategy="linear")
         self.data = SyntheticFlow(size=tuple(cfg.size), seed=cfg.seed, device=self.device)
+        self.loader = None
+        if cfg.data is not None:
+            from .datasets import FlowPairs, PairLoader
+
+            self.loader = PairLoader(FlowPairs.open(cfg.data, cfg.dataset), cfg.batch, seed=cfg.seed, rank=self.rank,
+                                     world=self.world, device=self.device)
+            if self.loader.frame[0] < cfg.size[0] or self.loader.frame[1] < cfg.size[1]:
+                raise ValueError(f"{cfg.data}: frames {self.loader.frame} are smaller than the crop {tuple(cfg.size)}")
         self.step = 0
         self.skipped = 0           # total dropped steps
         self._skip_run = 0         # consecutive dropped steps
@@ -247,6 +274,17 @@ class Trainer:
 
     def batch_for(self, step: int):
         cfg = self.cfg
+        if self.loader is not None:
+            # real data: the raw frames of this step, then crop + augmentation in one gather on the
+            # device (the golden op on a CPU device); records and indices are functions of the step
+            from ..ops import native as nat
+            from .augment import AugmentParams
+
+            img1, img2, flow = self.loader.fetch(step)
+            crop = (int(cfg.size[0]), int(cfg.size[1]))
+            params = AugmentParams.sample(cfg.batch, self.loader.frame, cfg.stage, crop, seed=cfg.seed, step=step,
+                                          rank=self.rank, augment=cfg.augment)
+            return nat.augment_pairs(img1, img2, flow, params, crop)
         base = (step * self.world + self.rank) * cfg.batch
         return self.data.batch(list(range(base, base + cfg.batch)))
 
