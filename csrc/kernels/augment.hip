@@ -10,16 +10,17 @@
 //      one integer atomic add per block and channel: order-independent, bitwise repeatable);
 //   2. the gather: grid (runs of a row, rows, samples) -- the sample's 48-word record is
 //      wave-uniform; one thread per 4 consecutive pixels of a row, 16-byte stores.
-#include "common.h"
+#include "augment_common.h"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-// record layout (train/augment.py)
-constexpr int REC_WORDS = 48, I_HR = 0, I_WR = 1, I_Y0 = 2, I_X0 = 3, I_HFLIP = 4, I_VFLIP = 5, I_NRECT = 6, I_RECT = 8;
-constexpr int F_BASE = 16, F_SX = 0, F_SY = 1, F_ISX = 2, F_ISY = 3, F_COL1 = 4, F_COL2 = 16;
+using namespace augment_dev;   // the record words, texel, blend, source_pos, image_pixel, store_run
+
+// record layout (train/augment.py:AugmentParams): 16 ints, then 32 floats
+constexpr int REC_WORDS = 48, F_BASE = 16;
 constexpr int SUM_PIX = 16;   // pixels per thread of the sums kernel
 
 // sums int32 [2][B][3] (image 1 frames, then image 2 frames); grid (blocks per frame, 2 * B)
@@ -50,55 +51,6 @@ __global__ __launch_bounds__(256) void augment_sums_kernel(const unsigned char* 
     const int c = threadIdx.x;
     atomicAdd(sums + n * 3 + c, (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]));
   }
-}
-
-struct Colour {
-  float b, k, s, m[9], mean[3], cm;   // cm: the contrast pivot min(255, b * luma(mean))
-};
-
-JR_DEVICE float clamp255(float v) { return fminf(fmaxf(v, 0.f), 255.f); }
-JR_DEVICE float luma(float r, float g, float b) { return (0.299f * r + 0.587f * g) + 0.114f * b; }
-
-JR_DEVICE Colour load_colour(const float* __restrict__ f, const int* __restrict__ sum, int npix) {
-  Colour c;
-  c.b = f[0]; c.k = f[1]; c.s = f[2];
-#pragma unroll
-  for (int j = 0; j < 9; ++j) c.m[j] = f[3 + j];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) c.mean[j] = (float)(((unsigned)sum[j] + (unsigned)(npix / 2)) / (unsigned)npix);
-  c.cm = fminf(c.b * luma(c.mean[0], c.mean[1], c.mean[2]), 255.f);
-  return c;
-}
-
-// brightness, contrast, saturation, hue of one texel, clamped to [0, 255] after every step
-JR_DEVICE void texel(float& r, float& g, float& b, const Colour& c) {
-  r = clamp255(r * c.b); g = clamp255(g * c.b); b = clamp255(b * c.b);
-  if (c.k != 1.f) {
-    r = clamp255((r - c.cm) * c.k + c.cm); g = clamp255((g - c.cm) * c.k + c.cm); b = clamp255((b - c.cm) * c.k + c.cm);
-  }
-  if (c.s != 1.f) {
-    const float l = luma(r, g, b);
-    r = clamp255((r - l) * c.s + l); g = clamp255((g - l) * c.s + l); b = clamp255((b - l) * c.s + l);
-  }
-  const float hr = clamp255((r * c.m[0] + g * c.m[1]) + b * c.m[2]);
-  const float hg = clamp255((r * c.m[3] + g * c.m[4]) + b * c.m[5]);
-  const float hb = clamp255((r * c.m[6] + g * c.m[7]) + b * c.m[8]);
-  r = hr; g = hg; b = hb;
-}
-
-JR_DEVICE float blend(float t00, float t01, float t10, float t11, float wx, float wy) {
-  const float top = t00 + wx * (t01 - t00);
-  const float bot = t10 + wx * (t11 - t10);
-  return top + wy * (bot - top);
-}
-
-// source position of resized coordinate u: taps lo / hi in [0, size - 1] and the weight of hi
-JR_DEVICE void source_pos(int u, float ratio, int size, int& lo, int& hi, float& wgt) {
-  const float s = fminf(fmaxf(((float)u + 0.5f) * ratio - 0.5f, 0.f), (float)(size - 1));
-  const float f = floorf(s);
-  wgt = s - f;
-  lo = min(max((int)f, 0), size - 1);   // clamped whatever the record says: never an out-of-bounds read
-  hi = min(lo + 1, size - 1);
 }
 
 // grid: (ceil(ceil(w / 4) / 64), ceil(h / 4), B), block (64, 4): thread = 4 pixels of one row
@@ -140,28 +92,12 @@ __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __res
     float wx;
     source_pos(u, sx, Ws, x_lo, x_hi, wx);
     const int ty[4] = {y_lo, y_lo, y_hi, y_hi}, tx[4] = {x_lo, x_hi, x_lo, x_hi};
-    float t1[4][3], t2[4][3], tf[4][2];
+    image_pixel(p1, p2, Ws, ty, tx, wx, wy, rec, nrect, c1, c2, a1 + 3 * k, a2 + 3 * k);
+    float tf[4][2];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const long o = (long)ty[q] * Ws + tx[q];
-      t1[q][0] = (float)p1[o * 3]; t1[q][1] = (float)p1[o * 3 + 1]; t1[q][2] = (float)p1[o * 3 + 2];
-      texel(t1[q][0], t1[q][1], t1[q][2], c1);
-      bool erased = false;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        erased |= j < nrect && tx[q] >= rec[I_RECT + 4 * j] && tx[q] < rec[I_RECT + 4 * j + 2] &&
-                  ty[q] >= rec[I_RECT + 4 * j + 1] && ty[q] < rec[I_RECT + 4 * j + 3];
-      t2[q][0] = erased ? c2.mean[0] : (float)p2[o * 3];
-      t2[q][1] = erased ? c2.mean[1] : (float)p2[o * 3 + 1];
-      t2[q][2] = erased ? c2.mean[2] : (float)p2[o * 3 + 2];
-      texel(t2[q][0], t2[q][1], t2[q][2], c2);
-      const float2 f = *(const float2*)(pf + o * 2);
+      const float2 f = *(const float2*)(pf + ((long)ty[q] * Ws + tx[q]) * 2);
       tf[q][0] = f.x; tf[q][1] = f.y;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      a1[3 * k + c] = blend(t1[0][c], t1[1][c], t1[2][c], t1[3][c], wx, wy) / 255.0f * 2.0f - 1.0f;
-      a2[3 * k + c] = blend(t2[0][c], t2[1][c], t2[2][c], t2[3][c], wx, wy) / 255.0f * 2.0f - 1.0f;
     }
     float fx = blend(tf[0][0], tf[1][0], tf[2][0], tf[3][0], wx, wy) * isx;
     float fy = blend(tf[0][1], tf[1][1], tf[2][1], tf[3][1], wx, wy) * isy;
@@ -174,26 +110,7 @@ __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __res
   }
 
   const long px = ((long)n * h + y) * w + x4;   // first output pixel of the run
-  if ((w & 3) == 0) {                           // every run starts at a multiple of 4 pixels: 16-byte stores
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      *(float4*)(o1 + px * 3 + 4 * j) = make_float4(a1[4 * j], a1[4 * j + 1], a1[4 * j + 2], a1[4 * j + 3]);
-      *(float4*)(o2 + px * 3 + 4 * j) = make_float4(a2[4 * j], a2[4 * j + 1], a2[4 * j + 2], a2[4 * j + 3]);
-    }
-    *(float4*)(oflow + px * 2) = make_float4(fl[0], fl[1], fl[2], fl[3]);
-    *(float4*)(oflow + px * 2 + 4) = make_float4(fl[4], fl[5], fl[6], fl[7]);
-    *(float4*)(ovalid + px) = make_float4(va[0], va[1], va[2], va[3]);
-  } else {                                      // rows start at any pixel: scalar stores, the tail cut off
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (x4 + k < w) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { o1[(px + k) * 3 + c] = a1[3 * k + c]; o2[(px + k) * 3 + c] = a2[3 * k + c]; }
-        oflow[(px + k) * 2] = fl[2 * k];
-        oflow[(px + k) * 2 + 1] = fl[2 * k + 1];
-        ovalid[px + k] = va[k];
-      }
-  }
+  store_run(o1, o2, oflow, ovalid, px, x4, w, a1, a2, fl, va);
 }
 
 }  // namespace

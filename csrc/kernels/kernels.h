@@ -313,6 +313,16 @@ int jr_augment_sums(const void* img1, const void* img2, int B, int Hs, int Ws, i
 int jr_augment(const void* img1, const void* img2, const float* flow, const int* params, const int* sums,
                float* out1, float* out2, float* out_flow, float* valid, int B, int Hs, int Ws, int h, int w,
                hipStream_t stream);
+// The sparse-ground-truth augmentation (augment_sparse.hip; train/augment.py:augment_pairs_sparse,
+// bitwise).  Every sample sits in the top-left corner of a [Hb][Wb] buffer: img1 / img2 uint8
+// [B][Hb][Wb][3], flow fp32 [B][Hb][Wb][2], valid_in uint8 [B][Hb][Wb], params int32 [B][52] (the dense
+// record plus the sample's own size, which the kernels clamp into the buffer), sums int32 [2][B][3] over
+// each sample's own region.  Outputs as jr_augment's.  Nothing outside a sample's region is read.
+int jr_augment_sparse_sums(const void* img1, const void* img2, const int* params, int B, int Hb, int Wb, int* sums,
+                           hipStream_t stream);
+int jr_augment_sparse(const void* img1, const void* img2, const float* flow, const void* valid_in, const int* params,
+                      const int* sums, float* out1, float* out2, float* out_flow, float* valid, int B, int Hb, int Wb,
+                      int h, int w, hipStream_t stream);
 // Conv of a 2-channel input (the flow branch's 7x7 / 3x3): x bf16 NHWC
 // [N][H][W][x_cstride] (channels 0, 1 used), stride 1, output H x W; w bf16
 // MFMA A fragments [cout/16][NKC][64 lanes][8] (jax_raft_amd/ops/native.py:

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <functional>
 #include <string>
 #include <vector>
@@ -1739,6 +1740,20 @@ static bool augment_overlap(const at::Tensor& a, const at::Tensor& b) {
   const char *a0 = (const char*)a.data_ptr(), *b0 = (const char*)b.data_ptr();
   return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
 }
+// the four outputs of a gather: fp32 [B][h][w][3 | 3 | 2 | 1], 16-byte aligned, aliasing no input and no other output
+static void check_augment_outputs(const std::string& op, std::array<const at::Tensor*, 4> outs,
+                                  std::initializer_list<const at::Tensor*> ins, int64_t B, int64_t h, int64_t w) {
+  const int64_t ch[4] = {3, 3, 2, 1};
+  const char* what[4] = {": image1 out", ": image2 out", ": flow out", ": valid out"};
+  for (int k = 0; k < 4; ++k) {
+    const std::string name = op + what[k];
+    check_f32(*outs[k], name.c_str());
+    TORCH_CHECK(outs[k]->numel() == B * h * w * ch[k] && reinterpret_cast<uintptr_t>(outs[k]->data_ptr()) % 16 == 0,
+                name, " must be [B][h][w][", ch[k], "], 16-byte aligned");
+    for (const at::Tensor* in : ins) TORCH_CHECK(!augment_overlap(*outs[k], *in), name, " aliases an input");
+    for (int j = 0; j < k; ++j) TORCH_CHECK(!augment_overlap(*outs[k], *outs[j]), name, " aliases another output");
+  }
+}
 // t = [img1, img2, sums], i = [B, Hs, Ws]
 static Launch make_augment_sums(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   at::Tensor a = opt(t, 0), b = opt(t, 1), sums = opt(t, 2);
@@ -1765,17 +1780,7 @@ static Launch make_augment(const TList& t, const IList& i, std::vector<at::Tenso
               "augment: flow [B][Hs][Ws][2], 16-byte aligned");
   TORCH_CHECK(params.defined() && params.is_cuda() && params.scalar_type() == at::kInt && params.is_contiguous() &&
                   params.numel() == 48 * B, "augment: params must be a contiguous device int32 [B][48]");
-  const at::Tensor* outs[4] = {&o1, &o2, &of, &ov};
-  const int64_t ch[4] = {3, 3, 2, 1};
-  const char* names[4] = {"augment: image1 out", "augment: image2 out", "augment: flow out", "augment: valid out"};
-  for (int k = 0; k < 4; ++k) {
-    check_f32(*outs[k], names[k]);
-    TORCH_CHECK(outs[k]->numel() == B * h * w * ch[k] && reinterpret_cast<uintptr_t>(outs[k]->data_ptr()) % 16 == 0,
-                names[k], " must be [B][h][w][", ch[k], "], 16-byte aligned");
-    for (const at::Tensor* in : {&a, &b, &flow, &params, &sums})
-      TORCH_CHECK(!augment_overlap(*outs[k], *in), names[k], " aliases an input");
-    for (int j = 0; j < k; ++j) TORCH_CHECK(!augment_overlap(*outs[k], *outs[j]), names[k], " aliases another output");
-  }
+  check_augment_outputs("augment", {&o1, &o2, &of, &ov}, {&a, &b, &flow, &params, &sums}, B, h, w);
   for (auto& v : {a, b, flow, params, sums, o1, o2, of, ov}) keep.push_back(v);
   const void *ap = a.data_ptr(), *bp = b.data_ptr();
   const float* fp = flow.data_ptr<float>();
@@ -1783,6 +1788,52 @@ static Launch make_augment(const TList& t, const IList& i, std::vector<at::Tenso
   float *p1 = o1.data_ptr<float>(), *p2 = o2.data_ptr<float>(), *pf = of.data_ptr<float>(), *pv = ov.data_ptr<float>();
   return [=](hipStream_t s, int) {
     return jr_augment(ap, bp, fp, pp, sp, p1, p2, pf, pv, (int)B, (int)Hs, (int)Ws, (int)h, (int)w, s);
+  };
+}
+
+// ---- sparse ground truth (kernels augment_sparse.hip): samples of several sizes in [Hb][Wb] buffers
+static void check_augment_records(const at::Tensor& params, int64_t B, int64_t words, const std::string& op) {
+  TORCH_CHECK(params.defined() && params.is_cuda() && params.scalar_type() == at::kInt && params.is_contiguous() &&
+                  params.numel() == words * B, op, ": params must be a contiguous device int32 [B][", words, "]");
+}
+// t = [img1, img2, params (int32 [B][52]), sums], i = [B, Hb, Wb]
+static Launch make_augment_sparse_sums(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  at::Tensor a = opt(t, 0), b = opt(t, 1), params = opt(t, 2), sums = opt(t, 3);
+  const int64_t B = i[0], Hb = i[1], Wb = i[2];
+  check_augment_frames(a, b, B, Hb, Wb, "augment_sparse_sums");
+  check_augment_records(params, B, 52, "augment_sparse_sums");
+  check_augment_sums(sums, B, "augment_sparse_sums");
+  for (const at::Tensor* in : {&a, &b, &params})
+    TORCH_CHECK(!augment_overlap(sums, *in), "augment_sparse_sums: sums aliases an input");
+  for (auto& v : {a, b, params, sums}) keep.push_back(v);
+  const void *ap = a.data_ptr(), *bp = b.data_ptr();
+  const int* pp = params.data_ptr<int>();
+  int* sp = sums.data_ptr<int>();
+  return [=](hipStream_t s, int) { return jr_augment_sparse_sums(ap, bp, pp, (int)B, (int)Hb, (int)Wb, sp, s); };
+}
+// t = [img1, img2, flow (fp32 [B][Hb][Wb][2]), valid (uint8 [B][Hb][Wb]), params (int32 [B][52]), sums, out1, out2
+// (fp32 [B][h][w][3]), out_flow (fp32 [B][h][w][2]), out_valid (fp32 [B][h][w])], i = [B, Hb, Wb, h, w]
+static Launch make_augment_sparse(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  at::Tensor a = opt(t, 0), b = opt(t, 1), flow = opt(t, 2), vin = opt(t, 3), params = opt(t, 4), sums = opt(t, 5);
+  at::Tensor o1 = opt(t, 6), o2 = opt(t, 7), of = opt(t, 8), ov = opt(t, 9);
+  const int64_t B = i[0], Hb = i[1], Wb = i[2], h = i[3], w = i[4];
+  check_augment_frames(a, b, B, Hb, Wb, "augment_sparse");
+  check_augment_sums(sums, B, "augment_sparse");
+  TORCH_CHECK(h >= 1 && w >= 1 && h <= 65535 * 4 && h * w <= 0x3fffffff, "augment_sparse: crop size");
+  check_f32(flow, "augment_sparse: flow");
+  TORCH_CHECK(flow.numel() == B * Hb * Wb * 2 && reinterpret_cast<uintptr_t>(flow.data_ptr()) % 16 == 0,
+              "augment_sparse: flow [B][Hb][Wb][2], 16-byte aligned");
+  TORCH_CHECK(vin.defined() && vin.is_cuda() && vin.scalar_type() == at::kByte && vin.is_contiguous() &&
+                  vin.numel() == B * Hb * Wb, "augment_sparse: valid must be a contiguous device uint8 [B][Hb][Wb]");
+  check_augment_records(params, B, 52, "augment_sparse");
+  check_augment_outputs("augment_sparse", {&o1, &o2, &of, &ov}, {&a, &b, &flow, &vin, &params, &sums}, B, h, w);
+  for (auto& v : {a, b, flow, vin, params, sums, o1, o2, of, ov}) keep.push_back(v);
+  const void *ap = a.data_ptr(), *bp = b.data_ptr(), *vp = vin.data_ptr();
+  const float* fp = flow.data_ptr<float>();
+  const int *pp = params.data_ptr<int>(), *sp = sums.data_ptr<int>();
+  float *p1 = o1.data_ptr<float>(), *p2 = o2.data_ptr<float>(), *pf = of.data_ptr<float>(), *pv = ov.data_ptr<float>();
+  return [=](hipStream_t s, int) {
+    return jr_augment_sparse(ap, bp, fp, vp, pp, sp, p1, p2, pf, pv, (int)B, (int)Hb, (int)Wb, (int)h, (int)w, s);
   };
 }
 
@@ -1952,6 +2003,8 @@ static const std::vector<OpRow>& op_table() {
       row_ti("bn_table", 2, 2, make_bn_table),
       row_ti("augment_sums", 3, 3, make_augment_sums),
       row_ti("augment", 5, 5, make_augment),
+      row_ti("augment_sparse_sums", 3, 3, make_augment_sparse_sums),
+      row_ti("augment_sparse", 5, 5, make_augment_sparse),
       // fp32 parity mode
       row_tia("conv_f32", "alpha", 22, 22, make_conv_f32),
       row_ti("stats_f32", 3, 3, make_stats_f32),

@@ -51,8 +51,9 @@ KERNEL_SOURCES = [
     CSRC / "kernels" / "warm.hip",
     CSRC / "kernels" / "fbcheck.hip",
     CSRC / "kernels" / "augment.hip",
+    CSRC / "kernels" / "augment_sparse.hip",
 ]
-HOST_SOURCES = [CSRC / "runtime" / "binding.cpp"]
+HOST_SOURCES = [CSRC / "runtime" / "binding.cpp", CSRC / "runtime" / "png.cpp"]
 # every header of csrc/ is a dependency of every object (a missed header left stale objects in
 # _C.so before: conv1x1.h, round 3); the set is small, so a rebuild on any header edit is cheap
 HEADERS = sorted(CSRC.rglob("*.h"))

@@ -1,7 +1,8 @@
 """Console entry points (reference CLIs: scripts/convert_checkpoint.py:59-68,
 scripts/validate_sintel.py:250-263).  ``scripts/*.py`` are thin wrappers so the
 repository works uninstalled; ``pip install .`` exposes the same functions as
-``jax-raft-amd-convert`` / ``jax-raft-amd-validate``."""
+``jax-raft-amd-convert`` / ``jax-raft-amd-validate``; ``validate_kitti_main`` is
+``scripts/validate_kitti.py``."""
 from __future__ import annotations
 
 import argparse
@@ -62,6 +63,41 @@ def validate_main(argv: Optional[Sequence[str]] = None) -> int:
         out[name] = validate_sintel(model, args.data_root, iters=args.iters, device=device, max_pairs=args.max_pairs,
                                     batch_size=args.batch_size,
                                     **({} if device.type == "cpu" else dict(precision=args.precision)))
+    if args.json and (world == 1 or torch.distributed.get_rank() == 0):
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+    if world > 1:
+        torch.distributed.destroy_process_group()
+    return 0
+
+
+def validate_kitti_main(argv: Optional[Sequence[str]] = None) -> int:
+    """KITTI-2015 (train split) EPE / F1-all of raft_large or raft_small, data-parallel over RCCL
+    when launched by torchrun."""
+    import torch
+
+    from . import raft_large, raft_small
+    from .eval.kitti import validate_kitti
+
+    ap = argparse.ArgumentParser(prog="validate_kitti")
+    ap.add_argument("data_root")
+    ap.add_argument("--model", choices=["raft_large", "raft_small"], default="raft_large")
+    ap.add_argument("--weights", default=None, help="Flax msgpack checkpoint (default: pretrained release file)")
+    ap.add_argument("--iters", type=int, default=24)
+    ap.add_argument("--max-pairs", type=int, default=None)
+    ap.add_argument("--cpu", action="store_true")
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args(argv)
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1:
+        from .parallel.dp import init_distributed
+
+        init_distributed("gloo" if args.cpu else None)
+    device = (torch.device("cpu") if args.cpu or not torch.cuda.is_available()
+              else torch.device("cuda", torch.cuda.current_device()))
+    factory = raft_large if args.model == "raft_large" else raft_small
+    model, _ = factory(weights=args.weights) if args.weights else factory(pretrained=True)
+    out = {args.model: validate_kitti(model, args.data_root, iters=args.iters, device=device, max_pairs=args.max_pairs)}
     if args.json and (world == 1 or torch.distributed.get_rank() == 0):
         with open(args.json, "w") as f:
             json.dump(out, f, indent=1)

@@ -673,6 +673,53 @@ def augment_pairs(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tens
     return out1, out2, oflow, valid
 
 
+def augment_sums_sparse(img1_u8: torch.Tensor, img2_u8: torch.Tensor, rec: torch.Tensor,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Exact per-channel integer sums of each sample's own region of two batches of (B, Hb, Wb, 3)
+    uint8 GPU buffers -> int32 (2, B, 3); ``rec``: the packed sparse records on the device."""
+    B, Hb, Wb, _ = img1_u8.shape
+    if out is None:
+        out = torch.empty((2, B, 3), dtype=torch.int32, device=img1_u8.device)
+    ops().augment_sparse_sums([img1_u8, img2_u8, rec, out], [B, Hb, Wb])
+    return out
+
+
+def augment_pairs_sparse(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tensor, valid_u8: torch.Tensor,
+                         params, crop: Tuple[int, int]):
+    """RAFT's sparse augmentation (KITTI / HD1K) of a batch of samples of several sizes, each in
+    the top-left corner of its (Hb, Wb) buffer -> ``(image1, image2, flow, valid)`` at the crop
+    size: ``train/augment.py:augment_pairs_sparse`` itself on CPU tensors, the HIP kernels of
+    ``augment_sparse.hip`` (bitwise equal; two launches and the upload of the records, no host
+    synchronisation) on GPU tensors.  ``params``: the batch's
+    :class:`~jax_raft_amd.train.augment.SparseAugmentParams`, validated here on the host before
+    anything is uploaded or launched."""
+    from ..train import augment as A
+
+    if not img1_u8.is_cuda:
+        return A.augment_pairs_sparse(img1_u8, img2_u8, flow, valid_u8, params, crop)
+    if (img1_u8.ndim != 4 or img1_u8.shape[-1] != 3 or img1_u8.shape != img2_u8.shape
+            or img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8):
+        raise ValueError("augment_pairs_sparse: images must be (B, Hb, Wb, 3) uint8 of one size")
+    B, Hb, Wb, _ = img1_u8.shape
+    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, Hb, Wb, 2):
+        raise ValueError(f"augment_pairs_sparse: flow must be ({B}, {Hb}, {Wb}, 2) fp32, got {tuple(flow.shape)} {flow.dtype}")
+    if valid_u8.dtype != torch.uint8 or tuple(valid_u8.shape) != (B, Hb, Wb):
+        raise ValueError(f"augment_pairs_sparse: valid must be ({B}, {Hb}, {Wb}) uint8, got {tuple(valid_u8.shape)} {valid_u8.dtype}")
+    if not isinstance(params, A.SparseAugmentParams) or len(params) != B:
+        raise ValueError(f"augment_pairs_sparse: SparseAugmentParams for a batch of {B} wanted")
+    h, w = int(crop[0]), int(crop[1])
+    params.validate((Hb, Wb), (h, w))
+    dev = img1_u8.device
+    rec = params.packed(pin=True).to(dev, non_blocking=True)
+    sums = augment_sums_sparse(img1_u8, img2_u8, rec)
+    out1 = torch.empty((B, h, w, 3), dtype=torch.float32, device=dev)
+    out2 = torch.empty_like(out1)
+    oflow = torch.empty((B, h, w, 2), dtype=torch.float32, device=dev)
+    valid = torch.empty((B, h, w), dtype=torch.float32, device=dev)
+    ops().augment_sparse([img1_u8, img2_u8, flow, valid_u8, rec, sums, out1, out2, oflow, valid], [B, Hb, Wb, h, w])
+    return out1, out2, oflow, valid
+
+
 def conv2d(spec: ConvSpec, x: torch.Tensor, act: int = ACT_NONE, out_dtype=torch.bfloat16, alpha: float = 1.0,
            res: Optional[torch.Tensor] = None, res_post: int = 0, cfg: Optional[int] = None) -> torch.Tensor:
     """Eager NHWC conv of a contiguous bf16 tensor [N, H, W, C] (C == cin8)."""

@@ -1,6 +1,7 @@
 """Training: the fused native step, the sequence loss, data (synthetic, and real datasets with
 the fused GPU augmentation) and the data-parallel trainer."""
-from .augment import AugmentParams, augment_pairs
-from .datasets import FlowPairs, PairLoader
+from .augment import AugmentParams, SparseAugmentParams, augment_pairs, augment_pairs_sparse, sample_sparse
+from .datasets import FlowPairs, PairLoader, SparseFlowPairs
 
-__all__ = ("augment_pairs", "AugmentParams", "FlowPairs", "PairLoader")
+__all__ = ("augment_pairs", "AugmentParams", "FlowPairs", "PairLoader", "augment_pairs_sparse", "SparseAugmentParams",
+           "sample_sparse", "SparseFlowPairs")

@@ -37,6 +37,10 @@ Per output pixel (y, x) of sample n:
 
 An identity record (Hr, Wr = Hs, Ws, no flips, factors 1, identity hue, no rectangles) is a
 plain crop plus normalisation: the ``augment=False`` path is this op with such records.
+
+Sparse ground truth (KITTI, HD1K) has an op of its own, :func:`augment_pairs_sparse`, with records
+that also carry each sample's size (:class:`SparseAugmentParams`, :func:`sample_sparse`): the
+images as above, the flow moved point by point (its docstring; ``csrc/kernels/augment_sparse.hip``).
 """
 from __future__ import annotations
 
@@ -245,24 +249,19 @@ def _blend(t00, t01, t10, t11, wx, wy):
     return top + wy * (bot - top)
 
 
-@torch.no_grad()
-def augment_pairs(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tensor, params: AugmentParams,
-                  crop: Tuple[int, int]):
-    """The golden op (module docstring): (B, Hs, Ws, 3) uint8 x 2, (B, Hs, Ws, 2) fp32 flow ->
-    image1, image2 (B, h, w, 3) fp32 in [-1, 1], flow (B, h, w, 2) fp32, valid (B, h, w) fp32."""
-    B, Hs, Ws, _ = img1_u8.shape
-    h, w = crop
-    if (img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8 or img1_u8.shape != img2_u8.shape
-            or img1_u8.shape[-1] != 3):
-        raise ValueError("augment_pairs: images must be (B, Hs, Ws, 3) uint8 of one size")
-    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, Hs, Ws, 2):
-        raise ValueError("augment_pairs: flow must be (B, Hs, Ws, 2) fp32")
-    if len(params) != B:
-        raise ValueError(f"augment_pairs: {len(params)} records for a batch of {B}")
-    params.validate((Hs, Ws), (h, w))
-    dev = img1_u8.device
+def _records_on(params, dev):
+    """The records as device tensors and accessors of one int / float word as (B, 1, 1)."""
+    B = len(params)
     pi = torch.from_numpy(params.ints).to(dev).long()
     pf = torch.from_numpy(params.floats).to(dev)
+    return pi, pf, (lambda j: pi[:, j].view(B, 1, 1)), (lambda j: pf[:, j].view(B, 1, 1))
+
+
+def _gather_images(img1_u8, img2_u8, pi, pf, h, w):
+    """Steps 1-3 of the module docstring on (B, Hs, Ws, 3) frames that ARE the samples (no padding):
+    (image1, image2), and the taps and weights for a caller that blends more."""
+    B, Hs, Ws, _ = img1_u8.shape
+    dev = img1_u8.device
     icol = lambda j: pi[:, j].view(B, 1, 1)
     fcol = lambda j: pf[:, j].view(B, 1, 1)
 
@@ -298,6 +297,27 @@ def augment_pairs(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tens
             tex.append(_texel([t[..., 0], t[..., 1], t[..., 2]], col, m))
         chans = [_blend(tex[0][c], tex[1][c], tex[2][c], tex[3][c], wx, wy) / 255.0 * 2.0 - 1.0 for c in range(3)]
         images.append(torch.stack(chans, dim=-1).contiguous())
+    return images[0], images[1], bidx, taps, wx, wy
+
+
+@torch.no_grad()
+def augment_pairs(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tensor, params: AugmentParams,
+                  crop: Tuple[int, int]):
+    """The golden op (module docstring): (B, Hs, Ws, 3) uint8 x 2, (B, Hs, Ws, 2) fp32 flow ->
+    image1, image2 (B, h, w, 3) fp32 in [-1, 1], flow (B, h, w, 2) fp32, valid (B, h, w) fp32."""
+    B, Hs, Ws, _ = img1_u8.shape
+    h, w = crop
+    if (img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8 or img1_u8.shape != img2_u8.shape
+            or img1_u8.shape[-1] != 3):
+        raise ValueError("augment_pairs: images must be (B, Hs, Ws, 3) uint8 of one size")
+    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, Hs, Ws, 2):
+        raise ValueError("augment_pairs: flow must be (B, Hs, Ws, 2) fp32")
+    if len(params) != B:
+        raise ValueError(f"augment_pairs: {len(params)} records for a batch of {B}")
+    params.validate((Hs, Ws), (h, w))
+    dev = img1_u8.device
+    pi, pf, icol, fcol = _records_on(params, dev)
+    image1, image2, bidx, taps, wx, wy = _gather_images(img1_u8, img2_u8, pi, pf, h, w)
 
     ft = [flow[bidx, yi, xi] for yi, xi in taps]
     fx = _blend(*[t[..., 0] for t in ft], wx, wy) * fcol(F_ISX)
@@ -307,4 +327,213 @@ def augment_pairs(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tens
     valid = (fx.abs() < MAX_FLOW) & (fy.abs() < MAX_FLOW)
     zero = torch.zeros((), dtype=torch.float32, device=dev)
     out_flow = torch.stack([torch.where(valid, fx, zero), torch.where(valid, fy, zero)], dim=-1).contiguous()
-    return images[0], images[1], out_flow, valid.float()
+    return image1, image2, out_flow, valid.float()
+
+
+# ------------------------------------------------------- sparse ground truth
+# RAFT's ``SparseFlowAugmentor`` (KITTI, HD1K).  The samples of a batch have sizes of their own
+# and sit in the top-left corners of (B, Hb, Wb, ...) buffers.
+# record layout (one sample: 20 int32 words + 32 fp32 words; csrc/kernels/augment_sparse.hip reads
+# the same): words 0..15 of the ints and all floats are the dense record's, then the sample's size
+N_INTS_SPARSE = 20
+I_HS, I_WS = 16, 17
+MAX_RATIO = 4.0        # Ws / Wr, Hs / Hr at most: bounds the kernel's scan
+MAX_SCAN = 16          # candidates per axis the kernel scans at most (a valid record needs sx + 5 <= 9)
+
+# RAFT's sparse-augmentor presets: ``kitti`` is the fine-tuning stage of its own, ``sintel`` what
+# KITTI / HD1K get inside the Sintel stage (no stretch in either)
+SPARSE_STAGES = {
+    "kitti": Stage(-0.2, 0.4, (288, 960)),
+    "sintel": Stage(-0.3, 0.5, (368, 768)),
+}
+_SPARSE_HFLIP = {"kitti": 0.0, "sintel": 0.5}
+
+
+def scan_window(T, ratio, size: int):
+    """The source indices ``lo .. hi`` the kernel scans for landers on target ``T`` (an int or an
+    array), the formula of ``augment_sparse.hip:scan_window`` in fp32: ``floor((T - 0.5) * ratio)
+    - 1 .. ceil((T + 0.5) * ratio) + 1`` clamped to ``[0, size - 1]``.  ``fp32(s) * inv`` is
+    monotone in s and ``rint(.) == T`` needs it within 0.5 of T up to rounding, far inside the
+    margin of 1."""
+    T = np.asarray(T, dtype=np.float32)
+    ratio = np.float32(ratio)
+    lo = np.maximum(np.floor((T - np.float32(0.5)) * ratio).astype(np.int64) - 1, 0)
+    hi = np.minimum(np.ceil((T + np.float32(0.5)) * ratio).astype(np.int64) + 1, size - 1)
+    return np.maximum(lo, hi - (MAX_SCAN - 1)), hi
+
+
+class SparseAugmentParams(AugmentParams):
+    """The records of one batch of samples with sizes of their own: ``ints`` (B, 20) int32 -- the
+    dense record's 16 words, then (Hs, Ws) -- and ``floats`` (B, 32) fp32 as in the dense record."""
+
+    def __init__(self, ints: np.ndarray, floats: np.ndarray):
+        self.ints = np.ascontiguousarray(ints, dtype=np.int32).reshape(-1, N_INTS_SPARSE)
+        self.floats = np.ascontiguousarray(floats, dtype=np.float32).reshape(-1, N_FLOATS)
+        if len(self.ints) != len(self.floats):
+            raise ValueError("SparseAugmentParams: ints and floats of different batch sizes")
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, SparseAugmentParams) and np.array_equal(self.ints, other.ints)
+                and np.array_equal(self.floats.view(np.int32), other.floats.view(np.int32)))
+
+    @property
+    def sizes(self):
+        return [(int(a), int(b)) for a, b in self.ints[:, [I_HS, I_WS]]]
+
+    @classmethod
+    def record(cls, src: Tuple[int, int], *args, **kw) -> "SparseAugmentParams":
+        """One record of a sample of size ``src``; the other arguments are ``AugmentParams.record``'s."""
+        dense = AugmentParams.record(src, *args, **kw)
+        ints = np.zeros((1, N_INTS_SPARSE), dtype=np.int32)
+        ints[:, :N_INTS] = dense.ints
+        ints[0, [I_HS, I_WS]] = src
+        return cls(ints, dense.floats)
+
+    @classmethod
+    def identity(cls, sizes: Sequence[Tuple[int, int]], origins=None) -> "SparseAugmentParams":
+        origins = origins or [(0, 0)] * len(sizes)
+        return cls.cat([cls.record(s, origin=o) for s, o in zip(sizes, origins)])
+
+    @classmethod
+    def sample(cls, *a, **kw):
+        raise TypeError("SparseAugmentParams: use sample_sparse (the samples have sizes of their own)")
+
+    def validate(self, buffer: Tuple[int, int], crop: Tuple[int, int]) -> None:
+        """Every record against its own sample size as the dense check does, plus: the sample fits
+        the ``buffer`` (Hb, Wb), and no axis shrinks by more than :data:`MAX_RATIO`."""
+        Hb, Wb = buffer
+        for n in range(len(self)):
+            Hs, Ws = (int(v) for v in self.ints[n, [I_HS, I_WS]])
+            if Hs < 1 or Ws < 1 or Hs > Hb or Ws > Wb:
+                raise ValueError(f"augment: record {n}: the sample {Hs}x{Ws} does not fit the buffer {Hb}x{Wb}")
+            try:
+                AugmentParams(self.ints[n:n + 1, :N_INTS], self.floats[n:n + 1]).validate((Hs, Ws), crop)
+            except ValueError as e:
+                raise ValueError(str(e).replace("record 0", f"record {n}")) from None
+            Hr, Wr = (int(v) for v in self.ints[n, [I_HR, I_WR]])
+            if Ws > MAX_RATIO * Wr or Hs > MAX_RATIO * Hr:
+                raise ValueError(f"augment: record {n}: {Hs}x{Ws} -> {Hr}x{Wr} shrinks an axis by more than {MAX_RATIO:g}")
+
+    # packed(): the base class's, (B, 52) words here
+
+
+def sample_sparse(batch: int, sizes: Sequence[Tuple[int, int]], stage: str = "kitti",
+                  crop: Optional[Tuple[int, int]] = None, seed: int = 0, step: int = 0, rank: int = 0,
+                  augment: bool = True) -> SparseAugmentParams:
+    """``batch`` records for samples of ``sizes`` from RAFT's sparse-augmentor distributions, a pure
+    function of its arguments: spatial augmentation with probability 0.8 -- one scale for both
+    axes, never below ``max((h + 1) / Hs, (w + 1) / Ws)`` --, an h-flip where the preset has one,
+    a crop origin drawn with margins and clipped (which pulls crops to the borders), symmetric
+    colour, the eraser of ``AugmentParams.sample``.  ``augment=False``: identity records with a
+    random crop."""
+    if stage not in SPARSE_STAGES:
+        raise ValueError(f"unknown sparse augmentation stage {stage!r} (one of {sorted(SPARSE_STAGES)})")
+    if len(sizes) != batch:
+        raise ValueError(f"sample_sparse: {len(sizes)} sizes for a batch of {batch}")
+    st = SPARSE_STAGES[stage]
+    h, w = crop or st.crop
+    out = []
+    for n, (Hs, Ws) in enumerate(sizes):
+        if Hs < h or Ws < w:
+            raise ValueError(f"source {Hs}x{Ws} is smaller than the crop {h}x{w}")
+        g = np.random.default_rng([int(seed), int(step), int(rank), n])
+        scale = 1.0
+        if augment and g.random() < 0.8:                # spatial augmentation
+            scale = max(2.0 ** g.uniform(st.min_scale, st.max_scale), (h + 1) / Hs, (w + 1) / Ws)
+        Hr, Wr = max(h, int(round(Hs * scale))), max(w, int(round(Ws * scale)))
+        hflip = bool(augment and g.random() < _SPARSE_HFLIP[stage])
+        y0 = int(np.clip(g.integers(0, Hr - h + 20), 0, Hr - h))
+        x0 = int(np.clip(g.integers(-50, Wr - w + 50), 0, Wr - w))
+        colour, rects = None, []
+        if augment:
+            b, k, s = g.uniform(0.6, 1.4, 3)
+            colour = (float(b), float(k), float(s), 2.0 * math.pi * g.uniform(-0.5 / 3.14, 0.5 / 3.14))
+            if g.random() < 0.5:                        # eraser
+                for _ in range(int(g.integers(1, 3))):
+                    rx, ry = int(g.integers(0, Ws)), int(g.integers(0, Hs))
+                    dx, dy = int(g.integers(50, 101)), int(g.integers(50, 101))
+                    rects.append((rx, ry, rx + dx, ry + dy))
+        out.append(SparseAugmentParams.record((Hs, Ws), (Hr, Wr), (y0, x0), hflip, False, colour, colour, rects))
+    return SparseAugmentParams.cat(out)
+
+
+@torch.no_grad()
+def augment_pairs_sparse(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tensor, valid_u8: torch.Tensor,
+                         params: SparseAugmentParams, crop: Tuple[int, int], return_landers: bool = False):
+    """The golden op for sparse ground truth, this project's definition of RAFT's
+    ``SparseFlowAugmentor`` as fp32 operations: (B, Hb, Wb, 3) uint8 x 2, (B, Hb, Wb, 2) fp32 flow,
+    (B, Hb, Wb) uint8 valid, sample n in the top-left (Hs, Ws) corner its record names -> the
+    outputs of :func:`augment_pairs`.  Nothing outside a sample's own region is read.
+
+    Images: steps 1-3 of the module docstring with the sample's own Hs, Ws and colour sums.
+
+    Flow: a sparse map cannot be interpolated, it is moved point by point.  A forward map from
+    every source pixel (ys, xs) with ``valid != 0``:
+
+    1. ``X = rint(fp32(xs) * isx)``, ``Y = rint(fp32(ys) * isy)`` (half to even), isx = Wr / Ws and
+       isy = Hr / Hs the record's fp32 words.
+    2. The point lands iff ``0 <= X < Wr`` and ``0 <= Y < Hr`` (one that rounds to Wr is dropped).
+       RAFT tests ``X > 0`` and so throws away row and column 0; this op does not, so that an
+       identity record is a plain crop.
+    3. Of several points on one cell the one with the largest ``ys * Ws + xs`` wins (RAFT's
+       ``flow_img[yy, xx] = flow1``: the last assignment stays).
+    4. The cell's value is ``(fx * isx, fy * isy)`` of the winner; a flip mirrors the cell
+       (``Wr - 1 - X``, ``Hr - 1 - Y``) and negates its component; the crop subtracts (y0, x0).
+    5. valid = 1 iff a point landed and both scaled components are below 1000 in magnitude
+       (false for NaN; there is no fallback to another lander); the flow is 0 where valid = 0.
+
+    Written as that forward scatter (``scatter_reduce(amax)`` of the linear source index, then a
+    gather of the winners); the kernel is a gather that inverts the map, so the two are independent.
+    ``return_landers``: also the number of landers per output pixel, (B, h, w) int64, and the number
+    of valid points dropped at ``X == Wr`` per sample."""
+    if (img1_u8.ndim != 4 or img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8
+            or img1_u8.shape != img2_u8.shape or img1_u8.shape[-1] != 3):
+        raise ValueError("augment_pairs_sparse: images must be (B, Hb, Wb, 3) uint8 of one size")
+    B, Hb, Wb, _ = img1_u8.shape
+    h, w = crop
+    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, Hb, Wb, 2):
+        raise ValueError("augment_pairs_sparse: flow must be (B, Hb, Wb, 2) fp32")
+    if valid_u8.dtype != torch.uint8 or tuple(valid_u8.shape) != (B, Hb, Wb):
+        raise ValueError("augment_pairs_sparse: valid must be (B, Hb, Wb) uint8")
+    if not isinstance(params, SparseAugmentParams) or len(params) != B:
+        raise ValueError(f"augment_pairs_sparse: SparseAugmentParams for a batch of {B} wanted")
+    params.validate((Hb, Wb), (h, w))
+    dev = img1_u8.device
+    outs, landers, dropped = [], [], []
+    for n in range(B):
+        Hs, Ws = params.sizes[n]
+        one = AugmentParams(params.ints[n:n + 1, :N_INTS], params.floats[n:n + 1])
+        pi, pf, _, _ = _records_on(one, dev)
+        image1, image2 = _gather_images(img1_u8[n:n + 1, :Hs, :Ws], img2_u8[n:n + 1, :Hs, :Ws], pi, pf, h, w)[:2]
+        Hr, Wr, y0, x0, hflip, vflip = (int(v) for v in params.ints[n, [I_HR, I_WR, I_Y0, I_X0, I_HFLIP, I_VFLIP]])
+        isx, isy = pf[0, F_ISX], pf[0, F_ISY]
+        # the forward scatter: the winner of a cell is the largest linear index that lands on it
+        X = torch.round(torch.arange(Ws, device=dev).float() * isx).long().view(1, Ws).expand(Hs, Ws)
+        Y = torch.round(torch.arange(Hs, device=dev).float() * isy).long().view(Hs, 1).expand(Hs, Ws)
+        on = valid_u8[n, :Hs, :Ws] != 0
+        lands = on & (X >= 0) & (X < Wr) & (Y >= 0) & (Y < Hr)
+        cell = (Y * Wr + X)[lands]
+        lin = torch.arange(Hs * Ws, device=dev).view(Hs, Ws)[lands]
+        winner = torch.full((Hr * Wr,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, cell, lin, "amax")
+        # the gather of the crop: output (y, x) is the cell (y + y0, x + x0), mirrored on a flip
+        v = torch.arange(h, device=dev) + y0
+        u = torch.arange(w, device=dev) + x0
+        v = Hr - 1 - v if vflip else v
+        u = Wr - 1 - u if hflip else u
+        cells = v.view(h, 1) * Wr + u.view(1, w)
+        win = winner[cells]
+        landed = win >= 0
+        f = flow[n, :Hs, :Ws].reshape(Hs * Ws, 2)[win.clamp(min=0)]
+        fx, fy = f[..., 0] * isx, f[..., 1] * isy
+        fx = -fx if hflip else fx
+        fy = -fy if vflip else fy
+        ok = landed & (fx.abs() < MAX_FLOW) & (fy.abs() < MAX_FLOW)
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        out_flow = torch.stack([torch.where(ok, fx, zero), torch.where(ok, fy, zero)], dim=-1)
+        outs.append((image1[0], image2[0], out_flow, ok.float()))
+        if return_landers:
+            count = torch.zeros(Hr * Wr, dtype=torch.int64, device=dev).scatter_add(0, cell, torch.ones_like(cell))
+            landers.append(count[cells])
+            dropped.append(int((on & (X == Wr)).sum()))
+    res = tuple(torch.stack([o[k] for o in outs]).contiguous() for k in range(4))
+    return res + (torch.stack(landers), dropped) if return_landers else res

@@ -7,9 +7,14 @@ and uploads them; the crop and every augmentation happen afterwards on the devic
 (``ops/native.py:augment_pairs``).  A worker thread decodes batch ``step + 1`` into a ring of
 pinned staging buffers while batch ``step`` trains.
 
-Not covered (``NotImplementedError`` or absent): the sparse KITTI / HD1K augmentor and ``.png``
-flow, mixed-dataset sampling for the Sintel stage, datasets with more than one frame size,
-FlyingThings' ``.pfm`` flow.
+Sparse ground truth: :class:`SparseFlowPairs` lists KITTI-2015 and HD1K, whose flow is a 16-bit
+PNG with a validity channel (``utils/flow_io.py:read_flow_png``) and whose frames come in several
+sizes.  The loader then stages every sample in the top-left corner of buffers of the largest
+size, adds a uint8 valid plane and the list of sizes, and the device op is
+``ops/native.py:augment_pairs_sparse``.
+
+Not covered (``NotImplementedError`` or absent): mixed-dataset sampling for the Sintel stage,
+dense and sparse samples in one batch, FlyingThings' ``.pfm`` flow.
 """
 from __future__ import annotations
 
@@ -25,7 +30,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ..utils.flow_io import read_flo, read_image
+from ..utils.flow_io import png_size, read_flo, read_flow_png, read_image
 
 MAX_THREADS = 16
 _PPM_HEADER = re.compile(rb"P6\s+(\d+)\s+(\d+)\s+255\s")
@@ -56,6 +61,12 @@ def read_frame(path: str) -> np.ndarray:
                 if data.size == h * w * 3:
                     return data.reshape(h, w, 3)
     return read_image(path)
+
+
+class SparseLayoutNotFound(FileNotFoundError, NotImplementedError):
+    """``root`` does not hold the KITTI / HD1K layout that was asked for.  A ``FileNotFoundError``;
+    also a ``NotImplementedError``, which is what ``FlowPairs.open`` raised for these two names
+    whatever the root held while they had no reader, so callers that catch that keep working."""
 
 
 class FlowPairs:
@@ -98,9 +109,48 @@ class FlowPairs:
             return cls.chairs(root)
         if dataset in ("sintel-clean", "sintel-final"):
             return cls.sintel(root, dataset.split("-")[1])
-        if dataset in ("things", "kitti", "hd1k"):
-            raise NotImplementedError(f"dataset {dataset!r}: .pfm / sparse .png flow readers are not implemented")
-        raise ValueError(f"unknown dataset {dataset!r} (chairs, sintel-clean, sintel-final)")
+        if dataset == "kitti":
+            return cls.kitti(root)
+        if dataset == "hd1k":
+            return cls.hd1k(root)
+        if dataset == "things":
+            raise NotImplementedError(f"dataset {dataset!r}: the .pfm flow reader is not implemented")
+        raise ValueError(f"unknown dataset {dataset!r} (chairs, sintel-clean, sintel-final, kitti, hd1k)")
+
+    @classmethod
+    def kitti(cls, root: str) -> "SparseFlowPairs":
+        """KITTI-2015 training: ``training/image_2/NNNNNN_10.png``, ``NNNNNN_11.png`` and the flow
+        ``training/flow_occ/NNNNNN_10.png``."""
+        firsts = sorted(glob(osp.join(root, "training", "image_2", "*_10.png")))
+        if not firsts:
+            raise SparseLayoutNotFound(f"no training/image_2/*_10.png under {root}")
+        items = []
+        for a in firsts:
+            b = a[:-len("_10.png")] + "_11.png"
+            f = osp.join(root, "training", "flow_occ", osp.basename(a))
+            for p in (b, f):
+                if not osp.isfile(p):
+                    raise FileNotFoundError(p)
+            items.append((a, b, f))
+        return SparseFlowPairs(items)
+
+    @classmethod
+    def hd1k(cls, root: str) -> "SparseFlowPairs":
+        """HD1K: ``hd1k_input/image_2/SSSSSS_NNNN.png`` with the flow
+        ``hd1k_flow_gt/flow_occ/SSSSSS_NNNN.png``; consecutive frames of one sequence are a pair."""
+        flows = sorted(glob(osp.join(root, "hd1k_flow_gt", "flow_occ", "*_*.png")))
+        if not flows:
+            raise SparseLayoutNotFound(f"no hd1k_flow_gt/flow_occ/*.png under {root}")
+        image = lambda f: osp.join(root, "hd1k_input", "image_2", osp.basename(f))
+        items = []
+        for f, nxt in zip(flows, flows[1:]):
+            if osp.basename(f).split("_")[0] != osp.basename(nxt).split("_")[0]:
+                continue                            # the last frame of a sequence has no successor
+            for p in (image(f), image(nxt)):
+                if not osp.isfile(p):
+                    raise FileNotFoundError(p)
+            items.append((image(f), image(nxt), f))
+        return SparseFlowPairs(items)
 
     def __len__(self) -> int:
         return len(self.items)
@@ -116,6 +166,22 @@ class FlowPairs:
         return read_frame(a), read_frame(b), flow
 
 
+class SparseFlowPairs(FlowPairs):
+    """``ds[i] -> (image1, image2, flow fp32 (H, W, 2), valid uint8 (H, W))`` over PNG frames and
+    KITTI-coded flow PNG; the pairs may differ in size."""
+
+    sparse = True
+
+    def __getitem__(self, i: int):
+        a, b, f = self.items[i]
+        flow, valid = read_flow_png(f)
+        return read_image(a), read_image(b), flow, valid
+
+    def sizes(self) -> List[Tuple[int, int]]:
+        """(H, W) of every pair's first image, from the files' IHDR chunks (24 bytes each)."""
+        return [png_size(a) for a, _, _ in self.items]
+
+
 class PairLoader:
     """Batches of raw frames, a pure function of the step.
 
@@ -126,6 +192,12 @@ class PairLoader:
     flow fp32 (B, H, W, 2))`` -- uploaded ``non_blocking`` on the current stream from pinned
     staging buffers, and starts decoding ``step + 1`` on the worker thread.  Fetching steps in
     order therefore overlaps decode with training; any other step is decoded on the spot.
+
+    Over a :class:`SparseFlowPairs` the frames may differ in size: ``frame_max`` / ``frame_min`` are
+    the largest / smallest height and width in the list, the buffers are (B, Hmax, Wmax, ...) with
+    every sample in the top-left corner, and ``fetch`` returns ``(image1, image2, flow, valid uint8
+    (B, Hmax, Wmax), sizes)``, ``sizes`` a host-side list of (Hs, Ws).  The bytes outside a
+    sample's own region are whatever an earlier batch left there: nothing may depend on them.
     """
 
     def __init__(self, dataset: FlowPairs, batch: int, seed: int = 0, rank: int = 0, world: int = 1,
@@ -135,10 +207,17 @@ class PairLoader:
         self.steps_per_epoch = len(dataset) // (self.batch * self.world)
         if self.steps_per_epoch < 1:
             raise ValueError(f"{len(dataset)} pairs do not fill one batch of {self.batch} on {self.world} rank(s)")
-        a, _, f = dataset[0]
-        self.frame = tuple(a.shape[:2])
-        if tuple(f.shape[:2]) != self.frame:
-            raise ValueError(f"{dataset.items[0][2]}: flow {f.shape[:2]} does not match its frame {self.frame}")
+        self.sparse = bool(getattr(dataset, "sparse", False))
+        if self.sparse:
+            self._sizes = dataset.sizes()
+            self.frame_max = (max(s[0] for s in self._sizes), max(s[1] for s in self._sizes))
+            self.frame_min = (min(s[0] for s in self._sizes), min(s[1] for s in self._sizes))
+            self.frame = self.frame_max            # the buffers' size
+        else:
+            a, _, f = dataset[0]
+            self.frame = self.frame_max = self.frame_min = tuple(a.shape[:2])
+            if tuple(f.shape[:2]) != self.frame:
+                raise ValueError(f"{dataset.items[0][2]}: flow {f.shape[:2]} does not match its frame {self.frame}")
         self.depth = max(2, int(depth))
         self._pin = self.device.type == "cuda"
         self._slots = [None] * self.depth          # staging buffers, allocated on first use
@@ -164,9 +243,20 @@ class PairLoader:
             mk = lambda shape, dt: torch.empty(shape, dtype=dt, pin_memory=self._pin)
             self._slots[slot] = (mk((self.batch, H, W, 3), torch.uint8), mk((self.batch, H, W, 3), torch.uint8),
                                  mk((self.batch, H, W, 2), torch.float32))
+            if self.sparse:
+                self._slots[slot] += (mk((self.batch, H, W), torch.uint8),)
         return self._slots[slot]
 
     def _decode_one(self, bufs, n: int, index: int) -> None:
+        if self.sparse:
+            arrs = self.ds[index]
+            Hs, Ws = self._sizes[index]
+            for arr, path in zip(arrs, self.ds.items[index] + (self.ds.items[index][2],)):
+                if tuple(arr.shape[:2]) != (Hs, Ws):
+                    raise ValueError(f"{path}: size {tuple(arr.shape[:2])} differs from the pair's first image {(Hs, Ws)}")
+            for buf, arr in zip(bufs, arrs):       # into the top-left corner; the rest of the buffer stays as it is
+                np.copyto(buf[n].numpy()[:Hs, :Ws], arr)
+            return
         a, b, f = self.ds[index]
         for arr, path in zip((a, b, f), self.ds.items[index]):
             if tuple(arr.shape[:2]) != self.frame:
@@ -203,6 +293,10 @@ class PairLoader:
             if step not in self._pending:
                 self._pending[step] = self._worker.submit(self._decode, step, idx)
 
+    def sizes_for(self, step: int) -> List[Tuple[int, int]]:
+        """(Hs, Ws) of every sample of ``step`` (all ``frame`` for a dense list)."""
+        return [self._sizes[i] if self.sparse else self.frame for i in self.indices_for(step)]
+
     def fetch(self, step: int):
         bufs = self.host_batch(step)
         if self.device.type == "cuda":
@@ -213,6 +307,8 @@ class PairLoader:
         else:
             out = tuple(b.clone() for b in bufs)
         self.prefetch(step + 1)
+        if self.sparse:
+            out += (self.sizes_for(step),)
         return out
 
     def close(self) -> None:

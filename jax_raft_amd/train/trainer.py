@@ -13,6 +13,8 @@ Without ``--data`` the batches are ``SyntheticFlow``.  ``--data <root> [--datase
 sintel-clean | sintel-final] [--stage chairs | things | sintel] [--no-augment]`` trains on files:
 the raw frames are uploaded as they are and cropped + augmented in one gather on the device
 (train/datasets.py, train/augment.py); every batch is a pure function of (seed, step, rank).
+``--dataset kitti | hd1k`` (sparse ground truth, frames of several sizes) takes ``--stage kitti``
+(crop 288x960) or ``--stage sintel`` and the sparse augmentation op.
 
 Checkpoints: ``<dir>/step_<n>.msgpack`` (Flax-format weights, loadable with
 ``raft_large(weights=...)``) + ``step_<n>.opt.pt`` (optimizer / scheduler
@@ -69,18 +71,24 @@ class TrainConfig:
     graph_warmup: int = 3          # eager steps before the capture (plan build, autotune, allocator warm-up)
     # Real data (train/datasets.py, train/augment.py).  data=None: SyntheticFlow, as ever.
     data: Optional[str] = None     # dataset root
-    dataset: str = "chairs"        # chairs | sintel-clean | sintel-final
-    stage: str = "chairs"          # augmentation preset (chairs | things | sintel); sets size when size is left at its default
+    dataset: str = "chairs"        # chairs | sintel-clean | sintel-final | kitti | hd1k (sparse ground truth)
+    # augmentation preset, dense: chairs | things | sintel, sparse: kitti | sintel; sets size when size is left at its default
+    stage: str = "chairs"
     augment: bool = True           # False: identity records, i.e. a random crop + normalisation only
 
     def __post_init__(self):
         if self.data is not None:
-            from .augment import STAGES
+            from .augment import SPARSE_STAGES, STAGES
 
-            if self.stage not in STAGES:
-                raise ValueError(f"unknown stage {self.stage!r} (one of {sorted(STAGES)})")
+            stages = SPARSE_STAGES if self.sparse else STAGES
+            if self.stage not in stages:
+                raise ValueError(f"unknown stage {self.stage!r} for dataset {self.dataset!r} (one of {sorted(stages)})")
             if tuple(self.size) == tuple(type(self).__dataclass_fields__["size"].default):
-                self.size = STAGES[self.stage].crop
+                self.size = stages[self.stage].crop
+
+    @property
+    def sparse(self) -> bool:
+        return self.dataset in ("kitti", "hd1k")
 
 
 def _adamw(params, cfg: TrainConfig, device, capturable: bool = False):
@@ -135,8 +143,8 @@ class Trainer:
 
             self.loader = PairLoader(FlowPairs.open(cfg.data, cfg.dataset), cfg.batch, seed=cfg.seed, rank=self.rank,
                                      world=self.world, device=self.device)
-            if self.loader.frame[0] < cfg.size[0] or self.loader.frame[1] < cfg.size[1]:
-                raise ValueError(f"{cfg.data}: frames {self.loader.frame} are smaller than the crop {tuple(cfg.size)}")
+            if self.loader.frame_min[0] < cfg.size[0] or self.loader.frame_min[1] < cfg.size[1]:
+                raise ValueError(f"{cfg.data}: frames {self.loader.frame_min} are smaller than the crop {tuple(cfg.size)}")
         self.step = 0
         self.skipped = 0           # total dropped steps
         self._skip_run = 0         # consecutive dropped steps
@@ -278,10 +286,15 @@ class Trainer:
             # real data: the raw frames of this step, then crop + augmentation in one gather on the
             # device (the golden op on a CPU device); records and indices are functions of the step
             from ..ops import native as nat
-            from .augment import AugmentParams
+            from .augment import AugmentParams, sample_sparse
 
-            img1, img2, flow = self.loader.fetch(step)
             crop = (int(cfg.size[0]), int(cfg.size[1]))
+            if self.loader.sparse:
+                img1, img2, flow, valid, sizes = self.loader.fetch(step)
+                params = sample_sparse(cfg.batch, sizes, cfg.stage, crop, seed=cfg.seed, step=step, rank=self.rank,
+                                       augment=cfg.augment)
+                return nat.augment_pairs_sparse(img1, img2, flow, valid, params, crop)
+            img1, img2, flow = self.loader.fetch(step)
             params = AugmentParams.sample(cfg.batch, self.loader.frame, cfg.stage, crop, seed=cfg.seed, step=step,
                                           rank=self.rank, augment=cfg.augment)
             return nat.augment_pairs(img1, img2, flow, params, crop)

@@ -16,7 +16,15 @@ sizes (source 384 x 512, crop 368 x 496, batch 6), in one fresh process on one G
 
 PNG decoding (Sintel) is not covered: the generated dataset is PPM.
 
+``--sparse``: the same for sparse ground truth at the KITTI sizes (sources 375 x 1242 and
+370 x 1226 mixed in one batch, crop 288 x 960, batch 6): the two launches of
+``augment_sparse.hip`` on sampled ``kitti`` records, the training loop on a generated KITTI tree
+(PNG frames, flow written by ``write_flow_png`` with the five filter types cycling over the rows)
+against ``SyntheticFlow`` at the crop size, and the host time of one flow-PNG decode with the
+C++ un-filter and with the numpy fallback.
+
   python tools/augment_bench.py [--out profiles/augment_overhead.txt]
+  python tools/augment_bench.py --sparse [--out profiles/sparse_augment_overhead.txt]
 """
 import argparse
 import os
@@ -30,11 +38,12 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from jax_raft_amd.ops import native as nat  # noqa: E402
-from jax_raft_amd.train import AugmentParams, FlowPairs, PairLoader  # noqa: E402
+from jax_raft_amd.train import AugmentParams, FlowPairs, PairLoader, sample_sparse  # noqa: E402
 from jax_raft_amd.train.trainer import TrainConfig, Trainer  # noqa: E402
-from jax_raft_amd.utils.flow_io import write_flo  # noqa: E402
+from jax_raft_amd.utils.flow_io import read_flow_png, write_flo, write_flow_png  # noqa: E402
 
 SRC, CROP, BATCH = (384, 512), (368, 496), 6
+KITTI_SIZES, KITTI_CROP = [(375, 1242), (370, 1226)], (288, 960)
 
 
 def write_dataset(root, n, seed=0):
@@ -53,19 +62,10 @@ def write_dataset(root, n, seed=0):
         write_flo(stem + "_flow.flo", flow)
 
 
-def kernel_times(dev, reps):
-    g = torch.Generator().manual_seed(0)
-    i1 = torch.randint(0, 256, (BATCH, *SRC, 3), generator=g, dtype=torch.uint8).to(dev)
-    i2 = torch.randint(0, 256, (BATCH, *SRC, 3), generator=g, dtype=torch.uint8).to(dev)
-    flow = torch.randn(BATCH, *SRC, 2, generator=g).to(dev)
-    recs = [AugmentParams.sample(BATCH, SRC, "chairs", step=s).packed().to(dev) for s in range(8)]
-    sums = torch.empty(2, BATCH, 3, dtype=torch.int32, device=dev)
-    o1, o2 = (torch.empty(BATCH, *CROP, 3, device=dev) for _ in range(2))
-    of, ov = torch.empty(BATCH, *CROP, 2, device=dev), torch.empty(BATCH, *CROP, device=dev)
-    run_sums = lambda k: nat.ops().augment_sums([i1, i2, sums], [BATCH, *SRC])
-    run_gather = lambda k: nat.ops().augment([i1, i2, flow, recs[k % 8], sums, o1, o2, of, ov], [BATCH, *SRC, *CROP])
+def timed(fns_by_name, dev, reps):
+    """us per batch of each named sequence of launches, from device events over ``reps`` repetitions."""
     out = {}
-    for name, fns in (("sums", (run_sums,)), ("gather", (run_gather,)), ("both", (run_sums, run_gather))):
+    for name, fns in fns_by_name:
         for k in range(10):
             for f in fns:
                 f(k)
@@ -77,15 +77,165 @@ def kernel_times(dev, reps):
                 f(k)
         e1.record()
         torch.cuda.synchronize(dev)
-        out[name] = 1000 * e0.elapsed_time(e1) / reps          # us per batch
+        out[name] = 1000 * e0.elapsed_time(e1) / reps
     return out
+
+
+def alternate(arms, args, dev):
+    """Warm both trainers up, then blocks of ``args.block`` steps alternated between them for
+    ``args.rounds`` rounds: pairs/s per block and the ms per step ``batch_for`` holds the loop."""
+    for name, tr in arms.items():
+        t0 = time.perf_counter()
+        for _ in range(args.warmup):
+            tr.train_step(tr.batch_for(tr.step))
+        tr.flush()
+        torch.cuda.synchronize(dev)
+        print(f"warm-up of {name}: {time.perf_counter() - t0:.1f} s", flush=True)
+    rate = {k: [] for k in arms}
+    held = {k: [] for k in arms}
+    for _ in range(args.rounds):
+        for name, tr in arms.items():
+            h = 0.0
+            t0 = time.perf_counter()
+            for _ in range(args.block):
+                h0 = time.perf_counter()
+                batch = tr.batch_for(tr.step)
+                h += time.perf_counter() - h0
+                m = tr.train_step(batch)
+            tr.flush()
+            torch.cuda.synchronize(dev)
+            dt = time.perf_counter() - t0
+            rate[name].append(BATCH * args.block / dt)
+            held[name].append(1000 * h / args.block)
+            assert torch.isfinite(m["loss"]).item(), name
+    return rate, held
+
+
+def write_kitti_dataset(root, n, seed=0):
+    """A KITTI-2015 training tree of n pairs, the two sizes alternating; half of the flow is valid."""
+    from PIL import Image
+
+    rng = np.random.default_rng(seed)
+    for d in ("image_2", "flow_occ"):
+        os.makedirs(os.path.join(root, "training", d))
+    for k in range(n):
+        Hs, Ws = KITTI_SIZES[k % 2]
+        ys, xs = np.mgrid[0:Hs, 0:Ws].astype(np.float32)
+        base = rng.integers(0, 256, (Hs // 8 + 1, Ws // 8 + 1, 3), dtype=np.uint8)
+        img = np.kron(base, np.ones((8, 8, 1), np.uint8))[:Hs, :Ws]                # blocky texture
+        a, b = rng.uniform(-4, 4, 2)
+        flow = np.stack([a + 0.01 * (xs - Ws / 2), b + 0.01 * (ys - Hs / 2)], -1).astype(np.float32)
+        valid = rng.random((Hs, Ws)) < 0.5
+        Image.fromarray(img).save(os.path.join(root, "training", "image_2", f"{k:06d}_10.png"))
+        Image.fromarray(np.roll(img, (int(round(b)), int(round(a))), (0, 1))).save(
+            os.path.join(root, "training", "image_2", f"{k:06d}_11.png"))
+        write_flow_png(os.path.join(root, "training", "flow_occ", f"{k:06d}_10.png"), flow, valid, np.arange(Hs) % 5)
+
+
+def sparse_kernel_times(dev, reps):
+    g = torch.Generator().manual_seed(0)
+    sizes = [KITTI_SIZES[n % 2] for n in range(BATCH)]
+    Hb, Wb = KITTI_SIZES[0]
+    i1 = torch.randint(0, 256, (BATCH, Hb, Wb, 3), generator=g, dtype=torch.uint8).to(dev)
+    i2 = torch.randint(0, 256, (BATCH, Hb, Wb, 3), generator=g, dtype=torch.uint8).to(dev)
+    flow = torch.randn(BATCH, Hb, Wb, 2, generator=g).to(dev)
+    valid = (torch.rand(BATCH, Hb, Wb, generator=g) < 0.5).to(torch.uint8).to(dev)
+    recs = [sample_sparse(BATCH, sizes, "kitti", step=s).packed().to(dev) for s in range(8)]
+    sums = torch.empty(2, BATCH, 3, dtype=torch.int32, device=dev)
+    o1, o2 = (torch.empty(BATCH, *KITTI_CROP, 3, device=dev) for _ in range(2))
+    of, ov = torch.empty(BATCH, *KITTI_CROP, 2, device=dev), torch.empty(BATCH, *KITTI_CROP, device=dev)
+    run_sums = lambda k: nat.ops().augment_sparse_sums([i1, i2, recs[k % 8], sums], [BATCH, Hb, Wb])
+    run_gather = lambda k: nat.ops().augment_sparse([i1, i2, flow, valid, recs[k % 8], sums, o1, o2, of, ov],
+                                                    [BATCH, Hb, Wb, *KITTI_CROP])
+    out = timed((("sums", (run_sums,)), ("gather", (run_gather,)), ("both", (run_sums, run_gather))), dev, reps)
+    # the upload of one batch as PairLoader.fetch does it: pinned staging buffers -> fresh device tensors, in-stream
+    pinned = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in (i1, i2, flow, valid)]
+    upload = lambda k: [torch.empty(b.shape, dtype=b.dtype, device=dev).copy_(b, non_blocking=True) for b in pinned]
+    out["upload"] = timed((("upload", (upload,)),), dev, 50)["upload"]
+    out["upload_mb"] = sum(b.numel() * b.element_size() for b in pinned) / 1e6
+    return out
+
+
+def sparse_main(args, dev):
+    lines = [f"training on sparse ground truth vs SyntheticFlow, {torch.cuda.get_device_name(dev)}",
+             f"KITTI sizes: sources {' and '.join(f'{h}x{w}' for h, w in KITTI_SIZES)} mixed, crop "
+             f"{KITTI_CROP[0]}x{KITTI_CROP[1]}, batch {BATCH}", ""]
+    kt = sparse_kernel_times(dev, args.reps)
+    lines += [f"(a) GPU time per batch, device events over {args.reps} repetitions (sampled kitti records):",
+              f"    sized colour sums (memset + kernel) {kt['sums']:8.1f} us",
+              f"    gather (images + flow scan)         {kt['gather']:8.1f} us",
+              f"    both, back to back                  {kt['both']:8.1f} us",
+              f"    upload of one batch, {kt['upload_mb']:.1f} MB pinned -> device in the stream (images, fp32 flow, valid): "
+              f"{kt['upload']:8.1f} us", ""]
+    print("\n".join(lines), flush=True)
+    with tempfile.TemporaryDirectory() as root:
+        t0 = time.perf_counter()
+        write_kitti_dataset(root, args.pairs)
+        t_write = time.perf_counter() - t0
+        one = os.path.join(root, "training", "flow_occ", "000000_10.png")
+        dec_c = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            read_flow_png(one, native=True)
+            dec_c.append(1000 * (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        read_flow_png(one, native=False)
+        dec_np = 1000 * (time.perf_counter() - t0)
+        total = args.warmup + args.block * args.rounds
+        kw = dict(arch=args.arch, steps=total, batch=BATCH, iters=args.iters, size=KITTI_CROP, log_every=10 ** 9)
+        arms = {"real": Trainer(TrainConfig(data=root, dataset="kitti", stage="kitti", **kw)), "synth": Trainer(TrainConfig(**kw))}
+        ld = PairLoader(FlowPairs.kitti(root), BATCH)           # a CPU loader: decode alone, nothing overlapping
+        dec = []
+        for s in range(4):
+            t0 = time.perf_counter()
+            ld.host_batch(s)
+            dec.append(1000 * (time.perf_counter() - t0))
+        ld.close()
+        rate, held = alternate(arms, args, dev)
+        arms["real"].loader.close()
+    mean = lambda v: sum(v) / len(v)
+    r, s = mean(rate["real"]), mean(rate["synth"])
+    ms = lambda x: 1000 * BATCH / x
+    spread = max(max(v) - min(v) for v in rate.values())
+    threads = __import__("jax_raft_amd.train.datasets", fromlist=["x"]).decode_threads()
+    lines += [f"(b) training loop, {args.arch}, {args.iters} iterations, {args.block} steps per block, blocks alternated "
+              f"real / synth x {args.rounds} in one process after {args.warmup} warm-up steps each",
+              f"    ({args.pairs} generated pairs, PNG frames + KITTI flow PNG, written in {t_write:.1f} s; decode threads: {threads})"]
+    for k in arms:
+        lines.append(f"    {k:5s} {mean(rate[k]):7.1f} pairs/s  {ms(mean(rate[k])):6.2f} ms/step  [per block: "
+                     + ", ".join(f"{v:.1f}" for v in rate[k]) + f"]   batch_for holds the loop {mean(held[k]):5.2f} ms/step")
+    lines += [f"    real - synth: {ms(r) - ms(s):+.2f} ms/step ({100 * (r - s) / s:+.1f} % pairs/s); "
+              f"largest spread between blocks of one arm {spread:.1f} pairs/s",
+              f"    one batch decoded alone (2 PNG frames + 1 flow PNG per sample into staging buffers, no overlap): "
+              f"{min(dec):.2f} ms best, {mean(dec[1:]):.2f} ms mean of {len(dec) - 1}",
+              f"    the two launches of (a) are {kt['both'] / 1000:.3f} ms and the upload {kt['upload'] / 1000:.3f} ms of a real step", "",
+              f"(c) host time of one flow-PNG decode ({KITTI_SIZES[0][0]}x{KITTI_SIZES[0][1]}, 16-bit RGB, filter types 0..4 "
+              "cycling over the rows), read + inflate + un-filter + decode:",
+              f"    C++ un-filter (csrc/runtime/png.cpp) {min(dec_c):8.2f} ms best of {len(dec_c)}, {mean(dec_c[1:]):.2f} ms mean",
+              f"    numpy fallback                       {dec_np:8.2f} ms (one run)", ""]
+    return "\n".join(lines) + "\n"
+
+
+def kernel_times(dev, reps):
+    g = torch.Generator().manual_seed(0)
+    i1 = torch.randint(0, 256, (BATCH, *SRC, 3), generator=g, dtype=torch.uint8).to(dev)
+    i2 = torch.randint(0, 256, (BATCH, *SRC, 3), generator=g, dtype=torch.uint8).to(dev)
+    flow = torch.randn(BATCH, *SRC, 2, generator=g).to(dev)
+    recs = [AugmentParams.sample(BATCH, SRC, "chairs", step=s).packed().to(dev) for s in range(8)]
+    sums = torch.empty(2, BATCH, 3, dtype=torch.int32, device=dev)
+    o1, o2 = (torch.empty(BATCH, *CROP, 3, device=dev) for _ in range(2))
+    of, ov = torch.empty(BATCH, *CROP, 2, device=dev), torch.empty(BATCH, *CROP, device=dev)
+    run_sums = lambda k: nat.ops().augment_sums([i1, i2, sums], [BATCH, *SRC])
+    run_gather = lambda k: nat.ops().augment([i1, i2, flow, recs[k % 8], sums, o1, o2, of, ov], [BATCH, *SRC, *CROP])
+    return timed((("sums", (run_sums,)), ("gather", (run_gather,)), ("both", (run_sums, run_gather))), dev, reps)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/augment_overhead.txt")
+    ap.add_argument("--sparse", action="store_true", help="sparse ground truth at the KITTI sizes")
+    ap.add_argument("--out", default=None, help="default: profiles/augment_overhead.txt, or profiles/sparse_augment_overhead.txt")
     ap.add_argument("--reps", type=int, default=500)
-    ap.add_argument("--pairs", type=int, default=48, help="pairs in the generated dataset")
+    ap.add_argument("--pairs", type=int, default=None, help="pairs in the generated dataset (default 48, sparse: 24)")
     ap.add_argument("--block", type=int, default=20, help="steps per block")
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=6)
@@ -94,6 +244,10 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), "augment_bench measures on the GPU"
     dev = torch.device("cuda", 0)
+    args.out = args.out or ("profiles/sparse_augment_overhead.txt" if args.sparse else "profiles/augment_overhead.txt")
+    args.pairs = args.pairs or (24 if args.sparse else 48)
+    if args.sparse:
+        return finish(sparse_main(args, dev), args.out)
     lines = [f"training on real data vs SyntheticFlow, {torch.cuda.get_device_name(dev)}",
              f"chairs sizes: source {SRC[0]}x{SRC[1]}, crop {CROP[0]}x{CROP[1]}, batch {BATCH}", ""]
     kt = kernel_times(dev, args.reps)
@@ -117,31 +271,7 @@ def main():
             ld.host_batch(s)
             dec.append(1000 * (time.perf_counter() - t0))
         ld.close()
-        for name, tr in arms.items():
-            t0 = time.perf_counter()
-            for _ in range(args.warmup):
-                tr.train_step(tr.batch_for(tr.step))
-            tr.flush()
-            torch.cuda.synchronize(dev)
-            print(f"warm-up of {name}: {time.perf_counter() - t0:.1f} s", flush=True)
-        torch.cuda.synchronize(dev)
-        rate = {k: [] for k in arms}
-        held = {k: [] for k in arms}
-        for _ in range(args.rounds):
-            for name, tr in arms.items():
-                h = 0.0
-                t0 = time.perf_counter()
-                for _ in range(args.block):
-                    h0 = time.perf_counter()
-                    batch = tr.batch_for(tr.step)
-                    h += time.perf_counter() - h0
-                    m = tr.train_step(batch)
-                tr.flush()
-                torch.cuda.synchronize(dev)
-                dt = time.perf_counter() - t0
-                rate[name].append(BATCH * args.block / dt)
-                held[name].append(1000 * h / args.block)
-                assert torch.isfinite(m["loss"]).item(), name
+        rate, held = alternate(arms, args, dev)
         arms["real"].loader.close()
     mean = lambda v: sum(v) / len(v)
     r, s = mean(rate["real"]), mean(rate["synth"])
@@ -160,9 +290,12 @@ def main():
               f"{min(dec):.2f} ms best, {mean(dec[1:]):.2f} ms mean of {len(dec) - 1}",
               f"    the two launches of (a) are {kt['both'] / 1000:.3f} ms of a real step",
               "    PNG decoding (Sintel) is not covered: the generated dataset is PPM.", ""]
-    text = "\n".join(lines) + "\n"
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
+    finish("\n".join(lines) + "\n", args.out)
+
+
+def finish(text, out):
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
         f.write(text)
     print(text)
 
