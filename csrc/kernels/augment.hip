@@ -17,7 +17,7 @@
 
 namespace {
 
-using namespace augment_dev;   // the record words, texel, blend, source_pos, image_pixel, store_run
+using namespace augment_dev;   // the record words, texel, blend, source_pos, image_pixel, flow_blend, flow_pixel, store_run
 
 // record layout (train/augment.py:AugmentParams): 16 ints, then 32 floats
 constexpr int REC_WORDS = 48, F_BASE = 16;
@@ -93,20 +93,9 @@ __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __res
     source_pos(u, sx, Ws, x_lo, x_hi, wx);
     const int ty[4] = {y_lo, y_lo, y_hi, y_hi}, tx[4] = {x_lo, x_hi, x_lo, x_hi};
     image_pixel(p1, p2, Ws, ty, tx, wx, wy, rec, nrect, c1, c2, a1 + 3 * k, a2 + 3 * k);
-    float tf[4][2];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float2 f = *(const float2*)(pf + ((long)ty[q] * Ws + tx[q]) * 2);
-      tf[q][0] = f.x; tf[q][1] = f.y;
-    }
-    float fx = blend(tf[0][0], tf[1][0], tf[2][0], tf[3][0], wx, wy) * isx;
-    float fy = blend(tf[0][1], tf[1][1], tf[2][1], tf[3][1], wx, wy) * isy;
-    if (hflip) fx = -fx;
-    if (vflip) fy = -fy;
-    const bool ok = fabsf(fx) < 1000.f && fabsf(fy) < 1000.f;   // false for NaN
-    fl[2 * k] = ok ? fx : 0.f;
-    fl[2 * k + 1] = ok ? fy : 0.f;
-    va[k] = ok ? 1.f : 0.f;
+    float fx, fy;
+    flow_blend(pf, Ws, ty, tx, wx, wy, fx, fy);
+    flow_pixel(fx, fy, true, isx, isy, hflip, vflip, fl + 2 * k, va + k);
   }
 
   const long px = ((long)n * h + y) * w + x4;   // first output pixel of the run

@@ -1,8 +1,9 @@
-// Device helpers shared by the dense and the sparse augmentation gathers (augment.hip,
-// augment_sparse.hip): the record words both layouts have in common, the texel transform, the
-// bilinear blend, the source position of a resized coordinate, one output pixel of both images
-// and the stores of a thread's run of 4 pixels.  Both files switch contraction off; the pragma
-// below covers the functions defined here.
+// Device helpers shared by the dense, the sparse and the mixed augmentation gathers (augment.hip,
+// augment_sparse.hip, augment_mixed.hip): the record words the layouts have in common, the texel
+// transform, the bilinear blend, the source position of a resized coordinate, one output pixel of
+// both images, the flow of one output pixel from dense ground truth (the four-tap blend) and from
+// sparse ground truth (the scan for the winner), and the stores of a thread's run of 4 pixels.
+// Every file switches contraction off; the pragma below covers the functions defined here.
 #pragma once
 #include "common.h"
 
@@ -90,6 +91,64 @@ JR_DEVICE void image_pixel(const unsigned char* __restrict__ p1, const unsigned 
     a1[c] = blend(t1[0][c], t1[1][c], t1[2][c], t1[3][c], wx, wy) / 255.0f * 2.0f - 1.0f;
     a2[c] = blend(t2[0][c], t2[1][c], t2[2][c], t2[3][c], wx, wy) / 255.0f * 2.0f - 1.0f;
   }
+}
+
+// Dense ground truth: the blend of the 4 flow taps of a frame pf with rows of `pitch` pixels (before the scale).
+JR_DEVICE void flow_blend(const float* __restrict__ pf, int pitch, const int ty[4], const int tx[4], float wx, float wy,
+                          float& fx, float& fy) {
+  float tf[4][2];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float2 f = *(const float2*)(pf + ((long)ty[q] * pitch + tx[q]) * 2);
+    tf[q][0] = f.x; tf[q][1] = f.y;
+  }
+  fx = blend(tf[0][0], tf[1][0], tf[2][0], tf[3][0], wx, wy);
+  fy = blend(tf[0][1], tf[1][1], tf[2][1], tf[3][1], wx, wy);
+}
+
+constexpr int MAX_SCAN = 16;    // candidates per axis at most (a valid sparse record needs sx + 5 <= 9)
+
+// Source indices that can land on target T (train/augment.py:scan_window is the same formula):
+// rint(fp32(s) * inv) == T needs |s * inv - T| <= 0.5 up to rounding, i.e. s within
+// (T -+ 0.5) * ratio; fp32(s) * inv is monotone in s, and the rounding of the two products and
+// of ratio and inv (sizes below 2^18: a few 2^-6 in source pixels) is far inside the margin of 1.
+JR_DEVICE void scan_window(int T, float ratio, int size, int& lo, int& hi) {
+  lo = max((int)floorf(((float)T - 0.5f) * ratio) - 1, 0);
+  hi = min((int)ceilf(((float)T + 0.5f) * ratio) + 1, size - 1);
+  lo = max(lo, hi - (MAX_SCAN - 1));
+}
+
+// Sparse ground truth: the winner of cell (v, u), i.e. the source pixel with the largest linear index
+// whose valid byte is set and that lands on the cell, as an offset ys * pitch + xs into a frame with
+// rows of `pitch` pixels, or -1.  ys_lo .. ys_hi: the row window of v; Ws: the sample's width.
+JR_DEVICE long sparse_winner(const unsigned char* __restrict__ pv, int pitch, int v, int u, int ys_lo, int ys_hi, float sx,
+                             float isx, float isy, int Ws) {
+  int xs_lo, xs_hi;
+  scan_window(u, sx, Ws, xs_lo, xs_hi);
+  long win = -1;
+  for (int ys = ys_hi; ys >= ys_lo && win < 0; --ys) {
+    if (rintf((float)ys * isy) != (float)v) continue;
+    for (int xs = xs_hi; xs >= xs_lo; --xs)
+      if (rintf((float)xs * isx) == (float)u && pv[(long)ys * pitch + xs] != 0) {
+        win = (long)ys * pitch + xs;
+        break;
+      }
+  }
+  return win;
+}
+
+// The flow of one output pixel from its source value (fx, fy): the scale, the flips, the range check
+// (false for NaN; `landed`: a sparse cell without a winner is not valid), 0 where not valid.
+JR_DEVICE void flow_pixel(float fx, float fy, bool landed, float isx, float isy, bool hflip, bool vflip, float* fl,
+                          float* va) {
+  fx = fx * isx;
+  fy = fy * isy;
+  if (hflip) fx = -fx;
+  if (vflip) fy = -fy;
+  const bool ok = landed && fabsf(fx) < 1000.f && fabsf(fy) < 1000.f;
+  fl[0] = ok ? fx : 0.f;
+  fl[1] = ok ? fy : 0.f;
+  *va = ok ? 1.f : 0.f;
 }
 
 // The run of 4 pixels that starts at output pixel px (column x4 of a row of w): a1 / a2 [12],

@@ -27,7 +27,6 @@ using namespace augment_dev;
 // own size, two spare words, then the dense record's 32 floats
 constexpr int REC_WORDS = 52, I_HS = 16, I_WS = 17, F_BASE = 20;
 constexpr int SUM_PIX = 16;     // pixels per thread of the sums kernel
-constexpr int MAX_SCAN = 16;    // candidates per axis at most (a valid record needs sx + 5 <= 9)
 
 // The sample's size as the kernels use it: inside the buffer whatever the record says.
 JR_DEVICE void sample_size(const int* __restrict__ rec, int Hb, int Wb, int& Hs, int& Ws) {
@@ -69,16 +68,6 @@ __global__ __launch_bounds__(256) void augment_sparse_sums_kernel(const unsigned
     const int c = threadIdx.x;
     atomicAdd(sums + n * 3 + c, (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]));
   }
-}
-
-// Source indices that can land on target T (train/augment.py:scan_window is the same formula):
-// rint(fp32(s) * inv) == T needs |s * inv - T| <= 0.5 up to rounding, i.e. s within
-// (T -+ 0.5) * ratio; fp32(s) * inv is monotone in s, and the rounding of the two products and
-// of ratio and inv (sizes below 2^18: a few 2^-6 in source pixels) is far inside the margin of 1.
-JR_DEVICE void scan_window(int T, float ratio, int size, int& lo, int& hi) {
-  lo = max((int)floorf(((float)T - 0.5f) * ratio) - 1, 0);
-  hi = min((int)ceilf(((float)T + 0.5f) * ratio) + 1, size - 1);
-  lo = max(lo, hi - (MAX_SCAN - 1));
 }
 
 // grid: (ceil(ceil(w / 4) / 64), ceil(h / 4), B), block (64, 4): thread = 4 pixels of one row
@@ -127,30 +116,10 @@ __global__ __launch_bounds__(256) void augment_sparse_kernel(
     image_pixel(p1, p2, Wb, ty, tx, wx, wy, rec, nrect, c1, c2, a1 + 3 * k, a2 + 3 * k);
 
     // the winner of cell (v, u): the valid source pixel with the largest ys * Ws + xs that lands on it
-    int xs_lo, xs_hi;
-    scan_window(u, sx, Ws, xs_lo, xs_hi);
-    long win = -1;
-    for (int ys = ys_hi; ys >= ys_lo && win < 0; --ys) {
-      if (rintf((float)ys * isy) != (float)v) continue;
-      for (int xs = xs_hi; xs >= xs_lo; --xs)
-        if (rintf((float)xs * isx) == (float)u && pv[(long)ys * Wb + xs] != 0) {
-          win = (long)ys * Wb + xs;
-          break;
-        }
-    }
-    bool ok = false;
-    float fx = 0.f, fy = 0.f;
-    if (win >= 0) {
-      const float2 f = *(const float2*)(pf + win * 2);
-      fx = f.x * isx;
-      fy = f.y * isy;
-      if (hflip) fx = -fx;
-      if (vflip) fy = -fy;
-      ok = fabsf(fx) < 1000.f && fabsf(fy) < 1000.f;          // false for NaN
-    }
-    fl[2 * k] = ok ? fx : 0.f;
-    fl[2 * k + 1] = ok ? fy : 0.f;
-    va[k] = ok ? 1.f : 0.f;
+    const long win = sparse_winner(pv, Wb, v, u, ys_lo, ys_hi, sx, isx, isy, Ws);
+    float2 f = make_float2(0.f, 0.f);
+    if (win >= 0) f = *(const float2*)(pf + win * 2);
+    flow_pixel(f.x, f.y, win >= 0, isx, isy, hflip, vflip, fl + 2 * k, va + k);
   }
 
   const long px = ((long)n * h + y) * w + x4;   // first output pixel of the run

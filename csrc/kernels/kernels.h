@@ -323,6 +323,16 @@ int jr_augment_sparse_sums(const void* img1, const void* img2, const int* params
 int jr_augment_sparse(const void* img1, const void* img2, const float* flow, const void* valid_in, const int* params,
                       const int* sums, float* out1, float* out2, float* out_flow, float* valid, int B, int Hb, int Wb,
                       int h, int w, hipStream_t stream);
+// Dense and sparse samples in one batch (augment_mixed.hip; train/augment.py:augment_pairs_mixed, bitwise).
+// Packed slots: img1 / img2 uint8 [B][S][3], flow fp32 [B][S][2], valid_in uint8 [B][S], sample n in the first
+// Hs * Ws pixels of slot n with row pitch Ws.  params int32 [B][52]: the sparse record, word 18 = 1 for a
+// dense sample (four-tap flow blend, valid_in not read) and 0 for a sparse one; the kernels clamp Hs * Ws
+// into the slot.  S * 255.5 must fit an int32.  sums and the outputs as jr_augment_sparse's.
+int jr_augment_mixed_sums(const void* img1, const void* img2, const int* params, int B, long S, int* sums,
+                          hipStream_t stream);
+int jr_augment_mixed(const void* img1, const void* img2, const float* flow, const void* valid_in, const int* params,
+                     const int* sums, float* out1, float* out2, float* out_flow, float* valid, int B, long S, int h, int w,
+                     hipStream_t stream);
 // Conv of a 2-channel input (the flow branch's 7x7 / 3x3): x bf16 NHWC
 // [N][H][W][x_cstride] (channels 0, 1 used), stride 1, output H x W; w bf16
 // MFMA A fragments [cout/16][NKC][64 lanes][8] (jax_raft_amd/ops/native.py:

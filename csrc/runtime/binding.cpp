@@ -1837,6 +1837,49 @@ static Launch make_augment_sparse(const TList& t, const IList& i, std::vector<at
   };
 }
 
+// ---- dense and sparse samples in one batch (kernels augment_mixed.hip): packed slots of S pixels, i.e.
+// frames [B][1][S] to the checks above
+// t = [img1, img2 (uint8 [B][S][3]), params (int32 [B][52]), sums], i = [B, S]
+static Launch make_augment_mixed_sums(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  at::Tensor a = opt(t, 0), b = opt(t, 1), params = opt(t, 2), sums = opt(t, 3);
+  const int64_t B = i[0], S = i[1];
+  check_augment_frames(a, b, B, 1, S, "augment_mixed_sums");
+  check_augment_records(params, B, 52, "augment_mixed_sums");
+  check_augment_sums(sums, B, "augment_mixed_sums");
+  for (const at::Tensor* in : {&a, &b, &params})
+    TORCH_CHECK(!augment_overlap(sums, *in), "augment_mixed_sums: sums aliases an input");
+  for (auto& v : {a, b, params, sums}) keep.push_back(v);
+  const void *ap = a.data_ptr(), *bp = b.data_ptr();
+  const int* pp = params.data_ptr<int>();
+  int* sp = sums.data_ptr<int>();
+  return [=](hipStream_t s, int) { return jr_augment_mixed_sums(ap, bp, pp, (int)B, (long)S, sp, s); };
+}
+// t = [img1, img2, flow (fp32 [B][S][2]), valid (uint8 [B][S]), params (int32 [B][52]), sums, out1, out2
+// (fp32 [B][h][w][3]), out_flow (fp32 [B][h][w][2]), out_valid (fp32 [B][h][w])], i = [B, S, h, w]
+static Launch make_augment_mixed(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  at::Tensor a = opt(t, 0), b = opt(t, 1), flow = opt(t, 2), vin = opt(t, 3), params = opt(t, 4), sums = opt(t, 5);
+  at::Tensor o1 = opt(t, 6), o2 = opt(t, 7), of = opt(t, 8), ov = opt(t, 9);
+  const int64_t B = i[0], S = i[1], h = i[2], w = i[3];
+  check_augment_frames(a, b, B, 1, S, "augment_mixed");
+  check_augment_sums(sums, B, "augment_mixed");
+  TORCH_CHECK(h >= 1 && w >= 1 && h <= 65535 * 4 && h * w <= 0x3fffffff, "augment_mixed: crop size");
+  check_f32(flow, "augment_mixed: flow");
+  TORCH_CHECK(flow.numel() == B * S * 2 && reinterpret_cast<uintptr_t>(flow.data_ptr()) % 16 == 0,
+              "augment_mixed: flow [B][S][2], 16-byte aligned");
+  TORCH_CHECK(vin.defined() && vin.is_cuda() && vin.scalar_type() == at::kByte && vin.is_contiguous() &&
+                  vin.numel() == B * S, "augment_mixed: valid must be a contiguous device uint8 [B][S]");
+  check_augment_records(params, B, 52, "augment_mixed");
+  check_augment_outputs("augment_mixed", {&o1, &o2, &of, &ov}, {&a, &b, &flow, &vin, &params, &sums}, B, h, w);
+  for (auto& v : {a, b, flow, vin, params, sums, o1, o2, of, ov}) keep.push_back(v);
+  const void *ap = a.data_ptr(), *bp = b.data_ptr(), *vp = vin.data_ptr();
+  const float* fp = flow.data_ptr<float>();
+  const int *pp = params.data_ptr<int>(), *sp = sums.data_ptr<int>();
+  float *p1 = o1.data_ptr<float>(), *p2 = o2.data_ptr<float>(), *pf = of.data_ptr<float>(), *pv = ov.data_ptr<float>();
+  return [=](hipStream_t s, int) {
+    return jr_augment_mixed(ap, bp, fp, vp, pp, sp, p1, p2, pf, pv, (int)B, (long)S, (int)h, (int)w, s);
+  };
+}
+
 // ------------------------------------------------------------- sequence loss
 // t = [pred (fp32 [N][P][2]), gt (fp32 [P][2]), valid? (fp32 [P]), part (fp32 [blocks][37])], i = [P, N]
 void seq_loss_op(const TList& t, IList i, double max_flow) {
@@ -2005,6 +2048,8 @@ static const std::vector<OpRow>& op_table() {
       row_ti("augment", 5, 5, make_augment),
       row_ti("augment_sparse_sums", 3, 3, make_augment_sparse_sums),
       row_ti("augment_sparse", 5, 5, make_augment_sparse),
+      row_ti("augment_mixed_sums", 2, 2, make_augment_mixed_sums),
+      row_ti("augment_mixed", 4, 4, make_augment_mixed),
       // fp32 parity mode
       row_tia("conv_f32", "alpha", 22, 22, make_conv_f32),
       row_ti("stats_f32", 3, 3, make_stats_f32),

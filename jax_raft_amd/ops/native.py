@@ -720,6 +720,53 @@ def augment_pairs_sparse(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: tor
     return out1, out2, oflow, valid
 
 
+def augment_sums_mixed(img1_u8: torch.Tensor, img2_u8: torch.Tensor, rec: torch.Tensor,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Exact per-channel integer sums of each sample's packed pixels in two batches of (B, S, 3) uint8
+    GPU slots -> int32 (2, B, 3); ``rec``: the packed mixed records on the device."""
+    B, S, _ = img1_u8.shape
+    if out is None:
+        out = torch.empty((2, B, 3), dtype=torch.int32, device=img1_u8.device)
+    ops().augment_mixed_sums([img1_u8, img2_u8, rec, out], [B, S])
+    return out
+
+
+def augment_pairs_mixed(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tensor, valid_u8: torch.Tensor,
+                        params, crop: Tuple[int, int]):
+    """The augmentation of a batch of dense and sparse samples (RAFT's Sintel stage) in packed slots --
+    (B, S, 3) uint8 x 2, (B, S, 2) fp32, (B, S) uint8, sample n in the first Hs * Ws pixels of slot n --
+    -> ``(image1, image2, flow, valid)`` at the crop size: ``train/augment.py:augment_pairs_mixed``
+    itself on CPU tensors, the HIP kernels of ``augment_mixed.hip`` (bitwise equal; two launches and the
+    upload of the records, no host synchronisation) on GPU tensors.  ``params``: the batch's
+    :class:`~jax_raft_amd.train.augment.MixedAugmentParams`, validated here on the host before
+    anything is uploaded or launched."""
+    from ..train import augment as A
+
+    if not img1_u8.is_cuda:
+        return A.augment_pairs_mixed(img1_u8, img2_u8, flow, valid_u8, params, crop)
+    if (img1_u8.ndim != 3 or img1_u8.shape[-1] != 3 or img1_u8.shape != img2_u8.shape
+            or img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8):
+        raise ValueError("augment_pairs_mixed: images must be (B, S, 3) uint8 of one size")
+    B, S, _ = img1_u8.shape
+    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, S, 2):
+        raise ValueError(f"augment_pairs_mixed: flow must be ({B}, {S}, 2) fp32, got {tuple(flow.shape)} {flow.dtype}")
+    if valid_u8.dtype != torch.uint8 or tuple(valid_u8.shape) != (B, S):
+        raise ValueError(f"augment_pairs_mixed: valid must be ({B}, {S}) uint8, got {tuple(valid_u8.shape)} {valid_u8.dtype}")
+    if not isinstance(params, A.MixedAugmentParams) or len(params) != B:
+        raise ValueError(f"augment_pairs_mixed: MixedAugmentParams for a batch of {B} wanted")
+    h, w = int(crop[0]), int(crop[1])
+    params.validate(S, (h, w))
+    dev = img1_u8.device
+    rec = params.packed(pin=True).to(dev, non_blocking=True)
+    sums = augment_sums_mixed(img1_u8, img2_u8, rec)
+    out1 = torch.empty((B, h, w, 3), dtype=torch.float32, device=dev)
+    out2 = torch.empty_like(out1)
+    oflow = torch.empty((B, h, w, 2), dtype=torch.float32, device=dev)
+    valid = torch.empty((B, h, w), dtype=torch.float32, device=dev)
+    ops().augment_mixed([img1_u8, img2_u8, flow, valid_u8, rec, sums, out1, out2, oflow, valid], [B, S, h, w])
+    return out1, out2, oflow, valid
+
+
 def conv2d(spec: ConvSpec, x: torch.Tensor, act: int = ACT_NONE, out_dtype=torch.bfloat16, alpha: float = 1.0,
            res: Optional[torch.Tensor] = None, res_post: int = 0, cfg: Optional[int] = None) -> torch.Tensor:
     """Eager NHWC conv of a contiguous bf16 tensor [N, H, W, C] (C == cin8)."""

@@ -1,7 +1,9 @@
 """Training: the fused native step, the sequence loss, data (synthetic, and real datasets with
 the fused GPU augmentation) and the data-parallel trainer."""
-from .augment import AugmentParams, SparseAugmentParams, augment_pairs, augment_pairs_sparse, sample_sparse
-from .datasets import FlowPairs, PairLoader, SparseFlowPairs
+from .augment import (AugmentParams, MixedAugmentParams, SparseAugmentParams, augment_pairs, augment_pairs_mixed,
+                      augment_pairs_sparse, sample_mixed, sample_sparse)
+from .datasets import FlowPairs, MixedFlowPairs, PairLoader, SparseFlowPairs
 
 __all__ = ("augment_pairs", "AugmentParams", "FlowPairs", "PairLoader", "augment_pairs_sparse", "SparseAugmentParams",
-           "sample_sparse", "SparseFlowPairs")
+           "sample_sparse", "SparseFlowPairs", "MixedFlowPairs", "MixedAugmentParams", "sample_mixed",
+           "augment_pairs_mixed")

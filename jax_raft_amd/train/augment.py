@@ -91,6 +91,60 @@ def _colour_words(colour) -> np.ndarray:
     return np.concatenate([np.array([b, k, s], dtype=np.float32), hue_matrix(float(theta)).reshape(9)])
 
 
+def _draw_dense(g, st: Stage, src, h: int, w: int, augment: bool):
+    """The draws of one dense sample from generator ``g``, in RAFT's order: the arguments of
+    ``AugmentParams.record`` after ``src``."""
+    Hs, Ws = src
+    sx = sy = 1.0
+    if augment and g.random() < 0.8:            # spatial augmentation
+        floor_ = max((h + 8) / Hs, (w + 8) / Ws)
+        sx = sy = 2.0 ** g.uniform(st.min_scale, st.max_scale)
+        if g.random() < 0.8:                    # stretch
+            sx *= 2.0 ** g.uniform(-0.2, 0.2)
+            sy *= 2.0 ** g.uniform(-0.2, 0.2)
+        sx, sy = max(sx, floor_), max(sy, floor_)
+    Hr, Wr = max(h, int(round(Hs * sy))), max(w, int(round(Ws * sx)))
+    hflip = bool(augment and g.random() < 0.5)
+    vflip = bool(augment and g.random() < 0.1)
+    y0, x0 = int(g.integers(0, Hr - h + 1)), int(g.integers(0, Wr - w + 1))
+    c1 = c2 = None
+    rects = []
+    if augment:
+        def colour():
+            b, k, s = g.uniform(0.6, 1.4, 3)
+            return float(b), float(k), float(s), 2.0 * math.pi * g.uniform(-0.5 / 3.14, 0.5 / 3.14)
+        c1 = colour()
+        c2 = colour() if g.random() < 0.2 else c1          # asymmetric
+        if g.random() < 0.5:                               # eraser
+            for _ in range(int(g.integers(1, 3))):
+                rx, ry = int(g.integers(0, Ws)), int(g.integers(0, Hs))
+                dx, dy = int(g.integers(50, 101)), int(g.integers(50, 101))
+                rects.append((rx, ry, rx + dx, ry + dy))
+    return (Hr, Wr), (y0, x0), hflip, vflip, c1, c2, rects
+
+
+def _draw_sparse(g, st: Stage, p_hflip: float, src, h: int, w: int, augment: bool):
+    """The draws of one sparse sample (``sample_sparse``), as :func:`_draw_dense` returns them."""
+    Hs, Ws = src
+    scale = 1.0
+    if augment and g.random() < 0.8:                # spatial augmentation
+        scale = max(2.0 ** g.uniform(st.min_scale, st.max_scale), (h + 1) / Hs, (w + 1) / Ws)
+    Hr, Wr = max(h, int(round(Hs * scale))), max(w, int(round(Ws * scale)))
+    hflip = bool(augment and g.random() < p_hflip)
+    y0 = int(np.clip(g.integers(0, Hr - h + 20), 0, Hr - h))
+    x0 = int(np.clip(g.integers(-50, Wr - w + 50), 0, Wr - w))
+    colour, rects = None, []
+    if augment:
+        b, k, s = g.uniform(0.6, 1.4, 3)
+        colour = (float(b), float(k), float(s), 2.0 * math.pi * g.uniform(-0.5 / 3.14, 0.5 / 3.14))
+        if g.random() < 0.5:                        # eraser
+            for _ in range(int(g.integers(1, 3))):
+                rx, ry = int(g.integers(0, Ws)), int(g.integers(0, Hs))
+                dx, dy = int(g.integers(50, 101)), int(g.integers(50, 101))
+                rects.append((rx, ry, rx + dx, ry + dy))
+    return (Hr, Wr), (y0, x0), hflip, False, colour, colour, rects
+
+
 class AugmentParams:
     """The records of one batch, on the host: ``ints`` (B, 16) int32 and ``floats`` (B, 32) fp32."""
 
@@ -149,36 +203,8 @@ class AugmentParams:
         Hs, Ws = src
         if Hs < h or Ws < w:
             raise ValueError(f"source {Hs}x{Ws} is smaller than the crop {h}x{w}")
-        out = []
-        for n in range(batch):
-            g = np.random.default_rng([int(seed), int(step), int(rank), n])
-            sx = sy = 1.0
-            if augment and g.random() < 0.8:            # spatial augmentation
-                floor_ = max((h + 8) / Hs, (w + 8) / Ws)
-                sx = sy = 2.0 ** g.uniform(st.min_scale, st.max_scale)
-                if g.random() < 0.8:                    # stretch
-                    sx *= 2.0 ** g.uniform(-0.2, 0.2)
-                    sy *= 2.0 ** g.uniform(-0.2, 0.2)
-                sx, sy = max(sx, floor_), max(sy, floor_)
-            Hr, Wr = max(h, int(round(Hs * sy))), max(w, int(round(Ws * sx)))
-            hflip = bool(augment and g.random() < 0.5)
-            vflip = bool(augment and g.random() < 0.1)
-            y0, x0 = int(g.integers(0, Hr - h + 1)), int(g.integers(0, Wr - w + 1))
-            c1 = c2 = None
-            rects = []
-            if augment:
-                def colour():
-                    b, k, s = g.uniform(0.6, 1.4, 3)
-                    return float(b), float(k), float(s), 2.0 * math.pi * g.uniform(-0.5 / 3.14, 0.5 / 3.14)
-                c1 = colour()
-                c2 = colour() if g.random() < 0.2 else c1          # asymmetric
-                if g.random() < 0.5:                               # eraser
-                    for _ in range(int(g.integers(1, 3))):
-                        rx, ry = int(g.integers(0, Ws)), int(g.integers(0, Hs))
-                        dx, dy = int(g.integers(50, 101)), int(g.integers(50, 101))
-                        rects.append((rx, ry, rx + dx, ry + dy))
-            out.append(cls.record(src, (Hr, Wr), (y0, x0), hflip, vflip, c1, c2, rects))
-        return cls.cat(out)
+        return cls.cat([AugmentParams.record(src, *_draw_dense(np.random.default_rng([int(seed), int(step), int(rank), n]),
+                                                               st, src, h, w, augment)) for n in range(batch)])
 
     # -------------------------------------------------------------- validation
     def validate(self, src: Tuple[int, int], crop: Tuple[int, int]) -> None:
@@ -437,23 +463,7 @@ def sample_sparse(batch: int, sizes: Sequence[Tuple[int, int]], stage: str = "ki
         if Hs < h or Ws < w:
             raise ValueError(f"source {Hs}x{Ws} is smaller than the crop {h}x{w}")
         g = np.random.default_rng([int(seed), int(step), int(rank), n])
-        scale = 1.0
-        if augment and g.random() < 0.8:                # spatial augmentation
-            scale = max(2.0 ** g.uniform(st.min_scale, st.max_scale), (h + 1) / Hs, (w + 1) / Ws)
-        Hr, Wr = max(h, int(round(Hs * scale))), max(w, int(round(Ws * scale)))
-        hflip = bool(augment and g.random() < _SPARSE_HFLIP[stage])
-        y0 = int(np.clip(g.integers(0, Hr - h + 20), 0, Hr - h))
-        x0 = int(np.clip(g.integers(-50, Wr - w + 50), 0, Wr - w))
-        colour, rects = None, []
-        if augment:
-            b, k, s = g.uniform(0.6, 1.4, 3)
-            colour = (float(b), float(k), float(s), 2.0 * math.pi * g.uniform(-0.5 / 3.14, 0.5 / 3.14))
-            if g.random() < 0.5:                        # eraser
-                for _ in range(int(g.integers(1, 3))):
-                    rx, ry = int(g.integers(0, Ws)), int(g.integers(0, Hs))
-                    dx, dy = int(g.integers(50, 101)), int(g.integers(50, 101))
-                    rects.append((rx, ry, rx + dx, ry + dy))
-        out.append(SparseAugmentParams.record((Hs, Ws), (Hr, Wr), (y0, x0), hflip, False, colour, colour, rects))
+        out.append(SparseAugmentParams.record((Hs, Ws), *_draw_sparse(g, st, _SPARSE_HFLIP[stage], (Hs, Ws), h, w, augment)))
     return SparseAugmentParams.cat(out)
 
 
@@ -537,3 +547,119 @@ def augment_pairs_sparse(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: tor
             dropped.append(int((on & (X == Wr)).sum()))
     res = tuple(torch.stack([o[k] for o in outs]).contiguous() for k in range(4))
     return res + (torch.stack(landers), dropped) if return_landers else res
+
+
+# ------------------------------------------- dense and sparse samples in one batch
+# RAFT's Sintel stage draws dense lists (Sintel, FlyingThings) and sparse ones (KITTI, HD1K) into the
+# same batches.  The samples sit in PACKED SLOTS: buffers (B, S, ...) with S the largest Hs * Ws, sample
+# n in the first Hs * Ws pixels of slot n with row pitch Ws.  The record is the sparse one with one of
+# its spare words in use (csrc/kernels/augment_mixed.hip reads the same).
+I_DENSE = 18           # 1: dense ground truth (the four-tap blend), 0: sparse (the point-by-point move)
+
+
+class MixedAugmentParams(SparseAugmentParams):
+    """The records of a batch of dense and sparse samples: the sparse record's 52 words with
+    ``ints[I_DENSE]`` = 1 for a dense sample, 0 for a sparse one."""
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, MixedAugmentParams) and np.array_equal(self.ints, other.ints)
+                and np.array_equal(self.floats.view(np.int32), other.floats.view(np.int32)))
+
+    @property
+    def dense_flags(self):
+        return [bool(v) for v in self.ints[:, I_DENSE]]
+
+    @classmethod
+    def record(cls, src: Tuple[int, int], dense: bool, *args, **kw) -> "MixedAugmentParams":
+        """One record of a sample of size ``src``; after ``dense`` the arguments of ``AugmentParams.record``."""
+        one = SparseAugmentParams.record(src, *args, **kw)
+        one.ints[0, I_DENSE] = bool(dense)
+        return cls(one.ints, one.floats)
+
+    @classmethod
+    def identity(cls, sizes, dense_flags, origins=None) -> "MixedAugmentParams":
+        origins = origins or [(0, 0)] * len(sizes)
+        return cls.cat([cls.record(s, d, origin=o) for s, d, o in zip(sizes, dense_flags, origins)])
+
+    def part(self, n: int):
+        """Record ``n`` as the existing ops take it: ``AugmentParams`` of a dense sample,
+        ``SparseAugmentParams`` of a sparse one."""
+        if self.ints[n, I_DENSE]:
+            return AugmentParams(self.ints[n:n + 1, :N_INTS], self.floats[n:n + 1])
+        ints = self.ints[n:n + 1].copy()
+        ints[0, I_DENSE] = 0
+        return SparseAugmentParams(ints, self.floats[n:n + 1])
+
+    def validate(self, slot_pixels: int, crop: Tuple[int, int]) -> None:
+        """Every record against its own (Hs, Ws) as the dense check does, plus: ``Hs * Ws`` fits the
+        slot, the flag is 0 or 1, and a sparse record shrinks no axis by more than :data:`MAX_RATIO`."""
+        for n in range(len(self)):
+            Hs, Ws, flag = (int(v) for v in self.ints[n, [I_HS, I_WS, I_DENSE]])
+            if flag not in (0, 1):
+                raise ValueError(f"augment: record {n}: the dense flag must be 0 or 1, got {flag}")
+            if Hs < 1 or Ws < 1 or Hs * Ws > slot_pixels:
+                raise ValueError(f"augment: record {n}: the sample {Hs}x{Ws} does not fit a slot of {slot_pixels} pixels")
+            try:
+                one = self.part(n)
+                one.validate((Hs, Ws), crop)       # dense: the dense check; sparse: that plus MAX_RATIO
+            except ValueError as e:
+                raise ValueError(str(e).replace("record 0", f"record {n}")) from None
+
+
+def sample_mixed(batch: int, sizes: Sequence[Tuple[int, int]], dense_flags: Sequence[bool], stage: str = "sintel",
+                 crop: Optional[Tuple[int, int]] = None, seed: int = 0, step: int = 0, rank: int = 0,
+                 augment: bool = True) -> MixedAugmentParams:
+    """``batch`` records for a mixed batch, a pure function of its arguments.  Sample ``n`` is drawn
+    from ``default_rng([seed, step, rank, n])``: a dense one with exactly the draws of
+    ``AugmentParams.sample`` (stretch, v-flip, asymmetric colour; ``STAGES[stage]``), a sparse one with
+    exactly those of :func:`sample_sparse` (``SPARSE_STAGES[stage]``), so an all-dense or all-sparse
+    batch has the existing samplers' records word for word.  ``stage`` must be in both tables."""
+    if stage not in STAGES or stage not in SPARSE_STAGES:
+        raise ValueError(f"unknown mixed augmentation stage {stage!r} (one of {sorted(set(STAGES) & set(SPARSE_STAGES))})")
+    if len(sizes) != batch or len(dense_flags) != batch:
+        raise ValueError(f"sample_mixed: {len(sizes)} sizes and {len(dense_flags)} flags for a batch of {batch}")
+    h, w = crop or STAGES[stage].crop
+    out = []
+    for n, ((Hs, Ws), dense) in enumerate(zip(sizes, dense_flags)):
+        if Hs < h or Ws < w:
+            raise ValueError(f"source {Hs}x{Ws} is smaller than the crop {h}x{w}")
+        g = np.random.default_rng([int(seed), int(step), int(rank), n])
+        if dense:
+            draws = _draw_dense(g, STAGES[stage], (Hs, Ws), h, w, augment)
+        else:
+            draws = _draw_sparse(g, SPARSE_STAGES[stage], _SPARSE_HFLIP[stage], (Hs, Ws), h, w, augment)
+        out.append(MixedAugmentParams.record((Hs, Ws), dense, *draws))
+    return MixedAugmentParams.cat(out)
+
+
+@torch.no_grad()
+def augment_pairs_mixed(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tensor, valid_u8: torch.Tensor,
+                        params: MixedAugmentParams, crop: Tuple[int, int]):
+    """The golden op of a mixed batch on packed slots: (B, S, 3) uint8 x 2, (B, S, 2) fp32 flow,
+    (B, S) uint8 valid -> the outputs of :func:`augment_pairs`.  A composition, no arithmetic of its
+    own: the first ``Hs * Ws`` pixels of slot ``n``, reshaped to ``(1, Hs, Ws, .)``, go through
+    :func:`augment_pairs` if the record is dense (valid then follows the dense rule, and the slot's
+    valid bytes are not read) or through :func:`augment_pairs_sparse` if it is sparse; the outputs
+    are stacked.  Nothing past ``Hs * Ws`` in a slot is read."""
+    if (img1_u8.ndim != 3 or img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8
+            or img1_u8.shape != img2_u8.shape or img1_u8.shape[-1] != 3):
+        raise ValueError("augment_pairs_mixed: images must be (B, S, 3) uint8 of one size")
+    B, S, _ = img1_u8.shape
+    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, S, 2):
+        raise ValueError("augment_pairs_mixed: flow must be (B, S, 2) fp32")
+    if valid_u8.dtype != torch.uint8 or tuple(valid_u8.shape) != (B, S):
+        raise ValueError("augment_pairs_mixed: valid must be (B, S) uint8")
+    if not isinstance(params, MixedAugmentParams) or len(params) != B:
+        raise ValueError(f"augment_pairs_mixed: MixedAugmentParams for a batch of {B} wanted")
+    crop = (int(crop[0]), int(crop[1]))
+    params.validate(S, crop)
+    outs = []
+    for n, (Hs, Ws) in enumerate(params.sizes):
+        N = Hs * Ws
+        a, b, f = (t[n, :N].reshape(1, Hs, Ws, -1) for t in (img1_u8, img2_u8, flow))
+        one = params.part(n)
+        if params.ints[n, I_DENSE]:
+            outs.append(augment_pairs(a, b, f, one, crop))
+        else:
+            outs.append(augment_pairs_sparse(a, b, f, valid_u8[n, :N].reshape(1, Hs, Ws), one, crop))
+    return tuple(torch.cat([o[k] for o in outs]).contiguous() for k in range(4))

@@ -13,8 +13,13 @@ sizes.  The loader then stages every sample in the top-left corner of buffers of
 size, adds a uint8 valid plane and the list of sizes, and the device op is
 ``ops/native.py:augment_pairs_sparse``.
 
-Not covered (``NotImplementedError`` or absent): mixed-dataset sampling for the Sintel stage,
-dense and sparse samples in one batch, FlyingThings' ``.pfm`` flow.
+FlyingThings3D (:meth:`FlowPairs.things`) is a dense list whose flow is ``.pfm``.
+
+The Sintel stage of RAFT's schedule trains on a weighted mixture of dense and sparse lists:
+:class:`MixedFlowPairs` (``FlowPairs.open(root, "mix")``).  Over one the loader uses PACKED SLOTS:
+buffers ``(B, S, ...)`` with ``S`` the largest ``Hs * Ws`` of the list, sample ``n`` in the first
+``Hs * Ws`` pixels of slot ``n`` with row pitch ``Ws``; only that prefix is uploaded, and the device op is
+``ops/native.py:augment_pairs_mixed``.
 """
 from __future__ import annotations
 
@@ -30,7 +35,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ..utils.flow_io import png_size, read_flo, read_flow_png, read_image
+from ..utils.flow_io import png_size, read_flo, read_flow_png, read_image, read_pfm
 
 MAX_THREADS = 16
 _PPM_HEADER = re.compile(rb"P6\s+(\d+)\s+(\d+)\s+255\s")
@@ -61,6 +66,31 @@ def read_frame(path: str) -> np.ndarray:
                 if data.size == h * w * 3:
                     return data.reshape(h, w, 3)
     return read_image(path)
+
+
+def frame_size(path: str) -> Tuple[int, int]:
+    """(H, W) of an image file from its header: a PNG's IHDR, a binary PPM's first line; anything
+    else is decoded."""
+    if path.endswith(".png"):
+        return png_size(path)
+    if path.endswith(".ppm"):
+        with open(path, "rb") as f:
+            m = _PPM_HEADER.match(f.read(32))
+        if m is not None:
+            return int(m.group(2)), int(m.group(1))
+    return tuple(read_frame(path).shape[:2])
+
+
+class ThingsLayoutNotFound(FileNotFoundError, NotImplementedError):
+    """``root`` does not hold the FlyingThings3D layout.  A ``FileNotFoundError``; also a
+    ``NotImplementedError``, which ``FlowPairs.open`` raised for ``things`` whatever the root held
+    while ``.pfm`` had no reader, so callers that catch that keep working."""
+
+
+# RAFT's Sintel-stage mixture, and the directory of each part under the mixture's root
+MIX_DEFAULT = (("sintel-clean", 100), ("sintel-final", 100), ("kitti", 200), ("hd1k", 5), ("things-clean", 1))
+MIX_DIRS = {"sintel-clean": "Sintel", "sintel-final": "Sintel", "kitti": "KITTI", "hd1k": "HD1K",
+            "things-clean": "FlyingThings3D", "things-final": "FlyingThings3D", "things": "FlyingThings3D"}
 
 
 class SparseLayoutNotFound(FileNotFoundError, NotImplementedError):
@@ -104,7 +134,51 @@ class FlowPairs:
         return cls([(a, b, f) for (a, b), f in zip(ds.image_list, ds.flow_list)])
 
     @classmethod
-    def open(cls, root: str, dataset: str = "chairs") -> "FlowPairs":
+    def things(cls, root: str, dstype: str = "clean") -> "FlowPairs":
+        """FlyingThings3D's training split, left camera, RAFT's listing: the image directories
+        ``<pass>/TRAIN/*/*/left`` (``clean`` / ``final``: ``frames_cleanpass`` / ``frames_finalpass``) against the
+        flow directories ``optical_flow/TRAIN/*/*/{into_future,into_past}/left``; ``into_future`` pairs
+        ``(img[i], img[i+1], flow[i])`` and ``into_past`` pairs ``(img[i+1], img[i], flow[i+1])``."""
+        frames = {"clean": "frames_cleanpass", "final": "frames_finalpass"}.get(dstype, dstype)
+        image_dirs = sorted(osp.join(d, "left") for d in glob(osp.join(root, frames, "TRAIN", "*", "*")))
+        if not image_dirs:
+            raise ThingsLayoutNotFound(f"no {frames}/TRAIN/*/* under {root}")
+        scenes = sorted(glob(osp.join(root, "optical_flow", "TRAIN", "*", "*")))
+        if len(scenes) != len(image_dirs):
+            raise FileNotFoundError(f"{root}: {len(image_dirs)} scenes under {frames}/TRAIN, {len(scenes)} under optical_flow/TRAIN")
+        items = []
+        for direction in ("into_future", "into_past"):
+            for idir, scene in zip(image_dirs, scenes):
+                images = sorted(glob(osp.join(idir, "*.png")))
+                flows = sorted(glob(osp.join(scene, direction, "left", "*.pfm")))
+                if len(images) != len(flows):
+                    raise FileNotFoundError(f"{osp.join(scene, direction, 'left')}: {len(flows)} flows for {len(images)} frames of {idir}")
+                for i in range(len(flows) - 1):
+                    if direction == "into_future":
+                        items.append((images[i], images[i + 1], flows[i]))
+                    else:
+                        items.append((images[i + 1], images[i], flows[i + 1]))
+        return cls(items)
+
+    @classmethod
+    def open(cls, root: str, dataset: str = "chairs", parts=None):
+        """The list of ``dataset`` under ``root``.  ``mix``: RAFT's Sintel-stage mixture, ``parts`` a
+        sequence of names or ``(name, weight)`` (default :data:`MIX_DEFAULT`), each part in its
+        directory ``Sintel``, ``KITTI``, ``HD1K`` or ``FlyingThings3D`` under ``root``; a named part
+        whose directory is missing is a ``FileNotFoundError``."""
+        if dataset == "mix":
+            named = [(p, 1) if isinstance(p, str) else (p[0], int(p[1])) for p in (parts or MIX_DEFAULT)]
+            opened = []
+            for name, weight in named:
+                if name not in MIX_DIRS:
+                    raise ValueError(f"unknown part {name!r} of a mixture (one of {sorted(MIX_DIRS)})")
+                d = osp.join(root, MIX_DIRS[name])
+                if not osp.isdir(d):
+                    raise FileNotFoundError(f"{d}: the directory of part {name!r} is missing")
+                opened.append((cls.open(d, name), weight))
+            return MixedFlowPairs(opened)
+        if parts is not None:
+            raise ValueError("FlowPairs.open: parts belong to dataset 'mix'")
         if dataset == "chairs":
             return cls.chairs(root)
         if dataset in ("sintel-clean", "sintel-final"):
@@ -113,9 +187,12 @@ class FlowPairs:
             return cls.kitti(root)
         if dataset == "hd1k":
             return cls.hd1k(root)
-        if dataset == "things":
-            raise NotImplementedError(f"dataset {dataset!r}: the .pfm flow reader is not implemented")
-        raise ValueError(f"unknown dataset {dataset!r} (chairs, sintel-clean, sintel-final, kitti, hd1k)")
+        if dataset == "things":                      # both passes, as RAFT's things stage uses them
+            return cls(cls.things(root, "clean").items + cls.things(root, "final").items)
+        if dataset in ("things-clean", "things-final"):
+            return cls.things(root, dataset.split("-")[1])
+        raise ValueError(f"unknown dataset {dataset!r} (chairs, sintel-clean, sintel-final, kitti, hd1k, things, "
+                         "things-clean, things-final, mix)")
 
     @classmethod
     def kitti(cls, root: str) -> "SparseFlowPairs":
@@ -157,6 +234,8 @@ class FlowPairs:
 
     def __getitem__(self, i: int):
         a, b, f = self.items[i]
+        if f.endswith(".pfm"):                      # a view of the file's bytes: the caller's copy is the only one
+            return read_frame(a), read_frame(b), read_pfm(f)[..., :2]
         try:
             flow = read_flo(f)
         except (ValueError, IndexError) as e:   # a truncated file: short header or short data
@@ -182,6 +261,67 @@ class SparseFlowPairs(FlowPairs):
         return [png_size(a) for a, _, _ in self.items]
 
 
+class MixedFlowPairs:
+    """A weighted mixture of lists, dense and sparse: ``parts`` is a sequence of ``(FlowPairs |
+    SparseFlowPairs, weight)``.  The index space is the concatenation of every part repeated
+    ``weight`` times -- ``len`` is the sum of ``weight * len(part)`` -- and item ``i`` maps to
+    ``(part, i mod len(part))`` inside its part's stretch; nothing is materialised.  Per item:
+    ``dense(i)`` and ``size(i)`` = (Hs, Ws), read from the files' headers once per part here.  A dense
+    part has one frame size (another is a ``ValueError`` naming the file); a sparse part may have several."""
+
+    mixed = True
+
+    def __init__(self, parts):
+        self.parts = [(p, int(w)) for p, w in parts]
+        if not self.parts:
+            raise ValueError("MixedFlowPairs: no parts")
+        self._ends, self._sizes, total = [], [], 0
+        for part, weight in self.parts:
+            if weight < 1:
+                raise ValueError(f"MixedFlowPairs: weight {weight} (a positive integer wanted)")
+            sizes = [frame_size(t[0]) for t in part.items]
+            if not getattr(part, "sparse", False):
+                for t, s in zip(part.items, sizes):
+                    if s != sizes[0]:
+                        raise ValueError(f"{t[0]}: frame size {s} differs from the part's {sizes[0]} "
+                                         "(a dense part has one frame size)")
+                sizes = sizes[:1]
+            self._sizes.append(sizes)
+            total += weight * len(part)
+            self._ends.append(total)
+        self.slot_pixels = max(h * w for sizes in self._sizes for h, w in sizes)
+
+    def __len__(self) -> int:
+        return self._ends[-1]
+
+    def locate(self, i: int) -> Tuple[int, int]:
+        """Item ``i`` -> (index of its part, index inside the part)."""
+        i = int(i)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        k = int(np.searchsorted(self._ends, i, side="right"))
+        return k, (i - (self._ends[k - 1] if k else 0)) % len(self.parts[k][0])
+
+    def dense(self, i: int) -> bool:
+        return not getattr(self.parts[self.locate(i)[0]][0], "sparse", False)
+
+    def size(self, i: int) -> Tuple[int, int]:
+        k, j = self.locate(i)
+        return self._sizes[k][j if len(self._sizes[k]) > 1 else 0]
+
+    def paths(self, i: int) -> Tuple[str, str, str]:
+        k, j = self.locate(i)
+        return self.parts[k][0].items[j]
+
+    def sizes(self) -> List[Tuple[int, int]]:
+        """Every frame size that occurs (not one per item)."""
+        return sorted({s for sizes in self._sizes for s in sizes})
+
+    def __getitem__(self, i: int):
+        k, j = self.locate(i)
+        return self.parts[k][0][j]
+
+
 class PairLoader:
     """Batches of raw frames, a pure function of the step.
 
@@ -198,6 +338,13 @@ class PairLoader:
     every sample in the top-left corner, and ``fetch`` returns ``(image1, image2, flow, valid uint8
     (B, Hmax, Wmax), sizes)``, ``sizes`` a host-side list of (Hs, Ws).  The bytes outside a
     sample's own region are whatever an earlier batch left there: nothing may depend on them.
+
+    Over a :class:`MixedFlowPairs` the slots are packed: buffers ``(B, S, 3)`` uint8 x 2, ``(B, S, 2)``
+    fp32 and ``(B, S)`` uint8 with ``S = slot_pixels``, the largest ``Hs * Ws`` of the list; sample
+    ``n`` is the first ``Hs * Ws`` pixels of slot ``n`` with row pitch ``Ws``.  ``fetch`` uploads only
+    those prefixes (the valid prefix of sparse samples only), returns ``(image1, image2, flow, valid,
+    sizes, dense_flags)`` and leaves the bytes it queued in ``last_upload_bytes``.  A dense sample's
+    valid bytes and everything past a prefix are unspecified.
     """
 
     def __init__(self, dataset: FlowPairs, batch: int, seed: int = 0, rank: int = 0, world: int = 1,
@@ -208,7 +355,15 @@ class PairLoader:
         if self.steps_per_epoch < 1:
             raise ValueError(f"{len(dataset)} pairs do not fill one batch of {self.batch} on {self.world} rank(s)")
         self.sparse = bool(getattr(dataset, "sparse", False))
-        if self.sparse:
+        self.mixed = bool(getattr(dataset, "mixed", False))
+        self.last_upload_bytes = 0
+        if self.mixed:
+            sizes = dataset.sizes()
+            self.slot_pixels = dataset.slot_pixels
+            self.frame_max = (max(s[0] for s in sizes), max(s[1] for s in sizes))
+            self.frame_min = (min(s[0] for s in sizes), min(s[1] for s in sizes))
+            self.frame = None                      # there is no one frame: the slots are packed
+        elif self.sparse:
             self._sizes = dataset.sizes()
             self.frame_max = (max(s[0] for s in self._sizes), max(s[1] for s in self._sizes))
             self.frame_min = (min(s[0] for s in self._sizes), min(s[1] for s in self._sizes))
@@ -238,6 +393,11 @@ class PairLoader:
 
     # ----------------------------------------------------------------- decode
     def _staging(self, slot: int):
+        if self._slots[slot] is None and self.mixed:
+            B, S = self.batch, self.slot_pixels
+            mk = lambda shape, dt: torch.empty(shape, dtype=dt, pin_memory=self._pin)
+            self._slots[slot] = (mk((B, S, 3), torch.uint8), mk((B, S, 3), torch.uint8), mk((B, S, 2), torch.float32),
+                                 mk((B, S), torch.uint8))
         if self._slots[slot] is None:
             H, W = self.frame
             mk = lambda shape, dt: torch.empty(shape, dtype=dt, pin_memory=self._pin)
@@ -248,6 +408,16 @@ class PairLoader:
         return self._slots[slot]
 
     def _decode_one(self, bufs, n: int, index: int) -> None:
+        if self.mixed:
+            arrs = self.ds[index]                  # 3 arrays of a dense item, 4 of a sparse one
+            Hs, Ws = self.ds.size(index)
+            paths = self.ds.paths(index)
+            for arr, path in zip(arrs, paths + (paths[2],)):
+                if tuple(arr.shape[:2]) != (Hs, Ws):
+                    raise ValueError(f"{path}: size {tuple(arr.shape[:2])} differs from the frame size {(Hs, Ws)} of its list")
+            for buf, arr in zip(bufs, arrs):       # the slot's prefix, row pitch Ws; the rest stays as it is
+                np.copyto(buf[n].numpy()[:Hs * Ws].reshape((Hs, Ws) + arr.shape[2:]), arr)
+            return
         if self.sparse:
             arrs = self.ds[index]
             Hs, Ws = self._sizes[index]
@@ -295,9 +465,35 @@ class PairLoader:
 
     def sizes_for(self, step: int) -> List[Tuple[int, int]]:
         """(Hs, Ws) of every sample of ``step`` (all ``frame`` for a dense list)."""
+        if self.mixed:
+            return [self.ds.size(i) for i in self.indices_for(step)]
         return [self._sizes[i] if self.sparse else self.frame for i in self.indices_for(step)]
 
+    def dense_for(self, step: int) -> List[bool]:
+        """Whether each sample of ``step`` has dense ground truth (a mixed list)."""
+        return [self.ds.dense(i) for i in self.indices_for(step)]
+
+    def _fetch_mixed(self, step: int):
+        bufs = self.host_batch(step)
+        sizes, dense = self.sizes_for(step), self.dense_for(step)
+        cuda = self.device.type == "cuda"
+        out = tuple(torch.empty(b.shape, dtype=b.dtype, device=self.device) for b in bufs)
+        queued = 0
+        for n, ((Hs, Ws), d) in enumerate(zip(sizes, dense)):
+            for dst, src in zip(out[:3 if d else 4], bufs):
+                dst[n, :Hs * Ws].copy_(src[n, :Hs * Ws], non_blocking=cuda)
+                queued += Hs * Ws * src[n, :1].numel() * src.element_size()
+        self.last_upload_bytes = queued
+        if cuda:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+            self._events[step % self.depth] = ev
+        self.prefetch(step + 1)
+        return out + (sizes, dense)
+
     def fetch(self, step: int):
+        if self.mixed:
+            return self._fetch_mixed(step)
         bufs = self.host_batch(step)
         if self.device.type == "cuda":
             out = tuple(torch.empty(b.shape, dtype=b.dtype, device=self.device).copy_(b, non_blocking=True) for b in bufs)

@@ -14,7 +14,11 @@ sintel-clean | sintel-final] [--stage chairs | things | sintel] [--no-augment]``
 the raw frames are uploaded as they are and cropped + augmented in one gather on the device
 (train/datasets.py, train/augment.py); every batch is a pure function of (seed, step, rank).
 ``--dataset kitti | hd1k`` (sparse ground truth, frames of several sizes) takes ``--stage kitti``
-(crop 288x960) or ``--stage sintel`` and the sparse augmentation op.
+(crop 288x960) or ``--stage sintel`` and the sparse augmentation op.  ``--dataset things --stage
+things`` is FlyingThings3D (both passes; ``things-clean`` / ``things-final``: one).  ``--dataset mix
+--stage sintel [--mix name[:weight],...]`` is RAFT's Sintel stage: dense and sparse lists drawn into
+the same batches (default ``sintel-clean:100,sintel-final:100,kitti:200,hd1k:5,things-clean:1``, each
+part in ``Sintel``, ``KITTI``, ``HD1K`` or ``FlyingThings3D`` under the root) through the mixed op.
 
 Checkpoints: ``<dir>/step_<n>.msgpack`` (Flax-format weights, loadable with
 ``raft_large(weights=...)``) + ``step_<n>.opt.pt`` (optimizer / scheduler
@@ -71,15 +75,28 @@ class TrainConfig:
     graph_warmup: int = 3          # eager steps before the capture (plan build, autotune, allocator warm-up)
     # Real data (train/datasets.py, train/augment.py).  data=None: SyntheticFlow, as ever.
     data: Optional[str] = None     # dataset root
-    dataset: str = "chairs"        # chairs | sintel-clean | sintel-final | kitti | hd1k (sparse ground truth)
+    # chairs | things[-clean | -final] | sintel-clean | sintel-final | kitti | hd1k (sparse ground truth) | mix
+    dataset: str = "chairs"
     # augmentation preset, dense: chairs | things | sintel, sparse: kitti | sintel; sets size when size is left at its default
     stage: str = "chairs"
     augment: bool = True           # False: identity records, i.e. a random crop + normalisation only
+    # dataset="mix" (RAFT's Sintel stage): the parts, each in its directory under data (Sintel, KITTI, HD1K,
+    # FlyingThings3D), and their integer weights; None: RAFT's (100, 100, 200, 5, 1 for the default parts)
+    mix: tuple = ("sintel-clean", "sintel-final", "kitti", "hd1k", "things-clean")
+    mix_weights: Optional[tuple] = None
 
     def __post_init__(self):
         if self.data is not None:
             from .augment import SPARSE_STAGES, STAGES
 
+            if self.dataset == "mix":
+                self.mix = tuple(self.mix)
+                if self.mix_weights is not None:
+                    self.mix_weights = tuple(int(v) for v in self.mix_weights)
+                    if len(self.mix_weights) != len(self.mix):
+                        raise ValueError(f"mix: {len(self.mix_weights)} weights for {len(self.mix)} parts")
+                if self.stage != "sintel":
+                    raise ValueError(f"dataset 'mix' is RAFT's Sintel stage: stage 'sintel' wanted, got {self.stage!r}")
             stages = SPARSE_STAGES if self.sparse else STAGES
             if self.stage not in stages:
                 raise ValueError(f"unknown stage {self.stage!r} for dataset {self.dataset!r} (one of {sorted(stages)})")
@@ -89,6 +106,14 @@ class TrainConfig:
     @property
     def sparse(self) -> bool:
         return self.dataset in ("kitti", "hd1k")
+
+    @property
+    def mix_parts(self):
+        """``[(name, weight)]`` of a mixture, as ``FlowPairs.open(..., "mix", parts=...)`` takes them."""
+        from .datasets import MIX_DEFAULT
+
+        weights = self.mix_weights or [dict(MIX_DEFAULT).get(n, 1) for n in self.mix]   # RAFT's weight of each part
+        return list(zip(self.mix, weights))
 
 
 def _adamw(params, cfg: TrainConfig, device, capturable: bool = False):
@@ -141,8 +166,9 @@ class Trainer:
         if cfg.data is not None:
             from .datasets import FlowPairs, PairLoader
 
-            self.loader = PairLoader(FlowPairs.open(cfg.data, cfg.dataset), cfg.batch, seed=cfg.seed, rank=self.rank,
-                                     world=self.world, device=self.device)
+            ds = (FlowPairs.open(cfg.data, "mix", parts=cfg.mix_parts) if cfg.dataset == "mix"
+                  else FlowPairs.open(cfg.data, cfg.dataset))
+            self.loader = PairLoader(ds, cfg.batch, seed=cfg.seed, rank=self.rank, world=self.world, device=self.device)
             if self.loader.frame_min[0] < cfg.size[0] or self.loader.frame_min[1] < cfg.size[1]:
                 raise ValueError(f"{cfg.data}: frames {self.loader.frame_min} are smaller than the crop {tuple(cfg.size)}")
         self.step = 0
@@ -286,9 +312,14 @@ class Trainer:
             # real data: the raw frames of this step, then crop + augmentation in one gather on the
             # device (the golden op on a CPU device); records and indices are functions of the step
             from ..ops import native as nat
-            from .augment import AugmentParams, sample_sparse
+            from .augment import AugmentParams, sample_mixed, sample_sparse
 
             crop = (int(cfg.size[0]), int(cfg.size[1]))
+            if self.loader.mixed:
+                img1, img2, flow, valid, sizes, dense = self.loader.fetch(step)
+                params = sample_mixed(cfg.batch, sizes, dense, cfg.stage, crop, seed=cfg.seed, step=step, rank=self.rank,
+                                      augment=cfg.augment)
+                return nat.augment_pairs_mixed(img1, img2, flow, valid, params, crop)
             if self.loader.sparse:
                 img1, img2, flow, valid, sizes = self.loader.fetch(step)
                 params = sample_sparse(cfg.batch, sizes, cfg.stage, crop, seed=cfg.seed, step=step, rank=self.rank,
@@ -357,11 +388,28 @@ class Trainer:
         self.skipped = int(st.get("skipped", 0))
 
 
+def config_from_args(a) -> TrainConfig:
+    kw = {k: (tuple(v) if k == "size" else v) for k, v in vars(a).items()}
+    mix = kw.pop("mix")
+    if mix is not None:                             # name[:weight],...
+        parts = [p.split(":") for p in mix.split(",") if p]
+        if not parts or any(len(p) > 2 or (len(p) == 2 and not p[1].isdigit()) for p in parts):
+            raise ValueError(f"--mix {mix!r}: name[:weight],... wanted")
+        kw["mix"] = tuple(p[0] for p in parts)
+        kw["mix_weights"] = tuple(int(p[1]) if len(p) == 2 else 1 for p in parts)
+    return TrainConfig(**kw)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     for f_ in TrainConfig.__dataclass_fields__.values():
         if f_.name == "size":
             ap.add_argument("--size", type=int, nargs=2, default=list(f_.default))
+        elif f_.name == "mix":
+            ap.add_argument("--mix", type=str, default=None, metavar="NAME[:WEIGHT],...",
+                            help="the parts of --dataset mix; a part without a weight counts once")
+        elif f_.name == "mix_weights":
+            continue                                # given inside --mix
         elif f_.type in ("bool", bool):
             ap.add_argument(f"--{f_.name.replace('_', '-')}", action=argparse.BooleanOptionalAction,
                             default=f_.default)
@@ -369,8 +417,7 @@ def main(argv=None):
             typ = {"int": int, "float": float, "str": str}.get(str(f_.type).replace("Optional[str]", "str"), str)
             ap.add_argument(f"--{f_.name.replace('_', '-')}", type=typ if f_.default is not None else str,
                             default=f_.default)
-    a = ap.parse_args(argv)
-    cfg = TrainConfig(**{k: (tuple(v) if k == "size" else v) for k, v in vars(a).items()})
+    cfg = config_from_args(ap.parse_args(argv))
     tr = Trainer(cfg)
     tr.fit()
     if dp.is_dist():

@@ -7,6 +7,7 @@
   NHWC tensors (``channels_last=True``).
 * image loading to NHWC float in [-1, 1] (``examples/demo.py:7-10``,
   ``validate_sintel.py:177-178``).
+* ``.pfm`` read/write (:func:`read_pfm`, :func:`write_pfm`): FlyingThings3D's flow.
 * PNG of 8 or 16 bits per sample (:func:`read_png`, :func:`write_png`) and KITTI's flow coding
   in it (:func:`read_flow_png`, :func:`write_flow_png`): a 16-bit RGB file, ``R, G = flow * 64 +
   32768``, ``B`` = valid.  The chunk parser and zlib are the standard library's; the row
@@ -48,6 +49,47 @@ def write_flo(path: str, flow: np.ndarray) -> None:
         np.array([FLO_MAGIC], np.float32).tofile(f)
         np.array([w, h], np.int32).tofile(f)
         flow.tofile(f)
+
+
+# ------------------------------------------------------------------------ PFM
+def read_pfm(path: str) -> np.ndarray:
+    """A ``.pfm`` file (FlyingThings3D's flow and disparity) -> (H, W, 3) for ``PF`` or (H, W) for
+    ``Pf``, float32, top row first.  The header is the magic, ``W H`` and a scale whose sign gives the
+    byte order (negative: little endian); the rows are stored bottom to top.  A little-endian file
+    comes back as a flipped VIEW of the bytes read, so a caller that copies it (or some of its
+    channels) into a buffer of its own makes the only copy.  Truncated data, a bad magic or a bad
+    header are a ``ValueError`` naming the file.  The flow of a Things file is ``[..., :2]``."""
+    bad = lambda why: ValueError(f"{path}: {why}")
+    with open(path, "rb") as f:
+        magic = f.readline().strip()
+        if magic not in (b"PF", b"Pf"):
+            raise bad("not a PFM file (bad magic)")
+        C = 3 if magic == b"PF" else 1
+        try:
+            dims = f.readline().split()
+            W, H = int(dims[0]), int(dims[1])
+            scale = float(f.readline().strip())
+            if len(dims) != 2 or W < 1 or H < 1 or scale == 0.0 or scale != scale:
+                raise ValueError
+        except (ValueError, IndexError):
+            raise bad("bad PFM header") from None
+        data = np.fromfile(f, "<f4" if scale < 0 else ">f4", count=H * W * C)
+    if data.size != H * W * C:
+        raise bad(f"truncated PFM data ({data.size} of {H * W * C} values)")
+    data = data.reshape((H, W, C) if C == 3 else (H, W))[::-1]
+    return data if data.dtype == np.float32 else data.astype(np.float32)
+
+
+def write_pfm(path: str, array: np.ndarray, little_endian: bool = True) -> None:
+    """The inverse of :func:`read_pfm`: (H, W) or (H, W, 3) float32, in either byte order."""
+    array = np.asarray(array, dtype=np.float32)
+    if array.ndim not in (2, 3) or (array.ndim == 3 and array.shape[2] != 3) or array.size == 0:
+        raise ValueError("write_pfm: (H, W) or (H, W, 3)")
+    H, W = array.shape[:2]
+    with open(path, "wb") as f:
+        f.write(b"PF\n" if array.ndim == 3 else b"Pf\n")
+        f.write(f"{W} {H}\n{'-1.0' if little_endian else '1.0'}\n".encode())
+        f.write(array[::-1].astype("<f4" if little_endian else ">f4").tobytes())
 
 
 # ------------------------------------------------------------------------ PNG
