@@ -333,6 +333,14 @@ int jr_augment_mixed_sums(const void* img1, const void* img2, const int* params,
 int jr_augment_mixed(const void* img1, const void* img2, const float* flow, const void* valid_in, const int* params,
                      const int* sums, float* out1, float* out2, float* out_flow, float* valid, int B, long S, int h, int w,
                      hipStream_t stream);
+// Flow validation metrics (metrics.hip; eval/metrics.py:flow_metrics: counts bitwise, fp64 sums up to
+// their order).  pred fp32 [B][Hp][Wp][2], gt fp32 [B][Hg][Wg][2], valid (optional) uint8 [B][Hg][Wg],
+// sizes int32 [B][2] = (Hs, Ws) on the device (clamped into both maps by the kernels): sample n is the
+// top-left Hs x Ws rectangle of both maps, nothing outside it is read.  part: scratch of B * NB * 2
+// 8-byte words, NB >= the blocks of the largest sample (ceil(Hs * ceil(Ws / 4) / 256)).  rows fp64
+// [B][6] is written, acc fp64 [8] is added to.  Two launches; no atomics, no memset.
+int jr_flow_metrics(const float* pred, const float* gt, const void* valid, const int* sizes, double* part,
+                    double* rows, double* acc, int B, int Hp, int Wp, int Hg, int Wg, int NB, hipStream_t stream);
 // Conv of a 2-channel input (the flow branch's 7x7 / 3x3): x bf16 NHWC
 // [N][H][W][x_cstride] (channels 0, 1 used), stride 1, output H x W; w bf16
 // MFMA A fragments [cout/16][NKC][64 lanes][8] (jax_raft_amd/ops/native.py:

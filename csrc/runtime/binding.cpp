@@ -1880,6 +1880,49 @@ static Launch make_augment_mixed(const TList& t, const IList& i, std::vector<at:
   };
 }
 
+// ---------------------------------------------------------- validation metrics
+// (kernels metrics.hip).  t = [pred (fp32 [B][Hp][Wp][2]), gt (fp32 [B][Hg][Wg][2]), valid? (uint8
+// [B][Hg][Wg]), sizes (int32 [B][2] on the device; the kernels clamp them into both maps), part (fp64
+// scratch, >= B * NB * 2), rows (fp64 [B][6]), acc (fp64 [8])], i = [B, Hp, Wp, Hg, Wg, NB]
+static Launch make_flow_metrics(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  at::Tensor pred = opt(t, 0), gt = opt(t, 1), valid = opt(t, 2), sizes = opt(t, 3), part = opt(t, 4);
+  at::Tensor rows = opt(t, 5), acc = opt(t, 6);
+  const int64_t B = i[0], Hp = i[1], Wp = i[2], Hg = i[3], Wg = i[4], NB = i[5];
+  TORCH_CHECK(B >= 1 && B <= 65535 && Hp >= 1 && Wp >= 1 && Hg >= 1 && Wg >= 1 && Hp * Wp <= 0x3fffffff &&
+                  Hg * Wg <= 0x3fffffff && NB >= 1 && NB <= 0x7fffffff, "flow_metrics: sizes");
+  check_f32(pred, "flow_metrics: pred");
+  check_f32(gt, "flow_metrics: gt");
+  TORCH_CHECK(pred.numel() == B * Hp * Wp * 2 && gt.numel() == B * Hg * Wg * 2,
+              "flow_metrics: pred [B][Hp][Wp][2], gt [B][Hg][Wg][2]");
+  if (valid.defined())
+    TORCH_CHECK(valid.is_cuda() && valid.scalar_type() == at::kByte && valid.is_contiguous() && valid.numel() == B * Hg * Wg,
+                "flow_metrics: valid must be a contiguous device uint8 [B][Hg][Wg]");
+  TORCH_CHECK(sizes.defined() && sizes.is_cuda() && sizes.scalar_type() == at::kInt && sizes.is_contiguous() &&
+                  sizes.numel() == 2 * B, "flow_metrics: sizes must be a contiguous device int32 [B][2]");
+  const int64_t need[3] = {B * NB * 2, B * 6, 8};
+  const char* what[3] = {"flow_metrics: part", "flow_metrics: rows", "flow_metrics: acc"};
+  const at::Tensor* out[3] = {&part, &rows, &acc};
+  for (int k = 0; k < 3; ++k) {
+    const at::Tensor& v = *out[k];
+    TORCH_CHECK(v.defined() && v.is_cuda() && v.scalar_type() == at::kDouble && v.is_contiguous() &&
+                    (k == 0 ? v.numel() >= need[k] : v.numel() == need[k]), what[k], " must be a contiguous device fp64 of ",
+                need[k], " elements");
+    for (const at::Tensor* in : {&pred, &gt, &sizes}) TORCH_CHECK(!augment_overlap(v, *in), what[k], " aliases an input");
+    TORCH_CHECK(!valid.defined() || !augment_overlap(v, valid), what[k], " aliases valid");
+    TORCH_CHECK(k != 0 || reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0, what[k], " must be 16-byte aligned");
+    for (int j = 0; j < k; ++j) TORCH_CHECK(!augment_overlap(v, *out[j]), what[k], " aliases another output");
+  }
+  for (auto& v : {pred, gt, valid, sizes, part, rows, acc})
+    if (v.defined()) keep.push_back(v);
+  const float *pp = pred.data_ptr<float>(), *gp = gt.data_ptr<float>();
+  const void* vp = ptr(valid);
+  const int* sp = sizes.data_ptr<int>();
+  double *wp = part.data_ptr<double>(), *rp = rows.data_ptr<double>(), *ap = acc.data_ptr<double>();
+  return [=](hipStream_t s, int) {
+    return jr_flow_metrics(pp, gp, vp, sp, wp, rp, ap, (int)B, (int)Hp, (int)Wp, (int)Hg, (int)Wg, (int)NB, s);
+  };
+}
+
 // ------------------------------------------------------------- sequence loss
 // t = [pred (fp32 [N][P][2]), gt (fp32 [P][2]), valid? (fp32 [P]), part (fp32 [blocks][37])], i = [P, N]
 void seq_loss_op(const TList& t, IList i, double max_flow) {
@@ -2050,6 +2093,7 @@ static const std::vector<OpRow>& op_table() {
       row_ti("augment_sparse", 5, 5, make_augment_sparse),
       row_ti("augment_mixed_sums", 2, 2, make_augment_mixed_sums),
       row_ti("augment_mixed", 4, 4, make_augment_mixed),
+      row_ti("flow_metrics", 6, 6, make_flow_metrics),
       // fp32 parity mode
       row_tia("conv_f32", "alpha", 22, 22, make_conv_f32),
       row_ti("stats_f32", 3, 3, make_stats_f32),

@@ -1,7 +1,8 @@
 """jax_raft_amd: an MI355X (gfx950)-native RAFT optical-flow framework with the
 API of alebeck/jax-raft (``RAFT``, ``raft_large``, ``raft_small``)."""
+from .eval.metrics import flow_metrics, metrics_from
 from .models.raft import RAFT, raft_large, raft_small
 from .models.reference import BidirectionalFlow, fb_consistency
 
 __version__ = "0.1.0"
-__all__ = ("RAFT", "raft_large", "raft_small", "BidirectionalFlow", "fb_consistency")
+__all__ = ("RAFT", "raft_large", "raft_small", "BidirectionalFlow", "fb_consistency", "flow_metrics", "metrics_from")

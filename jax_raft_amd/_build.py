@@ -53,6 +53,7 @@ KERNEL_SOURCES = [
     CSRC / "kernels" / "augment.hip",
     CSRC / "kernels" / "augment_sparse.hip",
     CSRC / "kernels" / "augment_mixed.hip",
+    CSRC / "kernels" / "metrics.hip",
 ]
 HOST_SOURCES = [CSRC / "runtime" / "binding.cpp", CSRC / "runtime" / "png.cpp"]
 # every header of csrc/ is a dependency of every object (a missed header left stale objects in

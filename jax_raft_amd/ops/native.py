@@ -767,6 +767,44 @@ def augment_pairs_mixed(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torc
     return out1, out2, oflow, valid
 
 
+METRICS_RUN, METRICS_BLOCK = 4, 256      # pixels per thread and threads per block of metrics.hip
+
+
+def flow_metrics_blocks(Hs: int, Ws: int) -> int:
+    """Blocks of the partials kernel that a sample of Hs x Ws occupies."""
+    return (Hs * ((Ws + METRICS_RUN - 1) // METRICS_RUN) + METRICS_BLOCK - 1) // METRICS_BLOCK
+
+
+def flow_metrics(pred: torch.Tensor, gt: torch.Tensor, valid: Optional[torch.Tensor] = None, sizes=None,
+                 acc: Optional[torch.Tensor] = None):
+    """Validation metrics of a batch, accumulated: ``eval/metrics.py:flow_metrics`` -- that golden op
+    itself on CPU tensors, the HIP kernels of ``metrics.hip`` on GPU tensors (every count bitwise equal,
+    the fp64 sums equal up to the order of their additions and bitwise repeatable; two launches and
+    the upload of the sizes, no host synchronisation; ``rows`` and ``acc`` stay on the device).
+    The arguments, ``sizes`` above all, are checked here on the host before anything is launched."""
+    from ..eval import metrics as M
+
+    if not pred.is_cuda:
+        return M.flow_metrics(pred, gt, valid, sizes, acc)
+    sizes = M.check_args(pred, gt, valid, sizes, acc)
+    dev = pred.device
+    B, Hp, Wp, _ = pred.shape
+    Hg, Wg = int(gt.shape[1]), int(gt.shape[2])
+    nb = max(flow_metrics_blocks(h, w) for h, w in sizes)
+    host = torch.empty((B, 2), dtype=torch.int32, pin_memory=True)
+    host.copy_(torch.tensor(sizes, dtype=torch.int32))
+    dsizes = host.to(dev, non_blocking=True)
+    part = torch.empty(B * nb * 2, dtype=torch.float64, device=dev)
+    rows = torch.empty((B, M.ROW), dtype=torch.float64, device=dev)
+    if acc is None:
+        acc = torch.zeros(M.ACC, dtype=torch.float64, device=dev)
+    elif not acc.is_contiguous():
+        raise ValueError("flow_metrics: acc must be contiguous")
+    ops().flow_metrics([pred.contiguous(), gt.contiguous(), None if valid is None else valid.contiguous(), dsizes, part,
+                        rows, acc], [B, Hp, Wp, Hg, Wg, nb])
+    return rows, acc
+
+
 def conv2d(spec: ConvSpec, x: torch.Tensor, act: int = ACT_NONE, out_dtype=torch.bfloat16, alpha: float = 1.0,
            res: Optional[torch.Tensor] = None, res_post: int = 0, cfg: Optional[int] = None) -> torch.Tensor:
     """Eager NHWC conv of a contiguous bf16 tensor [N, H, W, C] (C == cin8)."""

@@ -2,8 +2,8 @@
 the fused GPU augmentation) and the data-parallel trainer."""
 from .augment import (AugmentParams, MixedAugmentParams, SparseAugmentParams, augment_pairs, augment_pairs_mixed,
                       augment_pairs_sparse, sample_mixed, sample_sparse)
-from .datasets import FlowPairs, MixedFlowPairs, PairLoader, SparseFlowPairs
+from .datasets import FlowPairs, MixedFlowPairs, PairLoader, SequentialLoader, SparseFlowPairs
 
 __all__ = ("augment_pairs", "AugmentParams", "FlowPairs", "PairLoader", "augment_pairs_sparse", "SparseAugmentParams",
            "sample_sparse", "SparseFlowPairs", "MixedFlowPairs", "MixedAugmentParams", "sample_mixed",
-           "augment_pairs_mixed")
+           "augment_pairs_mixed", "SequentialLoader")

@@ -20,6 +20,10 @@ The Sintel stage of RAFT's schedule trains on a weighted mixture of dense and sp
 buffers ``(B, S, ...)`` with ``S`` the largest ``Hs * Ws`` of the list, sample ``n`` in the first
 ``Hs * Ws`` pixels of slot ``n`` with row pitch ``Ws``; only that prefix is uploaded, and the device op is
 ``ops/native.py:augment_pairs_mixed``.
+
+Validation: ``FlowPairs.chairs(root, split=...)`` lists FlyingChairs' training or validation pairs
+by its split file, and :class:`SequentialLoader` walks a list in order, unshuffled and with its
+tail, for ``eval/validate.py:evaluate``.
 """
 from __future__ import annotations
 
@@ -99,6 +103,29 @@ class SparseLayoutNotFound(FileNotFoundError, NotImplementedError):
     whatever the root held while they had no reader, so callers that catch that keep working."""
 
 
+CHAIRS_SPLITS = {"training": 1, "validation": 2}
+CHAIRS_SPLIT_FILES = ("FlyingChairs_train_val.txt", "chairs_split.txt")
+
+
+def read_chairs_split(root: str, pairs: int, split_file: Optional[str] = None) -> List[int]:
+    """The labels of FlyingChairs' split file: one integer per pair in sorted order, 1 = training,
+    2 = validation.  A missing file is a ``FileNotFoundError`` naming the paths tried; a wrong line
+    count or any other label is a ``ValueError`` naming the file."""
+    tried = ([split_file] if split_file is not None else
+             [osp.join(d, n) for d in (root, osp.dirname(osp.abspath(root))) for n in CHAIRS_SPLIT_FILES])
+    path = next((p for p in tried if osp.isfile(p)), None)
+    if path is None:
+        raise FileNotFoundError("no FlyingChairs split file: tried " + ", ".join(tried))
+    with open(path) as f:
+        words = f.read().split()
+    if len(words) != pairs:
+        raise ValueError(f"{path}: {len(words)} labels for {pairs} pairs")
+    if any(w not in ("1", "2") for w in words):
+        bad = next(w for w in words if w not in ("1", "2"))
+        raise ValueError(f"{path}: label {bad!r} (1 = training or 2 = validation wanted)")
+    return [int(w) for w in words]
+
+
 class FlowPairs:
     """``ds[i] -> (image1 uint8 (H, W, 3), image2, flow fp32 (H, W, 2))`` over a list of file triples."""
 
@@ -108,8 +135,18 @@ class FlowPairs:
             raise ValueError("FlowPairs: no pairs")
 
     @classmethod
-    def chairs(cls, root: str) -> "FlowPairs":
-        """FlyingChairs: ``NNNNN_img1.ppm``, ``NNNNN_img2.ppm``, ``NNNNN_flow.flo`` in one directory."""
+    def chairs(cls, root: str, split: Optional[str] = None, split_file: Optional[str] = None) -> "FlowPairs":
+        """FlyingChairs: ``NNNNN_img1.ppm``, ``NNNNN_img2.ppm``, ``NNNNN_flow.flo`` in one directory.
+
+        ``split``: ``"training"`` / ``"validation"`` keep the pairs whose line in the split file is
+        1 / 2 (one integer per pair, in sorted order); None: every pair.  ``split_file`` defaults to
+        ``FlyingChairs_train_val.txt``, then ``chairs_split.txt``, in ``root`` and then its parent."""
+        if split is not None:
+            if split not in CHAIRS_SPLITS:
+                raise ValueError(f"FlyingChairs split {split!r}: one of {sorted(CHAIRS_SPLITS)}, or None")
+            full = cls.chairs(root)
+            labels = read_chairs_split(root, len(full), split_file)
+            return cls([t for t, lab in zip(full.items, labels) if lab == CHAIRS_SPLITS[split]])
         firsts = sorted(glob(osp.join(root, "*_img1.ppm")))
         if not firsts:
             raise FileNotFoundError(f"no *_img1.ppm under {root}")
@@ -181,6 +218,8 @@ class FlowPairs:
             raise ValueError("FlowPairs.open: parts belong to dataset 'mix'")
         if dataset == "chairs":
             return cls.chairs(root)
+        if dataset in ("chairs-train", "chairs-val"):
+            return cls.chairs(root, "training" if dataset == "chairs-train" else "validation")
         if dataset in ("sintel-clean", "sintel-final"):
             return cls.sintel(root, dataset.split("-")[1])
         if dataset == "kitti":
@@ -191,7 +230,7 @@ class FlowPairs:
             return cls(cls.things(root, "clean").items + cls.things(root, "final").items)
         if dataset in ("things-clean", "things-final"):
             return cls.things(root, dataset.split("-")[1])
-        raise ValueError(f"unknown dataset {dataset!r} (chairs, sintel-clean, sintel-final, kitti, hd1k, things, "
+        raise ValueError(f"unknown dataset {dataset!r} (chairs, chairs-train, chairs-val, sintel-clean, sintel-final, kitti, hd1k, things, "
                          "things-clean, things-final, mix)")
 
     @classmethod
@@ -506,6 +545,98 @@ class PairLoader:
         if self.sparse:
             out += (self.sizes_for(step),)
         return out
+
+    def close(self) -> None:
+        self._worker.shutdown(wait=True)
+        self._pool.shutdown(wait=True)
+
+
+class SequentialLoader:
+    """The pairs of a list in order, for validation: rank ``r`` of ``world`` takes items ``r, r + world,
+    ...`` of the first ``max_pairs`` (all by default); consecutive items of one frame size form
+    batches of up to ``batch`` and the tail is kept as a smaller batch.  A sparse list (several frame
+    sizes) runs batch 1.
+
+    Iterating yields ``(image1 uint8 (k, H, W, 3), image2, flow fp32 (k, H, W, 2), valid uint8 (k, H, W)
+    or None, indices)`` on ``device``, each batch at its own frame size.  The next batch is decoded
+    by at most ``decode_threads()`` threads into a ring of pinned staging buffers -- the items
+    through the dataset's own ``__getitem__``, as :class:`PairLoader` reads them -- while the
+    caller works on the current one; the uploads are ``non_blocking`` on the current stream."""
+
+    def __init__(self, dataset: FlowPairs, batch: int = 4, rank: int = 0, world: int = 1, device=None,
+                 max_pairs: Optional[int] = None, depth: int = 3):
+        self.ds = dataset
+        self.device = torch.device(device) if device is not None else torch.device("cpu")
+        self.sparse = bool(getattr(dataset, "sparse", False))
+        if getattr(dataset, "mixed", False):
+            raise ValueError("SequentialLoader: a mixture is a training list, not a validation split")
+        self.pairs = len(dataset) if max_pairs is None else max(0, min(len(dataset), int(max_pairs)))
+        self.indices = list(range(int(rank), self.pairs, int(world)))
+        sizes = {i: frame_size(dataset.items[i][0]) for i in self.indices}
+        bs = 1 if self.sparse else max(1, int(batch))
+        self.batches: List[List[int]] = []
+        for i in self.indices:
+            last = self.batches[-1] if self.batches else None
+            if last is not None and len(last) < bs and sizes[last[0]] == sizes[i]:
+                last.append(i)
+            else:
+                self.batches.append([i])
+        self._sizes = sizes
+        self._cap = bs * max((h * w for h, w in sizes.values()), default=0)   # pixels of the largest batch
+        self.depth = max(2, int(depth))
+        self._pin = self.device.type == "cuda"
+        self._slots = [None] * self.depth
+        self._events = [None] * self.depth
+        self._pool = ThreadPoolExecutor(decode_threads(), thread_name_prefix="val-decode")
+        self._worker = ThreadPoolExecutor(1, thread_name_prefix="val-loader")
+
+    def __len__(self) -> int:
+        return len(self.batches)
+
+    def _staging(self, slot: int, k: int, size: Tuple[int, int]):
+        """Views (k, H, W, C) of the slot's flat pinned buffers."""
+        if self._slots[slot] is None:
+            mk = lambda n, dt: torch.empty(n, dtype=dt, pin_memory=self._pin)
+            self._slots[slot] = (mk(self._cap * 3, torch.uint8), mk(self._cap * 3, torch.uint8),
+                                 mk(self._cap * 2, torch.float32)) + ((mk(self._cap, torch.uint8),) if self.sparse else ())
+        H, W = size
+        return tuple(buf[:k * H * W * c].view((k, H, W) + ((c,) if c > 1 else ()))
+                     for buf, c in zip(self._slots[slot], (3, 3, 2, 1)))
+
+    def _decode_one(self, views, n: int, index: int, size: Tuple[int, int]) -> None:
+        arrs = self.ds[index]                      # 3 arrays of a dense item, 4 of a sparse one
+        paths = self.ds.items[index] + (self.ds.items[index][2],)
+        for arr, path in zip(arrs, paths):
+            if tuple(arr.shape[:2]) != size:
+                raise ValueError(f"{path}: size {tuple(arr.shape[:2])} differs from the pair's first image {size}")
+        for view, arr in zip(views, arrs):
+            np.copyto(view[n].numpy(), arr)
+
+    def _decode(self, k: int):
+        slot, idx = k % self.depth, self.batches[k]
+        ev = self._events[slot]
+        while ev is not None and not ev.query():   # the upload that read this slot (depth - 1 batches ago)
+            time.sleep(2e-4)
+        size = self._sizes[idx[0]]
+        views = self._staging(slot, len(idx), size)
+        for r in [self._pool.submit(self._decode_one, views, n, i, size) for n, i in enumerate(idx)]:
+            r.result()
+        return views
+
+    def __iter__(self):
+        cuda = self.device.type == "cuda"
+        fut = self._worker.submit(self._decode, 0) if self.batches else None
+        for k, idx in enumerate(self.batches):
+            views = fut.result()
+            fut = self._worker.submit(self._decode, k + 1) if k + 1 < len(self.batches) else None
+            if cuda:
+                out = tuple(torch.empty(v.shape, dtype=v.dtype, device=self.device).copy_(v, non_blocking=True) for v in views)
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self.device))
+                self._events[k % self.depth] = ev
+            else:
+                out = tuple(v.clone() for v in views)
+            yield out[0], out[1], out[2], (out[3] if self.sparse else None), list(idx)
 
     def close(self) -> None:
         self._worker.shutdown(wait=True)

@@ -20,6 +20,12 @@ things`` is FlyingThings3D (both passes; ``things-clean`` / ``things-final``: on
 the same batches (default ``sintel-clean:100,sintel-final:100,kitti:200,hd1k:5,things-clean:1``, each
 part in ``Sintel``, ``KITTI``, ``HD1K`` or ``FlyingThings3D`` under the root) through the mixed op.
 
+Validation on held-out data: ``--val name=root[,name=root...]`` (names ``chairs-val``, ``sintel-clean``,
+``sintel-final``, ``kitti``) evaluates the model after every ``--val-every`` steps and after the last one
+(``eval/validate.py:evaluate``: inference through the engine, metrics reduced on the device) and logs a JSON
+line with a ``"val"`` key; with ``--ckpt-dir`` the lines also go to ``<dir>/val.jsonl``.  ``--chairs-split FILE``
+trains ``--dataset chairs`` on the label-1 pairs of FlyingChairs' split file only, which ``chairs-val`` asks for.
+
 Checkpoints: ``<dir>/step_<n>.msgpack`` (Flax-format weights, loadable with
 ``raft_large(weights=...)``) + ``step_<n>.opt.pt`` (optimizer / scheduler
 state, tensors only) + ``latest.json``; ``--resume`` continues from latest.
@@ -84,8 +90,26 @@ class TrainConfig:
     # FlyingThings3D), and their integer weights; None: RAFT's (100, 100, 200, 5, 1 for the default parts)
     mix: tuple = ("sintel-clean", "sintel-final", "kitti", "hd1k", "things-clean")
     mix_weights: Optional[tuple] = None
+    # Validation on held-out splits (eval/validate.py).  The defaults mean none, as ever.
+    val: tuple = ()                # "name=root" strings: chairs-val | sintel-clean | sintel-final | kitti
+    val_every: int = 0             # validate after every val_every-th step and after the last; 0: after the last only
+    val_iters: int = 0             # 0: the protocol's default of each split
+    val_batch: int = 4             # batch size of the dense validation splits
+    val_max_pairs: Optional[int] = None
+    # a FlyingChairs split file: dataset="chairs" then lists its label-1 (training) pairs only
+    chairs_split: Optional[str] = None
 
     def __post_init__(self):
+        self.val = (self.val,) if isinstance(self.val, str) else tuple(self.val)
+        if self.val:
+            from ..eval.validate import parse_val
+
+            names = [n for n, _ in parse_val(self.val)]
+            if "chairs-val" in names and self.data is not None and self.dataset == "chairs" and not self.chairs_split:
+                raise ValueError("val: chairs-val while training on dataset 'chairs' without chairs_split would "
+                                 "validate on training data")
+            if self.graph_step:
+                raise ValueError("val: validation is not supported together with graph_step")
         if self.data is not None:
             from .augment import SPARSE_STAGES, STAGES
 
@@ -114,6 +138,9 @@ class TrainConfig:
 
         weights = self.mix_weights or [dict(MIX_DEFAULT).get(n, 1) for n in self.mix]   # RAFT's weight of each part
         return list(zip(self.mix, weights))
+
+
+VAL_FIELDS = ("val", "val_every", "val_iters", "val_batch", "val_max_pairs", "chairs_split")
 
 
 def _adamw(params, cfg: TrainConfig, device, capturable: bool = False):
@@ -166,8 +193,12 @@ class Trainer:
         if cfg.data is not None:
             from .datasets import FlowPairs, PairLoader
 
-            ds = (FlowPairs.open(cfg.data, "mix", parts=cfg.mix_parts) if cfg.dataset == "mix"
-                  else FlowPairs.open(cfg.data, cfg.dataset))
+            if cfg.dataset == "mix":
+                ds = FlowPairs.open(cfg.data, "mix", parts=cfg.mix_parts)
+            elif cfg.dataset == "chairs" and cfg.chairs_split:
+                ds = FlowPairs.chairs(cfg.data, "training", cfg.chairs_split)
+            else:
+                ds = FlowPairs.open(cfg.data, cfg.dataset)
             self.loader = PairLoader(ds, cfg.batch, seed=cfg.seed, rank=self.rank, world=self.world, device=self.device)
             if self.loader.frame_min[0] < cfg.size[0] or self.loader.frame_min[1] < cfg.size[1]:
                 raise ValueError(f"{cfg.data}: frames {self.loader.frame_min} are smaller than the crop {tuple(cfg.size)}")
@@ -175,6 +206,7 @@ class Trainer:
         self.skipped = 0           # total dropped steps
         self._skip_run = 0         # consecutive dropped steps
         self._pending = []         # (step, pinned non-finite flag, event): GPU steps not yet settled
+        self.val_history = []      # {"step": s, name: metrics, ...} of every validation (validate)
         if cfg.resume and cfg.ckpt_dir and os.path.exists(os.path.join(cfg.ckpt_dir, "latest.json")):
             self.load(cfg.ckpt_dir)
 
@@ -337,6 +369,7 @@ class Trainer:
         cfg = self.cfg
         end = cfg.steps if stop_at is None else min(stop_at, cfg.steps)
         t0 = time.perf_counter()
+        val_s = 0.0                # time spent validating: not training time
         last = {}
         while self.step < end:
             batch = self.batch_for(self.step)
@@ -346,17 +379,50 @@ class Trainer:
                 vals = dp.all_reduce_scalars({k: float(v) for k, v in m.items()}, self.device)
                 if self.device.type == "cuda":
                     torch.cuda.synchronize(self.device)
-                dt = time.perf_counter() - t0
+                dt = time.perf_counter() - t0 - val_s
                 vals.update(step=self.step, skipped=self.skipped, lr=float(self.sched.get_last_lr()[0]), elapsed_s=dt,
                             pairs_per_s=self.step * cfg.batch * self.world / dt)
+                if cfg.val:
+                    vals.update(val_s=val_s)
                 last = vals
                 if self.rank == 0:
                     log(json.dumps({k: (round(v, 6) if isinstance(v, float) else v) for k, v in vals.items()}))
+            if cfg.val and (self.step == cfg.steps or (cfg.val_every and self.step % cfg.val_every == 0)):
+                val_s += self.validate(log)
             if cfg.ckpt_dir and cfg.ckpt_every and self.step % cfg.ckpt_every == 0:
                 self.save(cfg.ckpt_dir)
         if cfg.ckpt_dir:
             self.save(cfg.ckpt_dir)
         return last
+
+    # ------------------------------------------------------------ validation
+    def validate(self, log=print) -> float:
+        """Evaluate the model as it stands on every split of ``cfg.val`` (``eval/validate.py:evaluate``:
+        inference through the engine, which repacks the updated weights by its version check; the
+        training plans, the optimizer, the BatchNorm statistics and the batch sequence are not
+        touched) -> the seconds it took.  The result is appended to ``val_history``, logged by rank 0
+        as a JSON line with a ``"val"`` key and appended to ``<ckpt_dir>/val.jsonl``."""
+        from ..eval.validate import evaluate, parse_val
+
+        cfg = self.cfg
+        self.flush()
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)    # the pause is the validation's own time
+        t0 = time.perf_counter()
+        entry = {"step": self.step}
+        for name, root in parse_val(cfg.val):
+            kw = {"chairs_split": cfg.chairs_split} if name == "chairs-val" and cfg.chairs_split else {}
+            entry[name] = evaluate(self.model, name, root, iters=cfg.val_iters or None, batch=cfg.val_batch,
+                                   max_pairs=cfg.val_max_pairs, device=self.device, **kw)
+        self.val_history.append(entry)
+        if self.rank == 0:
+            line = json.dumps({"val": entry})
+            log(line)
+            if cfg.ckpt_dir:
+                os.makedirs(cfg.ckpt_dir, exist_ok=True)
+                with open(os.path.join(cfg.ckpt_dir, "val.jsonl"), "a") as f:
+                    f.write(json.dumps(entry) + "\n")
+        return time.perf_counter() - t0
 
     # ------------------------------------------------------------ checkpoint
     def save(self, d: str) -> None:
@@ -371,9 +437,12 @@ class Trainer:
         torch.save({"opt": self.opt.state_dict(), "sched": self.sched.state_dict(), "step": self.step,
                     "skipped": self.skipped},
                    os.path.join(d, name + ".opt.pt"))
+        fields = type(self.cfg).__dataclass_fields__
+        config = {k: (list(v) if isinstance(v, tuple) else v) for k, v in asdict(self.cfg).items()
+                  # a run without validation writes the file it always wrote
+                  if k not in VAL_FIELDS or v != fields[k].default}
         with open(os.path.join(d, "latest.json"), "w") as f:
-            json.dump({"step": self.step, "weights": name + ".msgpack", "opt": name + ".opt.pt",
-                       "config": {k: (list(v) if isinstance(v, tuple) else v) for k, v in asdict(self.cfg).items()}}, f)
+            json.dump({"step": self.step, "weights": name + ".msgpack", "opt": name + ".opt.pt", "config": config}, f)
         if dp.is_dist():
             torch.distributed.barrier()
 
@@ -397,6 +466,10 @@ def config_from_args(a) -> TrainConfig:
             raise ValueError(f"--mix {mix!r}: name[:weight],... wanted")
         kw["mix"] = tuple(p[0] for p in parts)
         kw["mix_weights"] = tuple(int(p[1]) if len(p) == 2 else 1 for p in parts)
+    if isinstance(kw.get("val"), str):              # name=root,name=root
+        kw["val"] = tuple(p for p in kw["val"].split(",") if p)
+    if kw.get("val_max_pairs") is not None:
+        kw["val_max_pairs"] = int(kw["val_max_pairs"])
     return TrainConfig(**kw)
 
 
