@@ -303,6 +303,17 @@ int jr_forward_project(const float* flow, void* keys, float* out, int B, int h, 
 int jr_fb_check(const float* flow_fw, const float* flow_bw, const void* slot, long off_fw, long off_bw,
                 const float* thr, void* occ, float* err, int B, int H, int W, int H0, int W0, int top, int left,
                 hipStream_t stream);
+// Motion-compensated frames + masked photometric error (framewarp.hip; models/reference.py:warp_frames,
+// bitwise): one launch for dirs = 1 or 2 directions.  Direction d samples src[d] (uint8 [B][H0][W0][3]) at
+// x + flow[d](x), flow[d] fp32 [B][H][W][2] read inside the frame's rectangle (H0, W0, top, left) only --
+// tensors, or (slot, as in jr_fb_check) float offsets off[d] from a base address read at run time; 8-byte
+// aligned.  occ (optional) uint8 [dirs][B][H][W], own[d] (optional) the frame warped[d] should reproduce,
+// warped uint8 [dirs][B][H0][W0][3].  photo (optional, with own) int64 [dirs][B][2] = (sum |w - own| over
+// kept pixels and channels, kept pixels): ADDED to with integer atomics, so the caller clears it first.
+int jr_warp_frames(const void* src0, const void* src1, const void* own0, const void* own1, const float* flow0,
+                   const float* flow1, const void* slot, long off0, long off1, const void* occ, void* warped,
+                   long long* photo, int B, int H, int W, int H0, int W0, int top, int left, int dirs,
+                   hipStream_t stream);
 // Training-data augmentation (augment.hip; train/augment.py:augment_pairs, bitwise).  img1 / img2 uint8
 // [B][Hs][Ws][3], flow fp32 [B][Hs][Ws][2], params int32 [B][48] (the sampler's records), sums int32
 // [2][B][3].  jr_augment_sums clears sums (a memset in the stream) and adds up every frame's channels

@@ -1723,6 +1723,91 @@ static Launch make_fb_check(const TList& t, const IList& i, std::vector<at::Tens
   };
 }
 
+// ------------------------------------- motion-compensated frames + photometric error
+// (kernel framewarp.hip).  t = [src0, src1?, own0?, own1?, flow0?, flow1?, occ?, warped, photo?, out_slot?],
+// i = [B, H, W, H0, W0, top, left, dirs(, off0, off1)].  Direction d samples src d (uint8 [B][H0][W0][3]) with
+// flow d (fp32 [B][H][W][2]) and fills masked pixels from own d (0 without it); a bidirectional plan passes
+// src = (frame 2, frame 1), own = (frame 1, frame 2).  occ uint8 [dirs][B][H][W], warped uint8
+// [dirs][B][H0][W0][3], photo int64 [dirs][B][2] (added to: cleared by the caller), only together with own.
+// With out_slot the flows are read at float offsets off0 / off1 from the address it holds (see make_fb_check).
+static Launch make_warp_frames(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  at::Tensor src[2] = {opt(t, 0), opt(t, 1)}, own[2] = {opt(t, 2), opt(t, 3)}, flow[2] = {opt(t, 4), opt(t, 5)};
+  at::Tensor occ = opt(t, 6), warped = opt(t, 7), photo = opt(t, 8), slot = opt(t, 9);
+  const int B = (int)i[0], H = (int)i[1], W = (int)i[2], H0 = (int)i[3], W0 = (int)i[4], top = (int)i[5], left = (int)i[6];
+  const int dirs = (int)i[7];
+  TORCH_CHECK(dirs == 1 || dirs == 2, "warp_frames: dirs must be 1 or 2");
+  TORCH_CHECK(B >= 1 && (int64_t)dirs * B <= 65535 && H >= 1 && W >= 1 && (int64_t)H * W <= 0x3fffffff, "warp_frames: sizes");
+  TORCH_CHECK(H0 >= 1 && W0 >= 1 && top >= 0 && left >= 0 && top + H0 <= H && left + W0 <= W,
+              "warp_frames: the window (H0, W0, top, left) must lie inside the map");
+  const int64_t M = (int64_t)B * H * W, F = (int64_t)B * H0 * W0 * 3;
+  auto overlap = [](const at::Tensor& a, const at::Tensor& b) {
+    const char *a0 = (const char*)a.data_ptr(), *b0 = (const char*)b.data_ptr();
+    return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
+  };
+  auto is_frames = [&](const at::Tensor& v, int64_t n) {
+    return v.defined() && v.is_cuda() && v.scalar_type() == at::kByte && v.is_contiguous() && v.numel() == n;
+  };
+  TORCH_CHECK(is_frames(warped, dirs * F), "warp_frames: warped must be a contiguous device uint8 [dirs][B][H0][W0][3]");
+  TORCH_CHECK(own[0].defined() == own[1].defined() || dirs == 1, "warp_frames: two directions take both own frames or none");
+  TORCH_CHECK(photo.defined() ? own[0].defined() : true, "warp_frames: photo only together with own");
+  std::vector<at::Tensor> inputs;
+  for (int d = 0; d < 2; ++d) {
+    if (d >= dirs) {
+      TORCH_CHECK(!src[d].defined() && !own[d].defined() && !flow[d].defined(), "warp_frames: one direction takes one src / own / flow");
+      continue;
+    }
+    TORCH_CHECK(is_frames(src[d], F), "warp_frames: src must be a contiguous device uint8 [B][H0][W0][3]");
+    inputs.push_back(src[d]);
+    if (own[d].defined()) {
+      TORCH_CHECK(is_frames(own[d], F), "warp_frames: own must be a contiguous device uint8 [B][H0][W0][3]");
+      inputs.push_back(own[d]);
+    }
+  }
+  if (occ.defined()) {
+    TORCH_CHECK(occ.is_cuda() && occ.scalar_type() == at::kByte && occ.is_contiguous() && occ.numel() == dirs * M,
+                "warp_frames: occ must be a contiguous device uint8 [dirs][B][H][W]");
+    inputs.push_back(occ);
+  }
+  if (photo.defined())
+    TORCH_CHECK(photo.is_cuda() && photo.scalar_type() == at::kLong && photo.is_contiguous() && photo.numel() == 2 * dirs * B,
+                "warp_frames: photo must be a contiguous device int64 [dirs][B][2]");
+  int64_t off[2] = {0, 0};
+  if (slot.defined()) {
+    TORCH_CHECK(slot.is_cuda() && slot.scalar_type() == at::kLong && slot.numel() == 1,
+                "warp_frames: out_slot must be one device int64");
+    TORCH_CHECK(!flow[0].defined() && !flow[1].defined() && i.size() == 10,
+                "warp_frames: out_slot takes [.., off0, off1] and no flow tensors");
+    off[0] = i[8]; off[1] = i[9];
+    TORCH_CHECK(off[0] >= 0 && off[1] >= 0 && off[0] % 2 == 0 && off[1] % 2 == 0, "warp_frames: flow offsets (8-byte aligned)");
+    inputs.push_back(slot);
+  } else {
+    TORCH_CHECK(i.size() == 8, "warp_frames: expected [B, H, W, H0, W0, top, left, dirs] with flow tensors");
+    for (int d = 0; d < dirs; ++d) {
+      check_f32(flow[d], "warp_frames: flow");
+      TORCH_CHECK(flow[d].numel() == 2 * M, "warp_frames: flows [B][H][W][2]");
+      TORCH_CHECK(reinterpret_cast<uintptr_t>(flow[d].data_ptr()) % 8 == 0, "warp_frames: flows 8-byte aligned");
+      inputs.push_back(flow[d]);
+    }
+  }
+  for (const at::Tensor& v : inputs) {
+    TORCH_CHECK(!overlap(warped, v), "warp_frames: warped aliases an input");
+    TORCH_CHECK(!photo.defined() || !overlap(photo, v), "warp_frames: photo aliases an input");
+  }
+  TORCH_CHECK(!photo.defined() || !overlap(photo, warped), "warp_frames: photo aliases warped");
+  for (const at::Tensor& v : inputs) keep.push_back(v);
+  keep.push_back(warped);
+  if (photo.defined()) keep.push_back(photo);
+  const void *s0 = ptr(src[0]), *s1 = ptr(src[1]), *o0 = ptr(own[0]), *o1 = ptr(own[1]), *sp = ptr(slot), *mp = ptr(occ);
+  const float* f0 = (const float*)ptr(flow[0]);
+  const float* f1 = (const float*)ptr(flow[1]);
+  void* wp = warped.data_ptr();
+  long long* pp = photo.defined() ? (long long*)photo.data_ptr() : nullptr;
+  const long a0 = (long)off[0], a1 = (long)off[1];
+  return [=](hipStream_t s, int) {
+    return jr_warp_frames(s0, s1, o0, o1, f0, f1, sp, a0, a1, mp, wp, pp, B, H, W, H0, W0, top, left, dirs, s);
+  };
+}
+
 // -------------------------------------------------------- training-data augmentation
 // (kernels augment.hip).  The frames as uploaded: img1 / img2 uint8 [B][Hs][Ws][3]; sums int32 [2][B][3].
 static void check_augment_frames(const at::Tensor& a, const at::Tensor& b, int64_t B, int64_t Hs, int64_t Ws, const char* op) {
@@ -2066,6 +2151,7 @@ static const std::vector<OpRow>& op_table() {
       row_ti("init_flow_f32", 5, 5, make_init_flow_f32),
       row_ti("forward_project", 4, 4, make_forward_project),
       row_ti("fb_check", 7, 9, make_fb_check),           // flow tensors 7, a plan's output slot 9
+      row_ti("warp_frames", 8, 10, make_warp_frames),    // flow tensors 8, a plan's output slot 10
       row_t("memset", make_memset),
       row_t("copy", make_copy),
       row_ti("copy_channels", 4, 4, make_copy_channels),

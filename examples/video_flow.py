@@ -4,7 +4,7 @@
 previous pair's refinement loop and this pair's encoders + correlation
 pyramid, and returns the previous pair's flow; ``flush()`` drains the last.
 
-  python examples/video_flow.py frame_0000.png frame_0001.png ... [--arch raft_small] [--iters 12] [--warm-start | --bidirectional]
+  python examples/video_flow.py frame_0000.png frame_0001.png ... [--arch raft_small] [--iters 12] [--warm-start | --bidirectional [--warp [--out DIR]]]
 
 ``--warm-start`` runs the synchronous path instead (``RaftEngine.forward``) and
 starts every pair after the first from the previous pair's flow, projected
@@ -19,6 +19,14 @@ forward flows.  This path feeds the raw uint8 frames: the engine pads them on th
 the flows and the masks back, and its check treats the frame -- not the padded map -- as the
 image, so a landing point in the padding counts as outside.
 
+``--bidirectional --warp`` adds the motion-compensated frames and the masked photometric error
+from the same call (``forward(bidirectional=True, warp=True)``): frame 2 sampled with the flow
+1 -> 2 (and frame 1 with the flow 2 -> 1), occluded pixels taken from the frame itself.  It prints
+the mean absolute error in 8-bit levels over the kept pixels and the share of pixels kept, per
+direction over the sequence -- a label-free check of the flow, not an accuracy figure (with
+random weights it says nothing about accuracy at all); ``--out DIR`` writes ``warped_fw_NNNN.png``
+(the PNG encoder runs on the host between the calls, so the printed pairs/s then measures it too).
+
 Without frames a synthetic drifting sequence is used.  Needs an MI355X (the
 native engine); prints the pairs/s of the steady state.
 """
@@ -32,8 +40,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from jax_raft_amd import raft_large, raft_small  # noqa: E402
-from jax_raft_amd.utils.flow_io import InputPadder, normalize_image, read_image  # noqa: E402
+from jax_raft_amd import photometric_error, raft_large, raft_small  # noqa: E402
+from jax_raft_amd.utils.flow_io import InputPadder, normalize_image, read_image, write_png  # noqa: E402
 
 
 def frames(paths, n_synth=16, raw=False):
@@ -59,8 +67,15 @@ def main():
                     help="synchronous forwards, each pair after the first started from the previous pair's flow")
     ap.add_argument("--bidirectional", action="store_true",
                     help="synchronous forwards that return both directions' flows and the occlusion masks")
+    ap.add_argument("--warp", action="store_true",
+                    help="with --bidirectional: also the motion-compensated frames and the masked photometric error")
+    ap.add_argument("--out", default=None, help="with --warp: a directory for warped_fw_NNNN.png")
     args = ap.parse_args()
     assert not (args.warm_start and args.bidirectional), "--warm-start and --bidirectional exclude each other"
+    assert args.bidirectional or not args.warp, "--warp needs --bidirectional"
+    assert args.warp or args.out is None, "--out needs --warp"
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
     assert torch.cuda.is_available(), "the pipelined engine runs on the GPU"
     factory = raft_large if args.arch == "raft_large" else raft_small
     model, _ = factory(weights=args.weights) if args.weights else factory()
@@ -70,12 +85,18 @@ def main():
 
     flows, prev, padder = [], None, None
     flows_bw, occ_fw, occ_bw = [], [], []
+    photo, frame = None, None   # --warp: the running (2, 2) int64 sums over the sequence, on the device
     t0, n_pairs = None, 0
     for img in frames(args.frames, raw=args.bidirectional):
         if args.bidirectional:   # raw frames: padded, cropped and windowed by the engine
             cur = img.to(dev)
             if prev is not None:
-                res = eng.forward(prev, cur, args.iters, return_all_iters=False, bidirectional=True)
+                res = eng.forward(prev, cur, args.iters, return_all_iters=False, bidirectional=True, warp=args.warp)
+                if args.warp:
+                    photo = res.photo.sum(1) if photo is None else photo + res.photo.sum(1)
+                    frame = tuple(cur.shape[1:3])
+                    if args.out:
+                        write_png(os.path.join(args.out, f"warped_fw_{len(flows):04d}.png"), res.warped_fw[0].cpu().numpy())
                 flows.append(res.flows_fw[-1])
                 flows_bw.append(res.flows_bw[-1])
                 occ_fw.append(res.occ_fw)
@@ -118,6 +139,11 @@ def main():
         frac = [float(torch.stack(m).float().mean()) for m in (occ_fw, occ_bw)]
         print(f"{len(flows_bw)} backward flow fields, {len(occ_fw)} mask pairs {tuple(occ_fw[0].shape)}; "
               f"occluded 1->2 {100 * frac[0]:.1f} %, 2->1 {100 * frac[1]:.1f} %")
+    if photo is not None:
+        mae, cov = photometric_error(photo.cpu(), frame)
+        cov = cov / len(flows)   # the sums run over every pair of the sequence
+        print("masked photometric error (8-bit levels) / pixels kept: "
+              f"1->2 {float(mae[0]):.2f} / {100 * float(cov[0]):.1f} %, 2->1 {float(mae[1]):.2f} / {100 * float(cov[1]):.1f} %")
     print(f"{len(flows)} flow fields {tuple(flows[0].shape) if flows else ()}; "
           f"steady state {n_pairs / dt if dt > 0 and n_pairs else float('nan'):.1f} pairs/s")
 

@@ -50,6 +50,7 @@ KERNEL_SOURCES = [
     CSRC / "kernels" / "conv_fam_grp.hip",
     CSRC / "kernels" / "warm.hip",
     CSRC / "kernels" / "fbcheck.hip",
+    CSRC / "kernels" / "framewarp.hip",
     CSRC / "kernels" / "augment.hip",
     CSRC / "kernels" / "augment_sparse.hip",
     CSRC / "kernels" / "augment_mixed.hip",

@@ -112,3 +112,18 @@ def metrics_from(acc) -> Dict[str, float]:
     n = max(a[1], 1.0)
     return {"epe": a[0] / n, "1px": a[2] / n, "3px": a[3] / n, "5px": a[4] / n, "f1": 100.0 * a[5] / n,
             "epe_image_mean": a[6] / max(a[7], 1.0), "pixels": int(a[1])}
+
+
+def photometric_error(photo: torch.Tensor, size: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(mae, coverage)`` of ``models/reference.py:warp_frames``' ``photo`` (..., 2) int64 = (sum of
+    ``|warped - own|`` over kept pixels and channels, kept pixels) for frames of ``size = (H0, W0)``:
+    ``mae = sum / (3 * count)`` in 8-bit levels, NaN where nothing was kept, and ``coverage = count /
+    (H0 * W0)``; both fp64 of shape ``photo.shape[:-1]``.  A label-free check of a flow field, not an
+    accuracy figure."""
+    if photo.shape[-1] != 2 or photo.dtype != torch.int64:
+        raise ValueError(f"photometric_error: photo must be (..., 2) int64, got {tuple(photo.shape)} {photo.dtype}")
+    H0, W0 = (int(v) for v in size)
+    if H0 < 1 or W0 < 1:
+        raise ValueError(f"photometric_error: size must be (H0, W0) >= 1, got {tuple(size)}")
+    s, n = photo[..., 0].to(torch.float64), photo[..., 1].to(torch.float64)
+    return s / (3.0 * n), n / float(H0 * W0)

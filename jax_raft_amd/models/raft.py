@@ -78,7 +78,7 @@ class RAFT(nn.Module):
 
     def forward(self, image1, image2, train: bool = False, num_flow_updates: int = 12, return_all_iters: bool = True,
                 flow_init=None, return_flow_low: bool = False, bidirectional: bool = False, fb_alpha: float = 0.01,
-                fb_beta: float = 0.5, **engine_kw):
+                fb_beta: float = 0.5, warp: bool = False, **engine_kw):
         """Upsampled flows of every refinement iteration, (num_flow_updates, B, H, W, 2)
         (reference semantics, ``model.py:605``).  ``return_all_iters=False`` (inference
         serving mode) upsamples and returns only the final flow, shape (1, B, H, W, 2).
@@ -99,16 +99,27 @@ class RAFT(nn.Module):
         forward-backward consistency check (:func:`reference.fb_consistency`, UnFlow's criterion
         with ``fb_alpha``, ``fb_beta``) -- from one call: one plan of the native engine, or two
         golden passes plus the golden check elsewhere.  For uint8 frames everything is cropped to
-        the frame.  Inference only, and not together with ``flow_init`` / ``return_flow_low``."""
+        the frame.  Inference only, and not together with ``flow_init`` / ``return_flow_low``.
+
+        ``bidirectional=True, warp=True`` (uint8 frames only; anything else is a ``ValueError``)
+        returns :class:`~jax_raft_amd.models.reference.BidirectionalWarp`: the same four fields,
+        the motion-compensated frames ``warped_fw`` / ``warped_bw`` (B, H0, W0, 3) uint8 and
+        ``photo`` (2, B, 2) int64, the masked photometric sums (:func:`reference.warp_frames`) --
+        the last kernel of the same plan, or the golden warp elsewhere."""
         image1, image2 = _as_tensor(image1), _as_tensor(image2)
+        if warp and not bidirectional:
+            raise ValueError("warp=True requires bidirectional=True (the warp uses both flows' occlusion masks)")
         if bidirectional:
             if train or engine_kw.get("autograd"):
                 raise NotImplementedError("bidirectional: inference only (not with train / autograd)")
             if flow_init is not None or return_flow_low:
                 raise NotImplementedError("bidirectional: not with flow_init / return_flow_low (the warm seed and "
                                           "the low-resolution output are lowered for one direction)")
+            if warp and not (image1.dtype == torch.uint8 and image2.dtype == torch.uint8):
+                raise ValueError(f"bidirectional, warp=True requires uint8 frames (the warp samples the frames as "
+                                 f"given), got {image1.dtype}")
             return self._forward_bidirectional(image1, image2, num_flow_updates, return_all_iters, fb_alpha, fb_beta,
-                                               engine_kw)
+                                               engine_kw, warp)
         B, H, W, _ = image1.shape
         assert (H, W) == tuple(image2.shape[-3:-1]), "input images should have the same shape"
         warm = dict(flow_init=flow_init, return_flow_low=return_flow_low)
@@ -140,10 +151,12 @@ class RAFT(nn.Module):
                 return self.forward_reference(image1, image2, False, num_flow_updates, return_all_iters, **warm)
         return self.forward_reference(image1, image2, train, num_flow_updates, return_all_iters, **warm)
 
-    def _forward_bidirectional(self, image1, image2, num_flow_updates, return_all_iters, alpha, beta, engine_kw):
+    def _forward_bidirectional(self, image1, image2, num_flow_updates, return_all_iters, alpha, beta, engine_kw,
+                               warp=False):
         """``forward(bidirectional=True)``: the native engine's bidirectional plan for a model on
         the GPU it can lower (float or uint8 frames); everywhere else two passes of
-        :meth:`forward` and the golden check of their final flows."""
+        :meth:`forward` and the golden check of their final flows (+ the golden warp of both
+        frames with ``warp``)."""
         dev = self._param_device()
         if dev.type == "cuda" and self._lowering_error is None:
             eng = self._try_engine(dev, {k: v for k, v in engine_kw.items() if k not in ("autograd", "fused")})
@@ -154,11 +167,16 @@ class RAFT(nn.Module):
                 if not image1.is_cuda and image1.dtype != torch.uint8:
                     image1, image2 = image1.to(dev), image2.to(dev)
                 return eng.forward(image1, image2, num_flow_updates, return_all_iters=return_all_iters,
-                                   bidirectional=True, fb_alpha=alpha, fb_beta=beta)
+                                   bidirectional=True, fb_alpha=alpha, fb_beta=beta, warp=warp)
         with torch.no_grad():
             fw = self.forward(image1, image2, False, num_flow_updates, return_all_iters, **engine_kw)
             bw = self.forward(image2, image1, False, num_flow_updates, return_all_iters, **engine_kw)
             occ_fw, occ_bw = R.fb_consistency(fw[-1].contiguous(), bw[-1].contiguous(), alpha, beta)
+            if warp:   # the flows are already cropped to the frame: the whole map is the window
+                f1, f2 = image1.to(fw.device), image2.to(fw.device)
+                warped_fw, photo_fw = R.warp_frames(f2, fw[-1].contiguous(), occ_fw, f1)
+                warped_bw, photo_bw = R.warp_frames(f1, bw[-1].contiguous(), occ_bw, f2)
+                return R.BidirectionalWarp(fw, bw, occ_fw, occ_bw, warped_fw, warped_bw, torch.stack([photo_fw, photo_bw]))
         return R.BidirectionalFlow(fw, bw, occ_fw, occ_bw)
 
     def _forward_u8(self, image1, image2, train, num_flow_updates, return_all_iters, engine_kw, warm):

@@ -34,6 +34,8 @@ __all__ = [
     "fill_offsets",
     "fb_consistency",
     "BidirectionalFlow",
+    "warp_frames",
+    "BidirectionalWarp",
 ]
 
 
@@ -512,3 +514,86 @@ def fb_consistency(flow_fw: torch.Tensor, flow_bw: torch.Tensor, alpha: float = 
     if return_err:
         return res[0][0], res[1][0], res[0][1], res[1][1]
     return res[0][0], res[1][0]
+
+
+class BidirectionalWarp(NamedTuple):
+    """What ``bidirectional=True, warp=True`` returns: :class:`BidirectionalFlow`'s four fields,
+    the motion-compensated frames (B, H0, W0, 3) uint8 -- ``warped_fw`` is frame 2 sampled with the
+    flow 1 -> 2 (it reproduces frame 1), ``warped_bw`` frame 1 sampled with the flow 2 -> 1 -- and
+    ``photo`` (2, B, 2) int64: per direction and sample (sum of ``|warped - own|`` over kept pixels
+    and channels, kept pixels) (:func:`warp_frames`)."""
+    flows_fw: torch.Tensor
+    flows_bw: torch.Tensor
+    occ_fw: torch.Tensor
+    occ_bw: torch.Tensor
+    warped_fw: torch.Tensor
+    warped_bw: torch.Tensor
+    photo: torch.Tensor
+
+
+def warp_frames(src: torch.Tensor, flow: torch.Tensor, occ: Optional[torch.Tensor] = None,
+                own: Optional[torch.Tensor] = None, window: Optional[Tuple[int, int, int, int]] = None):
+    """Motion-compensated frame and masked photometric error: ``src`` sampled at ``x + flow(x)``,
+    the occluded pixels and those that land outside replaced.  Returns ``(warped, photo)``.
+
+    src: (B, H0, W0, 3) uint8, the frame that is sampled; flow: (B, H, W, 2) fp32, channel 0 = x;
+    ``window = (H0, W0, top, left)``: the frame's rectangle inside the flow map (default: the
+    whole map); occ: (B, H, W) bool or None (True = occluded, :func:`fb_consistency`); own:
+    (B, H0, W0, 3) uint8 or None, the frame ``warped`` should reproduce.
+
+    A fixed sequence of fp32 operations, every product and sum rounded on its own (the kernel
+    csrc/kernels/framewarp.hip equals it bit for bit).  Steps 1 and 2 are :func:`fb_consistency`'s,
+    so the two ops agree on what "outside" means.  For a frame pixel (y, x) with
+    ``f = flow[top + y, left + x]``:
+
+    1. ``px = float(x) + f.x``, ``py = float(y) + f.y``; ``inside`` iff ``0 <= px <= W0-1`` and
+       ``0 <= py <= H0-1`` (NaN fails).
+    2. ``x0 = floor(px)``, ``x1 = min(x0+1, W0-1)``, ``wx = px - float(x0)``; y likewise.
+    3. Per channel, the texels converted to fp32: ``t = c00 + wx*(c01 - c00)``,
+       ``b = c10 + wx*(c11 - c10)``, ``v = t + wy*(b - t)`` (in [0, 255]: every step is monotone
+       under rounding).
+    4. ``w = uint8(rint(v))``, ties to even.
+    5. ``keep = inside && !occ``; ``warped = keep ? w : own`` (0 without ``own``).
+    6. ``photo[b] = (sum over kept pixels and the 3 channels of |w - own|, kept pixels)``, int64
+       (B, 2); ``None`` without ``own``."""
+    assert flow.ndim == 4 and flow.shape[-1] == 2 and flow.dtype == torch.float32, "flow: (B, H, W, 2) fp32"
+    B, H, W, _ = flow.shape
+    H0, W0, top, left = (H, W, 0, 0) if window is None else map(int, window)
+    assert H0 >= 1 and W0 >= 1 and top >= 0 and left >= 0 and top + H0 <= H and left + W0 <= W, \
+        "window (H0, W0, top, left) must lie inside the map"
+    for name, t in (("src", src), ("own", own)):
+        assert t is None or (tuple(t.shape) == (B, H0, W0, 3) and t.dtype == torch.uint8), \
+            f"{name}: (B, H0, W0, 3) uint8"
+    assert occ is None or (tuple(occ.shape) == (B, H, W) and occ.dtype == torch.bool), "occ: (B, H, W) bool"
+    dev = flow.device
+    f = flow[:, top:top + H0, left:left + W0]
+    grid = make_coords_grid(1, H0, W0, device=dev)
+    px = grid[..., 0] + f[..., 0]
+    py = grid[..., 1] + f[..., 1]
+    inside = (px >= 0) & (px <= W0 - 1) & (py >= 0) & (py <= H0 - 1)   # NaN fails
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    pxs = torch.where(inside, px, zero)
+    pys = torch.where(inside, py, zero)
+    x0f, y0f = torch.floor(pxs), torch.floor(pys)
+    wx, wy = (pxs - x0f).unsqueeze(-1), (pys - y0f).unsqueeze(-1)
+    x0, y0 = x0f.long(), y0f.long()
+    x1, y1 = torch.clamp(x0 + 1, max=W0 - 1), torch.clamp(y0 + 1, max=H0 - 1)
+    sf = src.reshape(B, H0 * W0, 3).to(torch.float32)
+
+    def tap(yy, xx):
+        idx = (yy * W0 + xx).reshape(B, H0 * W0, 1).expand(-1, -1, 3)
+        return torch.gather(sf, 1, idx).view(B, H0, W0, 3)
+
+    c00, c01, c10, c11 = tap(y0, x0), tap(y0, x1), tap(y1, x0), tap(y1, x1)
+    t = c00 + wx * (c01 - c00)
+    b = c10 + wx * (c11 - c10)
+    v = t + wy * (b - t)
+    w = torch.round(v).to(torch.uint8)
+    keep = inside if occ is None else inside & ~occ[:, top:top + H0, left:left + W0]
+    fill = own if own is not None else torch.zeros_like(src)
+    warped = torch.where(keep.unsqueeze(-1), w, fill)
+    if own is None:
+        return warped, None
+    d = (w.to(torch.int64) - own.to(torch.int64)).abs().sum(-1)
+    photo = torch.stack([(d * keep).sum((1, 2)), keep.sum((1, 2))], dim=-1)
+    return warped, photo

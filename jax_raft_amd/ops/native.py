@@ -630,6 +630,51 @@ def fb_check(flow_fw: torch.Tensor, flow_bw: torch.Tensor, alpha: float = 0.01, 
     return occ[0], occ[1]
 
 
+def warp_frames(src: torch.Tensor, flow: torch.Tensor, occ: Optional[torch.Tensor] = None,
+                own: Optional[torch.Tensor] = None, window: Optional[Tuple[int, int, int, int]] = None):
+    """Motion-compensated frame and masked photometric error of one direction, ``(warped,
+    photo)``: ``models/reference.py:warp_frames`` -- that golden op itself on CPU tensors, the HIP
+    kernel (csrc/kernels/framewarp.hip, bitwise equal, one launch after the clear of the two
+    sums) on GPU tensors.  src / own: (B, H0, W0, 3) uint8, flow: (B, H, W, 2) fp32, occ:
+    (B, H, W) bool, ``window = (H0, W0, top, left)`` (default: the whole map).  Returns fresh
+    tensors; ``photo`` is None without ``own``.  Wrong shapes or dtypes raise ``ValueError``
+    before anything is launched."""
+    if flow.ndim != 4 or flow.shape[-1] != 2 or flow.dtype != torch.float32:
+        raise ValueError(f"warp_frames: flow must be (B, H, W, 2) fp32, got {tuple(flow.shape)} {flow.dtype}")
+    B, H, W, _ = flow.shape
+    win = [H, W, 0, 0] if window is None else [int(v) for v in window]
+    H0, W0, top, left = win
+    if len(win) != 4 or H0 < 1 or W0 < 1 or top < 0 or left < 0 or top + H0 > H or left + W0 > W:
+        raise ValueError(f"warp_frames: window (H0, W0, top, left) = {tuple(win)} must lie inside the {H} x {W} map")
+    for name, t in (("src", src), ("own", own)):
+        if t is None and name == "own":
+            continue
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (B, H0, W0, 3) or t.dtype != torch.uint8:
+            raise ValueError(f"warp_frames: {name} must be {(B, H0, W0, 3)} uint8, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else t} {getattr(t, 'dtype', '')}")
+        if t.device != flow.device:
+            raise ValueError(f"warp_frames: {name} is on {t.device}, flow on {flow.device}")
+    if occ is not None:
+        if tuple(occ.shape) != (B, H, W) or occ.dtype != torch.bool:
+            raise ValueError(f"warp_frames: occ must be {(B, H, W)} bool, got {tuple(occ.shape)} {occ.dtype}")
+        if occ.device != flow.device:
+            raise ValueError(f"warp_frames: occ is on {occ.device}, flow on {flow.device}")
+    if not flow.is_cuda:
+        from ..models.reference import warp_frames as golden
+
+        return golden(src, flow, occ, own, win)
+    dev = flow.device
+    flow = flow.contiguous()
+    if flow.data_ptr() % 8:   # the kernel's 8-byte loads
+        flow = flow.clone()
+    warped = torch.empty((1, B, H0, W0, 3), dtype=torch.uint8, device=dev)
+    photo = None if own is None else torch.zeros((1, B, 2), dtype=torch.int64, device=dev)
+    mask = None if occ is None else occ.contiguous().view(torch.uint8).view(1, B, H, W)
+    ops().warp_frames([src.contiguous(), None, None if own is None else own.contiguous(), None, flow, None, mask,
+                       warped, photo], [B, H, W] + win + [1])
+    return warped[0], (None if photo is None else photo[0])
+
+
 def augment_sums(img1_u8: torch.Tensor, img2_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Exact per-channel integer sums of two batches of (B, Hs, Ws, 3) uint8 GPU frames ->
     int32 (2, B, 3) (launch 1 of :func:`augment_pairs`; the kernel clears ``out`` itself)."""

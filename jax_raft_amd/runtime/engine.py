@@ -39,7 +39,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from ..models.reference import BidirectionalFlow
+from ..models.reference import BidirectionalFlow, BidirectionalWarp
 from ..models.layers import (
     NORM_BATCH,
     NORM_CUSTOM,
@@ -162,6 +162,10 @@ class _PlanState:
     occ: Optional[torch.Tensor] = None
     thr: Optional[torch.Tensor] = None
     thr_vals: Optional[Tuple[float, float]] = None
+    # ... with ``warp``: the motion-compensated frames (2, B, H0, W0, 3) uint8 (0 = frame 2 sampled with
+    # the flow 1 -> 2) and the photometric sums (2, B, 2) int64 (framewarp.hip)
+    warped: Optional[torch.Tensor] = None
+    photo: Optional[torch.Tensor] = None
 
 
 _VERSION = operator.attrgetter("_version")
@@ -373,10 +377,11 @@ class RaftEngine:
         return (B, H, W, n_iters, bool(all_iters))
 
     def _build_key(self, key: tuple) -> _PlanState:
-        """Key layout: (B, H, W, n, all)[ + ("u8", H0, W0, pt, pl)][ + ("warm",) | ("bidir",)][ + ("pslot", slot)]."""
+        """Key layout: (B, H, W, n, all)[ + ("u8", H0, W0, pt, pl)][ + ("warm",) | ("bidir",) | ("bidir", "warp")]
+        [ + ("pslot", slot)]."""
         src = tuple(key[6:10]) if len(key) >= 10 and key[5] == "u8" else None
         if "bidir" in key[5:]:
-            return self._build_bidir(*key[:5], src)
+            return self._build_bidir(*key[:5], src, warp="warp" in key[5:])
         return self._build(*key[:5], src=src, warm="warm" in key[5:])
 
     @staticmethod
@@ -1146,15 +1151,21 @@ class RaftEngine:
         return st, ((0, 1, 2) if on else (0, 0, 0))
 
     def _build_bidir(self, B: int, H: int, W: int, n_iters: int, all_iters: bool,
-                     src: Optional[Tuple[int, int, int, int]]) -> _PlanState:
+                     src: Optional[Tuple[int, int, int, int]], warp: bool = False) -> _PlanState:
         """The plan of ``forward(bidirectional=True)``: one part whose loop runs both directions at
         batch 2B (:meth:`_build_part` with ``bidir``), so the lane decision, the ConvGRU lowering
         and every tile choice are those of loop batch 2B; ``out`` is (N, 2B, H, W, 2) with 1 -> 2
         in ``[:, :B]`` and 2 -> 1 in ``[:, B:]``.  The epilogue ends with the forward-backward
         check (fbcheck.hip) of the final iteration's two flows, on lane 0 after the last
-        upsampling; it reads them through the output slot, where that replay wrote them."""
+        upsampling; it reads them through the output slot, where that replay wrote them.
+
+        ``warp`` (uint8 frames): the same recording followed, on lane 0 after the check, by the
+        ``memset`` of the photometric sums and one ``warp_frames`` over both directions
+        (framewarp.hip): it samples the frames as uploaded (``inp1`` / ``inp2``) with the same
+        two flows, masked by ``occ``, into the plan's ``warped`` and ``photo``."""
         if self.cp:
             raise NotImplementedError("bidirectional flow is not lowered under context parallelism")
+        assert not warp or src is not None, "warp: uint8 frames only"
         saved, self.split = self.split, 1   # one part (``split`` lays ``out`` by part)
         try:
             on = self.uses_lanes(2 * B, all_iters)
@@ -1176,6 +1187,16 @@ class RaftEngine:
                               [B, H, W] + window + [off, off + B * H * W * 2])
         else:   # a generic mask head writes the captured buffer itself
             plan.add_fb_check([last[:B], last[B:], st.occ, None, st.thr], [B, H, W] + window)
+        if warp:
+            st.warped = torch.zeros((2, B, src[0], src[1], 3), dtype=torch.uint8, device=self.device)
+            st.photo = torch.zeros((2, B, 2), dtype=torch.int64, device=self.device)
+            plan.add_memset([st.photo])
+            frames = [st.inp2, st.inp1, st.inp1, st.inp2]   # src (fw, bw), own (fw, bw)
+            if st.slot_ok:
+                plan.add_warp_frames(frames + [None, None, st.occ, st.warped, st.photo, st.out_slot],
+                                     [B, H, W] + window + [2, off, off + B * H * W * 2])
+            else:
+                plan.add_warp_frames(frames + [last[:B], last[B:], st.occ, st.warped, st.photo], [B, H, W] + window + [2])
         return st
 
     def _build_part(self, st: _PlanState, plan, b0: int, B: int, H: int, W: int, n_iters: int, pt: str,
@@ -1666,7 +1687,7 @@ class RaftEngine:
     @torch.no_grad()
     def forward(self, image1: torch.Tensor, image2: torch.Tensor, num_flow_updates: int = 12,
                 return_all_iters: bool = True, flow_init=None, return_flow_low: bool = False,
-                bidirectional: bool = False, fb_alpha: float = 0.01, fb_beta: float = 0.5):
+                bidirectional: bool = False, fb_alpha: float = 0.01, fb_beta: float = 0.5, warp: bool = False):
         """All ``num_flow_updates`` upsampled flows (N, B, H, W, 2), as the reference
         returns; ``return_all_iters=False`` returns only the final one, (1, B, H, W, 2).
 
@@ -1678,6 +1699,14 @@ class RaftEngine:
         a device tensor, so changing them builds no new plan.  Not with ``flow_init`` /
         ``return_flow_low``, :meth:`pipelined`, context parallelism or the fp32 / mixed engines
         (``NotImplementedError``); such a call forgets the engine's "previous" flow.
+
+        ``bidirectional=True, warp=True`` (uint8 frames; anything else is a ``ValueError``)
+        returns :class:`BidirectionalWarp`: the same four fields, then ``warped_fw`` / ``warped_bw``
+        (B, H0, W0, 3) uint8 -- frame 2 sampled with the flow 1 -> 2 and frame 1 with the flow
+        2 -> 1, occluded and outside pixels taken from the frame itself -- and ``photo`` (2, B, 2)
+        int64, the masked photometric sums (``models/reference.py:warp_frames``), from one more
+        kernel (+ the clear of the sums) at the end of a plan of its own (plan key + "bidir",
+        "warp"); every other plan is recorded as before.
 
         Warm start (video): ``flow_init`` -- a (B, h, w, 2) fp32 tensor in 1/8-resolution
         pixels, channel 0 = x (h, w = the plan's size / 8: the *padded* size for uint8 frames)
@@ -1701,9 +1730,12 @@ class RaftEngine:
             self._last = None
         if self.cp and flow_init is not None:
             raise NotImplementedError("forward(flow_init=...): not with context parallelism (cp_group)")
+        if warp and not bidirectional:
+            raise ValueError("forward(warp=True) requires bidirectional=True (the warp is the last op of the "
+                             "bidirectional plan)")
         if bidirectional:
             return self._forward_bidir(image1, image2, num_flow_updates, return_all_iters, flow_init,
-                                       return_flow_low, fb_alpha, fb_beta)
+                                       return_flow_low, fb_alpha, fb_beta, warp)
         if image1.dtype == torch.uint8 and not self._native_u8:
             a, b, src = self._host_u8(image1, image2)
             res = self.forward(a, b, num_flow_updates, return_all_iters, flow_init, return_flow_low)
@@ -1766,7 +1798,7 @@ class RaftEngine:
         return res
 
     def _forward_bidir(self, image1, image2, n_iters: int, all_iters: bool, flow_init, return_flow_low: bool,
-                       alpha: float, beta: float) -> BidirectionalFlow:
+                       alpha: float, beta: float, warp: bool = False):
         """``forward(bidirectional=True)`` (weights already repacked where stale)."""
         if flow_init is not None or return_flow_low:
             raise NotImplementedError("forward(bidirectional=True): not with flow_init / return_flow_low (the warm "
@@ -1777,9 +1809,12 @@ class RaftEngine:
         if self.precision != "bf16":
             raise NotImplementedError(f"forward(bidirectional=True): not with precision={self.precision!r} (the "
                                       "bidirectional plan is lowered for the bf16 engine only)")
+        if warp and not (image1.dtype == torch.uint8 and image2.dtype == torch.uint8):
+            raise ValueError("forward(bidirectional=True, warp=True) requires uint8 frames (the warp samples the "
+                             f"frames as uploaded), got {image1.dtype}")
         # a later flow_init="previous" must not seed from this call's half-batch
         self._last = None
-        key = self._key(image1, image2, n_iters, all_iters) + ("bidir",)
+        key = self._key(image1, image2, n_iters, all_iters) + (("bidir", "warp") if warp else ("bidir",))
         st = self._plan_state(key, lambda: self._build_key(key))
         st.inp1.copy_(image1)
         st.inp2.copy_(image2)
@@ -1797,6 +1832,9 @@ class RaftEngine:
         occ = st.occ if st.src is None else st.occ[:, :, st.src[2]:st.src[2] + st.src[0], st.src[3]:st.src[3] + st.src[1]]
         occ = occ.bool()   # a fresh tensor either way (the plan's buffer is uint8)
         B = key[0]
+        if warp:   # fresh tensors, copied in stream order
+            warped, photo = st.warped.clone(), st.photo.clone()
+            return BidirectionalWarp(res[:, :B], res[:, B:], occ[0], occ[1], warped[0], warped[1], photo)
         return BidirectionalFlow(res[:, :B], res[:, B:], occ[0], occ[1])
 
     @staticmethod
