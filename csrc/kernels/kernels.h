@@ -153,6 +153,21 @@ int jr_corr_lookup(const void* const* levels, int num_levels, int B, int h, int 
                    const float* coords, void* out, int out_cstride, int lv_bf16, int blocked, hipStream_t stream,
                    const TapsUpd* upd = nullptr);
 
+// On-demand correlation (corr_od.hip): no all-pairs volume, O(P * C) memory.
+// jr_feat_pool: f2 bf16 [B][h][w] rows of C channels (channel stride cs) -> pooled target
+// features p[l - 1], fp32 [B][h >> l][w >> l][C], l = 1 .. num_levels - 1: level l is the 2x2
+// VALID mean of level l - 1 (fp32, floor sizes).  C % 64 == 0.
+int jr_feat_pool(const void* f2, int B, int h, int w, int C, int cs, float* p1, float* p2, float* p3, int num_levels,
+                 hipStream_t stream);
+// jr_lookup_od: jr_corr_lookup's output (and optional fused flow update) computed from the
+// feature maps: per query and level the (2r+2)^2 correlations f1[q] . f2_l[y][x] * scale around
+// floor(coords / 2^l) - r (fp32 accumulation, 0 outside the level map), blended to (2r+1)^2
+// samples.  f1, f2: bf16 [B][h*w] rows of C channels (channel stride fcs); radius 1..4,
+// C % 64 == 0, C <= 512.
+int jr_lookup_od(const void* f1, const void* f2, int fcs, const float* p1, const float* p2, const float* p3,
+                 int num_levels, int B, int h, int w, int C, int radius, float scale, const float* coords, void* out,
+                 int out_cstride, hipStream_t stream, const TapsUpd* upd = nullptr);
+
 // Backward of jr_corr_lookup w.r.t. the levels: accumulates into fp32 dlevels
 // (same shapes as the levels).  gout: bf16 (g_bf16=1) or fp32 [B*nq][gcs].
 int jr_corr_lookup_bwd(void* const* dlevels, int num_levels, int B, int h, int w, int nq, int radius,

@@ -1058,6 +1058,104 @@ static Launch make_lookup(const TList& t, const IList& i, std::vector<at::Tensor
   };
 }
 
+// ---------------------------------------------------- on-demand correlation (corr_od.hip)
+// The pooled target features of level l = 1 .. L-1: fp32, contiguous, >= B * (h >> l) * (w >> l) * C
+static float* check_pooled(const at::Tensor& v, const char* op, int l, int B, int h, int w, int C) {
+  check_f32(v, "pooled features");
+  const int hl = h >> l, wl = w >> l;
+  TORCH_CHECK(hl >= 2 && wl >= 2, op, ": pyramid level too small");
+  TORCH_CHECK(v.numel() >= (int64_t)B * hl * wl * C, op, ": pooled level ", l, " too small");
+  return v.data_ptr<float>();
+}
+static void check_fmap(const at::Tensor& f, const char* op, const char* what, int B, int h, int w, int C) {
+  check_bf16(f, what);
+  TORCH_CHECK(C >= 64 && C % 64 == 0, op, ": feature channels must be a multiple of 64");
+  TORCH_CHECK(cs(f) % 8 == 0 && cs(f) >= C, op, ": ", what, " channel stride");
+  TORCH_CHECK(B >= 1 && h >= 2 && w >= 2 && f.numel() >= (int64_t)B * h * w * cs(f), op, ": ", what, " size");
+}
+
+// t = [f2, p1?, p2?, p3?], i = [B, h, w, C, num_levels]
+static Launch make_feat_pool(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  at::Tensor f2 = opt(t, 0);
+  const int B = (int)i[0], h = (int)i[1], w = (int)i[2], C = (int)i[3], L = (int)i[4];
+  TORCH_CHECK(L >= 1 && L <= 4, "feat_pool: 1..4 levels");
+  check_fmap(f2, "feat_pool", "f2", B, h, w, C);
+  float* p[3] = {nullptr, nullptr, nullptr};
+  for (int l = 1; l < L; ++l) {
+    at::Tensor v = opt(t, l);
+    p[l - 1] = check_pooled(v, "feat_pool", l, B, h, w, C);
+    keep.push_back(v);
+  }
+  keep.push_back(f2);
+  const void* fp = f2.data_ptr();
+  const int fcs = cs(f2);
+  return [=](hipStream_t s, int) { return jr_feat_pool(fp, B, h, w, C, fcs, p[0], p[1], p[2], L, s); };
+}
+
+// t = [coords, out, f1, f2, p1?, p2?, p3?], i = [num_levels, B, h, w, radius, C]: the lookup op's output
+// (bf16 rows [B*h*w][cs(out)]) from the feature maps.  Optional fused flow update as in make_lookup:
+// t[7..12] = taps, bias, flow32, hx, qx?, flow8?; i[6..7] = hx_off, qx_off; t[13]: the odd iterations' flow32
+static Launch make_lookup_od(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  at::Tensor coords = opt(t, 0), out = opt(t, 1), f1 = opt(t, 2), f2 = opt(t, 3);
+  check_f32(coords, "coords"); check_bf16(out, "out");
+  const int L = (int)i[0], B = (int)i[1], h = (int)i[2], w = (int)i[3], r = (int)i[4], C = (int)i[5];
+  const int S = 2 * r + 1;
+  TORCH_CHECK(L >= 1 && L <= 4 && r >= 1 && r <= 4, "lookup_od: levels 1..4, radius 1..4");
+  check_fmap(f1, "lookup_od", "f1", B, h, w, C);
+  check_fmap(f2, "lookup_od", "f2", B, h, w, C);
+  TORCH_CHECK(C <= 512 && cs(f1) == cs(f2), "lookup_od: at most 512 feature channels, one channel stride");
+  const int64_t M = (int64_t)B * h * w;
+  TORCH_CHECK(M < (1LL << 31), "lookup_od: B * h * w must stay below 2^31");
+  TORCH_CHECK(cs(out) % 8 == 0 && cs(out) >= L * S * S, "lookup_od: output channel stride");
+  TORCH_CHECK(out.numel() >= M * cs(out) && coords.numel() >= M * 2, "lookup_od: sizes");
+  const float* p[3] = {nullptr, nullptr, nullptr};
+  for (int l = 1; l < L; ++l) {
+    at::Tensor v = opt(t, 3 + l);
+    p[l - 1] = check_pooled(v, "lookup_od", l, B, h, w, C);
+    keep.push_back(v);
+  }
+  for (auto& v : {coords, out, f1, f2}) keep.push_back(v);
+  TapsUpd upd{};
+  at::Tensor tp = opt(t, 7);
+  if (tp.defined()) {
+    at::Tensor bias = opt(t, 8), f32 = opt(t, 9), hx = opt(t, 10), qx = opt(t, 11), f8 = opt(t, 12);
+    TORCH_CHECK(i.size() >= 8, "lookup_od: the fused flow update needs [.., hx_off, qx_off]");
+    check_f32(tp, "taps"); check_f32(bias, "bias"); check_f32(f32, "flow32"); check_bf16(hx, "hx");
+    TORCH_CHECK(cs(tp) >= 18 && tp.numel() >= M * cs(tp) && bias.numel() >= 2 && f32.numel() >= 2 * M,
+                "lookup_od: fused update needs taps [M][>=18], bias [2], flow32 [M][2]");
+    const int hx_off = (int)i[6], qx_off = (int)i[7];
+    TORCH_CHECK(hx_off >= 0 && hx.numel() >= M * cs(hx) && hx_off + 2 <= cs(hx), "lookup_od: hx");
+    if (qx.defined()) {
+      check_bf16(qx, "qx");
+      TORCH_CHECK(qx_off >= 0 && qx.numel() >= M * cs(qx) && qx_off + 2 <= cs(qx), "lookup_od: qx");
+    }
+    if (f8.defined()) { check_bf16(f8, "flow8"); TORCH_CHECK(f8.numel() >= M * cs(f8) && cs(f8) >= 2, "lookup_od: flow8"); }
+    upd = TapsUpd{tp.data_ptr<float>(), cs(tp), bias.data_ptr<float>(), coords.data_ptr<float>(), f32.data_ptr<float>(),
+                  hx.data_ptr(), cs(hx), hx_off, ptr(qx), cs(qx), qx_off, ptr(f8), cs(f8), 1};
+    for (auto& v : {tp, bias, f32, hx, qx, f8}) if (v.defined()) keep.push_back(v);
+  }
+  float* f32b = nullptr;
+  if (at::Tensor fb = opt(t, 13); fb.defined()) {
+    TORCH_CHECK(upd.on, "lookup_od: an odd-iteration flow32 needs the fused update");
+    check_f32(fb, "flow32 (odd)");
+    TORCH_CHECK(fb.numel() >= M * 2, "lookup_od: odd-iteration flow32 [M][2]");
+    f32b = fb.data_ptr<float>();
+    keep.push_back(fb);
+  }
+  const void* a = f1.data_ptr();
+  const void* b = f2.data_ptr();
+  const int fcs = cs(f1), ocs = cs(out);
+  const float* cp = coords.data_ptr<float>();
+  void* op = out.data_ptr();
+  const float scale = (float)(1.0 / std::sqrt((double)C));
+  return [=](hipStream_t s, int it) {
+    TapsUpd u = upd;
+    u.on = upd.on && it > 0;
+    if (f32b && (it & 1)) u.flow32 = f32b;
+    return jr_lookup_od(a, b, fcs, p[0], p[1], p[2], L, B, h, w, C, r, scale, cp, op, ocs, s, &u);
+  };
+}
+
 // ------------------------------------------------------------------ upsample
 // Upsampled-flow output: a view whose trailing (B, 8h, 8w, 2) block is dense
 // (the engine passes out[:, b0:b1] of the (iters, B_total, H, W, 2) buffer).
@@ -2139,6 +2237,10 @@ static const std::vector<OpRow>& op_table() {
       // a stand-alone lookup applies its fused flow update when one is given (in a plan the
       // update is skipped in loop iteration 0, which has no previous taps): eager iteration 1
       row_ti("lookup", 5, 9, make_lookup, 1),
+      // on-demand correlation: the pooled target features (prologue) and the lookup from the
+      // feature maps (eager iteration 1 for the same reason as lookup)
+      row_ti("feat_pool", 5, 5, make_feat_pool),
+      row_ti("lookup_od", 6, 8, make_lookup_od, 1),
       row_ti("upsample_convex", 4, 4, make_upsample_convex),
       row_tia("convex_head", "alpha", 5, 7, make_convex_head),
       row_ti("upsample_bilinear", 4, 5, make_upsample_bilinear),

@@ -107,6 +107,22 @@ class RAFT(nn.Module):
         ``photo`` (2, B, 2) int64, the masked photometric sums (:func:`reference.warp_frames`) --
         the last kernel of the same plan, or the golden warp elsewhere."""
         image1, image2 = _as_tensor(image1), _as_tensor(image2)
+        corr = check_corr(engine_kw.get("corr", "volume"))
+        if corr == "on_demand":
+            # what the on-demand engine does not lower, refused here (an engine's refusal would read
+            # as "this model cannot be lowered" and fall back to the golden path)
+            if train or engine_kw.get("autograd") or engine_kw.get("fused"):
+                raise NotImplementedError("corr='on_demand': inference only (the lookup from the feature maps has "
+                                          "no backward; not with train / autograd)")
+            if bidirectional:
+                raise NotImplementedError("corr='on_demand': not with bidirectional=True (the bidirectional plan "
+                                          "is lowered for the all-pairs volume only)")
+            if engine_kw.get("precision", "bf16") != "bf16":
+                raise NotImplementedError("corr='on_demand': not with precision='fp32' / 'mixed' (the on-demand "
+                                          "lookup is lowered for the bf16 engine only)")
+            if engine_kw.get("cp_group") is not None:
+                raise NotImplementedError("corr='on_demand': not with context parallelism (cp_group splits the "
+                                          "volume the on-demand path never builds)")
         if warp and not bidirectional:
             raise ValueError("warp=True requires bidirectional=True (the warp uses both flows' occlusion masks)")
         if bidirectional:
@@ -148,8 +164,9 @@ class RAFT(nn.Module):
             # counts outside the fused kernels' tiling): op by op on the same native kernels
             # (convs, correlation pyramid, lookup: ops/functional.py), no graph
             with torch.no_grad():
-                return self.forward_reference(image1, image2, False, num_flow_updates, return_all_iters, **warm)
-        return self.forward_reference(image1, image2, train, num_flow_updates, return_all_iters, **warm)
+                return self.forward_reference(image1, image2, False, num_flow_updates, return_all_iters, **warm,
+                                              corr=corr)
+        return self.forward_reference(image1, image2, train, num_flow_updates, return_all_iters, **warm, corr=corr)
 
     def _forward_bidirectional(self, image1, image2, num_flow_updates, return_all_iters, alpha, beta, engine_kw,
                                warp=False):
@@ -257,11 +274,17 @@ class RAFT(nn.Module):
 
     # ------------------------------------------------------- golden execution
     def forward_reference(self, image1, image2, train: bool, num_flow_updates: int, return_all_iters: bool = True,
-                          flow_init: Optional[torch.Tensor] = None, return_flow_low: bool = False):
+                          flow_init: Optional[torch.Tensor] = None, return_flow_low: bool = False,
+                          corr: str = "volume"):
         """Reference-semantics forward (``model.py:557-605`` with the scan body
         ``UpdateCell.__call__``, ``model.py:495-510``).  ``flow_init`` (B, H/8, W/8, 2):
         ``coords1 = coords0 + flow_init`` (warm start), everything else unchanged;
-        ``return_flow_low``: ``(flows, final coords1 - coords0)``."""
+        ``return_flow_low``: ``(flows, final coords1 - coords0)``.  ``corr="on_demand"``: every
+        lookup is :func:`reference.index_on_demand` on the two feature maps and no correlation
+        pyramid is built (inference only); ``"volume"`` (default) is the reference's path."""
+        on_demand = check_corr(corr) == "on_demand"
+        if on_demand and train:
+            raise NotImplementedError("corr='on_demand': inference only (not with train=True)")
         B, H, W, _ = image1.shape
         if isinstance(flow_init, str):
             raise ValueError(f"flow_init={flow_init!r} is a mode of the native engine; this path takes a tensor")
@@ -272,7 +295,7 @@ class RAFT(nn.Module):
         fmaps = self.feature_encoder(torch.cat([image1, image2], dim=0), train)
         fmap1, fmap2 = torch.chunk(fmaps, 2, dim=0)
         assert tuple(fmap1.shape[1:3]) == (H // 8, W // 8), "The feature encoder should downsample H and W by 8"
-        pyramid = self.corr_block.build_pyramid(fmap1, fmap2)
+        pyramid = None if on_demand else self.corr_block.build_pyramid(fmap1, fmap2)
         ctx = self.context_encoder(image1, train)
         assert tuple(ctx.shape[1:3]) == (H // 8, W // 8), "The context encoder should downsample H and W by 8"
         hs = self.update_block.hidden_state_size
@@ -287,7 +310,10 @@ class RAFT(nn.Module):
         preds = []
         for it in range(num_flow_updates):
             coords1 = coords1.detach()  # stop_gradient, model.py:498
-            corr = self.corr_block.index_pyramid(pyramid, coords1)
+            if on_demand:
+                corr = R.index_on_demand(fmap1, fmap2, coords1, self.corr_block.radius, self.corr_block.num_levels)
+            else:
+                corr = self.corr_block.index_pyramid(pyramid, coords1)
             flow = coords1 - coords0
             hidden, delta = self.update_block(hidden, context, corr, flow, train)
             coords1 = coords1 + delta
@@ -324,6 +350,14 @@ class RAFT(nn.Module):
             if "_engines" in self.__dict__:
                 self.__dict__["_engines"] = {}
         super().__setattr__(name, value)
+
+
+def check_corr(corr) -> str:
+    """``corr``: "volume" (the all-pairs correlation pyramid) or "on_demand" (lookups computed from
+    the feature maps), else ``ValueError``."""
+    if corr not in ("volume", "on_demand"):
+        raise ValueError(f"corr must be 'volume' or 'on_demand', got {corr!r}")
+    return corr
 
 
 def check_flow_init(flow_init, B: int, H: int, W: int) -> torch.Tensor:

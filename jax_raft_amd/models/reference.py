@@ -29,6 +29,7 @@ __all__ = [
     "corr_volume",
     "build_pyramid",
     "index_pyramid",
+    "index_on_demand",
     "neighborhood_offsets",
     "forward_project",
     "fill_offsets",
@@ -355,6 +356,73 @@ def index_pyramid(pyramid: Sequence[torch.Tensor], coords: torch.Tensor, radius:
         sc = c + delta
         s = grid_sample(vol.unsqueeze(-1), sc).reshape(B, h, w, side * side)
         out.append(s)
+        c = c / 2
+    return torch.cat(out, dim=-1)
+
+
+def pool_features(fmap: torch.Tensor, num_levels: int) -> List[torch.Tensor]:
+    """The target features of every pyramid level: level 0 is ``fmap`` (B, h, w, C), level l+1 the
+    2x2/stride-2 VALID (floor) mean of level l, sizes ``h >> l, w >> l`` -- what
+    :func:`build_pyramid` does to the volume's target dims, applied to the features."""
+    levels = [fmap]
+    for _ in range(num_levels - 1):
+        B, h, w, C = fmap.shape
+        hh, ww = h // 2, w // 2
+        fmap = fmap[:, : 2 * hh, : 2 * ww].reshape(B, hh, 2, ww, 2, C).mean(dim=(2, 4))
+        levels.append(fmap)
+    return levels
+
+
+def index_on_demand(fmap1: torch.Tensor, fmap2: torch.Tensor, coords: torch.Tensor, radius: int,
+                    num_levels: int) -> torch.Tensor:
+    """On-demand correlation lookup (original RAFT's ``alternate_corr``; no counterpart in the
+    reference): what ``index_pyramid(build_pyramid(fmap1, fmap2, L), coords, r)`` returns, computed
+    from the two feature maps without the all-pairs volume.  Memory O(P * C) instead of O(P^2).
+
+    Pooling is linear, so the level-l volume cell ``(q; y, x)`` equals the correlation of query
+    ``q`` with the level-l pooled target features (:func:`pool_features`):
+    ``sum_c fmap1[q, c] * f2_l[y, x, c] / sqrt(C)``, and 0 outside the level map.  Per level the
+    ``(2r+2)^2`` integer cells around ``floor(coords / 2^l) - r`` are formed and blended to the
+    ``(2r+1)^2`` samples with :func:`grid_sample`'s weights (all samples of a level share one
+    fractional offset); the channel order ``l*S^2 + i*S + j`` (x offset ``i - r`` slow) is
+    :func:`index_pyramid`'s.  A fixed sequence of fp32 operations; equal to the volume path up
+    to fp32 rounding.
+
+    fmap1, fmap2: (B, h, w, C); coords: (B, h, w, 2) -> (B, h, w, L*(2r+1)^2)"""
+    assert fmap1.shape == fmap2.shape, "Input feature maps should have the same shapes"
+    B, h, w, C = fmap1.shape
+    min_fmap_size = 2 * (2 ** (num_levels - 1))
+    assert h >= min_fmap_size and w >= min_fmap_size, (
+        f"Feature maps are too small for {num_levels} pyramid levels: H and W should be at least "
+        f"{min_fmap_size}; got: {(h, w)}.")
+    assert tuple(coords.shape) == (B, h, w, 2), "coords: (B, h, w, 2)"
+    S = 2 * radius + 1
+    W1 = S + 1
+    dev = coords.device
+    q = fmap1.reshape(B, h * w, 1, C)
+    c = coords.reshape(B, h * w, 2)
+    bidx = torch.arange(B, device=dev).view(B, 1, 1)
+    win = torch.arange(W1, device=dev)
+    out = []
+    for f2 in pool_features(fmap2, num_levels):
+        hl, wl = f2.shape[1:3]
+        x0f = torch.floor(c[..., 0])
+        y0f = torch.floor(c[..., 1])
+        wx = (c[..., 0] - x0f).view(B, h * w, 1, 1)
+        wy = (c[..., 1] - y0f).view(B, h * w, 1, 1)
+        # the integer window base, clamped before it becomes an index (far-outside coordinates)
+        bx = x0f.clamp(-2.0 ** 20, 2.0 ** 20).long() - radius
+        by = y0f.clamp(-2.0 ** 20, 2.0 ** 20).long() - radius
+        xs = (bx.unsqueeze(-1) + win).view(B, h * w, 1, W1)      # window columns
+        ys = (by.unsqueeze(-1) + win).view(B, h * w, W1, 1)      # window rows
+        valid = (xs >= 0) & (xs < wl) & (ys >= 0) & (ys < hl)    # (B, hw, W1, W1) [row, column]
+        lin = (ys.clamp(0, hl - 1) * wl + xs.clamp(0, wl - 1)).view(B, h * w, W1 * W1)
+        feats = f2.reshape(B, hl * wl, C)[bidx.expand_as(lin), lin]              # (B, hw, W1*W1, C)
+        cells = (feats * q).sum(-1) / math.sqrt(C)
+        cells = (cells * valid.view(B, h * w, W1 * W1).to(cells.dtype)).view(B, h * w, W1, W1)
+        v = (1.0 - wy) * cells[:, :, :-1, :] + wy * cells[:, :, 1:, :]           # vertical: rows j, j + 1
+        s = (1.0 - wx) * v[..., :-1] + wx * v[..., 1:]                           # horizontal: columns i, i + 1
+        out.append(s.transpose(2, 3).reshape(B, h, w, S * S))                   # [i (x)][j (y)]
         c = c / 2
     return torch.cat(out, dim=-1)
 

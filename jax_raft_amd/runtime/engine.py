@@ -232,6 +232,13 @@ class RaftEngine:
             the update block runs replicated.  Pyramid memory per rank / world.
             One lane, eager from C++ (the collective sits between the two
             halves of the loop body, ``Plan.run_segment``).
+        corr: "volume" (default: the all-pairs correlation pyramid, built in the prologue) or
+            "on_demand": no volume -- the prologue pools the target features (``feat_pool``)
+            and every iteration's lookup forms the correlations it needs from the two
+            feature maps (``lookup_od``, csrc/kernels/corr_od.hip).  Memory O(P * C) instead
+            of O(P^2); every other op of the plan is the volume plan's.  Cold and warm
+            forwards, float and uint8 frames, both output modes; not with ``bidirectional``,
+            :meth:`pipelined`, ``cp_group`` or the fp32 / mixed engines (``NotImplementedError``).
         precision: "bf16" (default: bf16 MFMA operands and activations, fp32
             accumulation, fp32 hidden state / flow / upsampled output) or "fp32"
             (the reference's own precision end to end on the f32 MFMA:
@@ -281,7 +288,23 @@ class RaftEngine:
     def __init__(self, model, device, use_graph: bool = True, copy_output: bool = True,
                  corr_dtype: torch.dtype = torch.bfloat16, gate_dtype: torch.dtype = torch.bfloat16,
                  autotune: bool = True, streams="auto", split: int = 1,
-                 cfg_override: Optional[Dict[str, int]] = None, precision: str = "bf16", cp_group=None):
+                 cfg_override: Optional[Dict[str, int]] = None, cp_group=None, **mode):
+        # the two keywords that select the engine's variant: ``precision`` (already consumed by
+        # __new__, which picked the class) and ``corr``
+        mode.pop("precision", None)
+        corr = mode.pop("corr", "volume")
+        if mode:
+            raise TypeError(f"RaftEngine: unexpected keyword arguments {sorted(mode)}")
+        if corr not in ("volume", "on_demand"):
+            raise ValueError(f"corr must be 'volume' or 'on_demand', got {corr!r}")
+        if corr == "on_demand":
+            if self.precision != "bf16":
+                raise NotImplementedError(f"corr='on_demand': not with precision={self.precision!r} (the on-demand "
+                                          "lookup is lowered for the bf16 engine only)")
+            if cp_group is not None:
+                raise NotImplementedError("corr='on_demand': not with context parallelism (cp_group splits the "
+                                          "volume the on-demand path never builds)")
+        self.corr_mode = corr
         nat.require()
         self._init_cp(cp_group)
         assert streams in (True, False, "auto"), streams
@@ -1368,15 +1391,21 @@ class RaftEngine:
         slabs = self._cp_slabs(h) if self.cp else [(0, h)]
         r0, r1 = slabs[self.cp_rank]
         nq = (r1 - r0) * w
+        on_demand = self.corr_mode == "on_demand"
+        assert not (on_demand and (bidir or self.cp)), "on-demand plans: one direction, no context parallelism"
         levels = []
         hl, wl = h, w
-        for l in range(L):
+        # on demand: no volume -- the pooled target features of levels 1 .. L-1 (fp32) instead
+        pooled = [alloc(f"fpool.l{l}", (Bi, h >> l, w >> l, self.fmap_ch), F32) for l in range(1, L)] if on_demand else []
+        for l in range(0 if on_demand else L):
             shape = (M, -(-h // 8) * (8 >> l), -(-w // 16) * (16 >> l)) if blocked and l < 2 else (B * nq, hl, wl)
             levels.append(alloc(f"corr.l{l}", shape, self.corr_dtype))
             hl //= 2
             wl //= 2
         scale = 1.0 / float(self.fmap_ch) ** 0.5
-        if self.cp:
+        if on_demand:
+            plan.add_feat_pool([fmap[Bi:]] + pooled, [Bi, h, w, self.fmap_ch, L])
+        elif self.cp:
             for b in range(B):
                 plan.add_corr([fmap[b, r0:r1], fmap[B + b]] + [v[b * nq:(b + 1) * nq] for v in levels] + [None] * (4 - L),
                               [1, h, w, self.fmap_ch, L, nq, 0], scale)
@@ -1508,6 +1537,10 @@ class RaftEngine:
             if with_update and parity:
                 upd.append(flow32b)   # t[12]: the odd iterations' flow
             extra = [self.flow_off, self.flow_off] if with_update else []
+            if on_demand:
+                plan.add_lookup_od([coords, corr, fmap[:Bi], fmap[Bi:]] + pooled + [None] * (4 - L) + upd,
+                                   [L, B, h, w, self.radius, self.fmap_ch] + extra)
+                return
             plan.add_lookup([coords, corr] + levels + [None] * (4 - L) + upd,
                             [L, B, h, w, self.radius, h * w, blocked] + extra)
 
@@ -1733,6 +1766,9 @@ class RaftEngine:
         if warp and not bidirectional:
             raise ValueError("forward(warp=True) requires bidirectional=True (the warp is the last op of the "
                              "bidirectional plan)")
+        if bidirectional and self.corr_mode == "on_demand":
+            raise NotImplementedError("forward(bidirectional=True): not with corr='on_demand' (the bidirectional "
+                                      "plan is lowered for the all-pairs volume only)")
         if bidirectional:
             return self._forward_bidir(image1, image2, num_flow_updates, return_all_iters, flow_init,
                                        return_flow_low, fb_alpha, fb_beta, warp)
@@ -1914,6 +1950,9 @@ class RaftEngine:
         if bidirectional:
             raise NotImplementedError("pipelined(bidirectional=True): the bidirectional plan (its second correlation "
                                       "launch and epilogue check) is not lowered for pipelined slots; use forward()")
+        if self.corr_mode == "on_demand":
+            raise NotImplementedError("pipelined(): not with corr='on_demand' (a slot's prologue is not lowered for "
+                                      "the pooled target features); use forward()")
         if self._stale():
             self._last = None
             if self._pp is not None and self._pp["pending"] is not None:
