@@ -25,11 +25,17 @@
 // reads the tile's h while it is replaced (tap neighbours never leave the
 // tile), so h' is written in place.
 //
+// The 1x5 stage can also compute its own x (template flag ME, op gru_fused_me): x's motion
+// channels are a 3x3 conv of cf (the motion encoder's output conv, model.py:275-289), and a row's
+// x needs only cf rows y - 1 .. y + 1, so the row workgroup runs that conv as a 128 x 128 x 2304
+// GEMM in front of GEMM 1 -- no launch, no tail and no round trip of x between the two.
+//
 // MFMA: v_mfma_f32_32x32x16_bf16, operands staged as in kernel M32
 // (conv_igemm.h: 64-deep K stages, register-staged global loads two stages
 // ahead, double-buffered LDS with the swzB swizzle, permuted weight rows from
 // ops/native.py:pack_weight so each lane owns 16 contiguous channels).
 #include <cstdlib>
+#include <type_traits>
 
 #include "conv_igemm.h"
 
@@ -60,8 +66,13 @@ JR_DEVICE void load_map(const GruFusedParams& p, int m, int c, float* v) {
   else load_f32<NV>((const float*)p.bmap + o, v);
 }
 
-template <bool G2ALL>
-__global__ __launch_bounds__(1024) void gru_fused_kernel(const GruFusedParams p) {
+// ME: the motion encoder's output conv runs first (GruFusedMeParams; rows only, G2ALL)
+template <bool G2ALL, bool ME = false>
+__global__ __launch_bounds__(1024) void gru_fused_kernel(const std::conditional_t<ME, GruFusedMeParams, GruFusedParams> pp) {
+  const GruFusedParams& p = [&]() -> const GruFusedParams& {
+    if constexpr (ME) return pp.g;
+    else return pp;
+  }();
   __shared__ __attribute__((aligned(16))) bf16 smem[2 * ASTAGE + IMG_ROWS * CIN];
   bf16* const img = smem + 2 * ASTAGE;   // the tile's [h | x] rows (+ zero pad rows); h -> r*h after GEMM 1
 
@@ -70,7 +81,7 @@ __global__ __launch_bounds__(1024) void gru_fused_kernel(const GruFusedParams p)
   const int rho = lane & 31, hh = lane >> 5;
   const int tile = blockIdx.x;
   auto stamp = [&](int k) {
-    if (p.dbg && tid == 0) p.dbg[tile * 6 + k] = (long long)wall_clock64();
+    if (p.dbg && tid == 0) p.dbg[tile * (ME ? 8 : 6) + k] = (long long)wall_clock64();
   };
   stamp(0);
   const int n = tile / p.tiles_per_img, tt = tile - n * p.tiles_per_img;
@@ -100,10 +111,10 @@ __global__ __launch_bounds__(1024) void gru_fused_kernel(const GruFusedParams p)
   // it too and its r*h channels from the h part, which epilogue 1 overwrites with r*h.  (The
   // round-4 form staged B per K stage from global memory: 5 x the tile's bytes per GEMM.)
   constexpr int NIMG = (IMG_ROWS * 32 + 1023) / 1024;
-  u32x4 iv[NIMG];
+  [[maybe_unused]] u32x4 iv[NIMG];
   const int nrow = p.J * (p.L + 4);
 #pragma unroll
-  for (int k = 0; k < NIMG; ++k) {
+  for (int k = 0; k < (ME ? 0 : NIMG); ++k) {
     const int idx = k * 1024 + tid, R = idx >> 5, c = idx & 31;
     const int j = R / (p.L + 4), r = R - j * (p.L + 4) - 2;
     const bool in = R < nrow && (unsigned)r < (unsigned)p.L;
@@ -125,10 +136,6 @@ __global__ __launch_bounds__(1024) void gru_fused_kernel(const GruFusedParams p)
     putA(sA_of(buf), lrow + 128, r.a1);
   };
   f32x16 acc[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int k = 0; k < 16; ++k) acc[t][k] = 0.f;
   const int prow = wp * 32 + rho;   // this lane's pixel row in the tile
   const int m = pix(prow);
   const int jrun = prow / p.L;
@@ -174,17 +181,178 @@ __global__ __launch_bounds__(1024) void gru_fused_kernel(const GruFusedParams p)
     }
   };
   u32x4 bm1[2][2];
-  {
-    Regs ra, rb;
+  Regs ra, rb;
+  if constexpr (ME) {
+    // ------------------------------------------------------- motion conv (pre-GEMM)
+    // x[:, 0:cout) = relu(conv3x3(cf) + bias) of this row: 128 (padded) channels x 128 px,
+    // K = 9 x 256 tap-major as conv_halo.hip runs it (u, v, then channels in k16 steps, one
+    // accumulator chain), waves tiled 4 x 32 channels x 4 x 32 pixels as GEMM 2 (G2ALL).
+    // A: pack_weight rows through GEMM 2's two staging buffers.  B: one cf row (130 zero-padded
+    // pixels x 256 channels) at a time in the tile image's space, which nothing needs before the
+    // conv is done; the next row waits in registers behind the MFMAs.
+    constexpr int KME = 9 * CIN, NSME = KME / BK, CF_ROWS = 130;
+    constexpr int NCF = (CF_ROWS * 32 + 1023) / 1024;
+    constexpr int NHI = (IMG_ROWS * 16 + 1023) / 1024;
+    const __amdgpu_buffer_rsrc_t cfs = __builtin_amdgcn_make_buffer_rsrc((void*)pp.cf, (short)0, (int)pp.cf_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wms = __builtin_amdgcn_make_buffer_rsrc((void*)pp.wm, (short)0, (int)pp.wm_bytes, 0x00020000);
+    const unsigned moff = (unsigned)(lrow * KME * 2 + ch * 16);
+    auto issueM = [&](u32x4& r, int s) {
+      r = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wms, s < NSME ? moff + (unsigned)s * (BK * 2u) : OOB, 0, 0));
+    };
+    auto sAm = [&](int buf) { return smem + buf * (HD * BK); };
+    u32x4 cv[NCF];
+    // cf row tt + u - 1 -> registers: buffer row R = pixel R - 1; zero outside the image
+    auto cfload = [&](int u) {
+      const int yy = tt + u - 1;
+      const bool yin = (unsigned)yy < (unsigned)p.H;
+#pragma unroll
+      for (int k = 0; k < NCF; ++k) {
+        const int idx = k * 1024 + tid, R = idx >> 5, c = idx & 31;
+        const bool in = yin && (unsigned)(R - 1) < (unsigned)p.W;
+        const int mm = (n * p.H + yy) * p.W + R - 1;
+        cv[k] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+            cfs, in ? (unsigned)mm * (unsigned)pp.cf_cs * 2u + (unsigned)c * 16u : OOB, 0, 0));
+      }
+    };
+    auto cfstore = [&]() {
+#pragma unroll
+      for (int k = 0; k < NCF; ++k) {
+        const int idx = k * 1024 + tid, R = idx >> 5, c = idx & 31;
+        if (R < CF_ROWS) *(u32x4*)(img + img_off(R, c)) = cv[k];
+      }
+    };
+    const int prowM = (wave >> 2) * 32 + rho;
+    const int arowM = 64 * (wco >> 1) + m32_arow(wco & 1, rho);   // channels 32 wco + ..
+    f32x16 accm;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) accm[k] = 0.f;
+    // stage j of a tap row: tap column j / 4 (the pixel row shifted by it), 64-channel block j % 4
+    auto computeM = [&](int buf, int j) {
+      const bf16* sA = sAm(buf);
+      const int row = prowM + (j >> 2);
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const int chunk = kk * 2 + hh;
+        const bf16x8 b = *(const bf16x8*)(img + img_off(row, (j & 3) * 8 + chunk));
+        const bf16x8 a = *(const bf16x8*)(sA + arowM * BK + ((chunk ^ swzA(arowM)) << 3));
+        accm = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, accm, 0, 0, 0);
+      }
+    };
+    // the bias waits in LDS behind the two staging buffers (free until GEMM 1's second stage)
+    float* const bl = (float*)(smem + 2 * HD * BK);
+    const float bias_t = pp.bias[(tid & (HD - 1)) < pp.cout ? (tid & (HD - 1)) : pp.cout - 1];
+    u32x4 ma, mb;
+    cfload(0);
+    issueM(ma, 0);
+    issueM(mb, 1);
+    cfstore();
+    if (tid < HD) bl[tid] = bias_t;
+    cfload(1);
+    putA(sAm(0), lrow, ma);
+    __syncthreads();
+    stamp(6);   // first cf row and weight stage landed
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      const int jend = u == 2 ? 10 : 12;
+#pragma nounroll
+      for (int j = 0; j < jend; j += 2) {
+        issueM(ma, u * 12 + j + 2);
+        computeM(0, j);
+        putA(sAm(1), lrow, mb);
+        __syncthreads();
+        issueM(mb, u * 12 + j + 3);
+        computeM(1, j + 1);
+        putA(sAm(0), lrow, ma);
+        __syncthreads();
+      }
+      if (u < 2) {   // every wave is past the row's last read (the barrier above)
+        cfstore();
+        if (u == 0) cfload(2);
+        __syncthreads();
+      }
+    }
+    // last two stages: no operand loads left; the epilogue's operands, the image's h half and
+    // GEMM 1's first two weight stages load instead (all unconditional, see pre_map)
+    const int mM = pix(prowM), mldM = mM >= 0 ? mM : 0;
+    const int c0 = 32 * wco + 16 * hh;
+    u32x4 xh[2];   // this lane's x channels as they are in hx: channels >= cout (the flow) stay
+    {
+      const u32x4* q = (const u32x4*)((const bf16*)p.hx + (long)mldM * p.hx_cs + HD + c0);
+      xh[0] = q[0];
+      xh[1] = q[1];
+    }
+    u32x4 hv[NHI];
+#pragma unroll
+    for (int k = 0; k < NHI; ++k) {
+      const int idx = k * 1024 + tid, R = idx >> 4, c = idx & 15;
+      const bool in = R < nrow && (unsigned)(R - 2) < (unsigned)p.L;
+      const int mm = in ? pix(R - 2) : 0;
+      hv[k] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+          xs, in ? (unsigned)mm * (unsigned)p.hx_cs * 2u + (unsigned)c * 16u : OOB, 0, 0));
+    }
     issue1(ra, 0);
     issue1(rb, 1);
+    computeM(0, 10);
+    putA(sAm(1), lrow, mb);
+    __syncthreads();
+    computeM(1, 11);
+    __syncthreads();   // the cf row and the staging buffers are free
+    // epilogue: bias, relu, bf16 -> the image's x half and hx; lane: channels c0 + [0, 16) of pixel prowM
+    float bv[16];
 #pragma unroll
-    for (int k = 0; k < NIMG; ++k) {
-      const int idx = k * 1024 + tid, R = idx >> 5, c = idx & 31;
-      if (R < IMG_ROWS) *(u32x4*)(img + img_off(R, c)) = iv[k];
+    for (int k = 0; k < 4; ++k) *(f32x4*)(bv + 4 * k) = *(const f32x4*)(bl + c0 + 4 * k);
+    bf16x8 o[2];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const bf16 keep = __builtin_bit_cast(bf16x8, xh[k >> 3])[k & 7];
+      o[k >> 3][k & 7] = c0 + k < pp.cout ? f2bf(fmaxf(accm[k] + bv[k], 0.f)) : keep;
+    }
+    if (mM < 0) {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) o[k >> 3][k & 7] = f2bf(0.f);
+    } else {
+      bf16* yp = (bf16*)p.hx + (long)mM * p.hx_cs + HD + c0;
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        if (c0 + 8 * q + 8 <= pp.cout) {
+          *(bf16x8*)(yp + 8 * q) = o[q];
+        } else {
+#pragma unroll
+          for (int k = 0; k < 8; ++k)
+            if (c0 + 8 * q + k < pp.cout) yp[8 * q + k] = o[q][k];
+        }
+      }
+    }
+    *(bf16x8*)(img + img_off(prowM + 2, 16 + (c0 >> 3))) = o[0];
+    *(bf16x8*)(img + img_off(prowM + 2, 17 + (c0 >> 3))) = o[1];
+    if (tid < 128) {   // x half of the rows no pixel owns: 0, 1 and 130 .. 135
+      const int R = tid >> 4;
+      const u32x4 zero = {0u, 0u, 0u, 0u};
+      *(u32x4*)(img + img_off(R < 2 ? R : 128 + R, 16 + (tid & 15))) = zero;
+    }
+#pragma unroll
+    for (int k = 0; k < NHI; ++k) {
+      const int idx = k * 1024 + tid, R = idx >> 4, c = idx & 15;
+      if (R < IMG_ROWS) *(u32x4*)(img + img_off(R, c)) = hv[k];
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc[t][k] = 0.f;
+  {
+    if constexpr (!ME) {
+      issue1(ra, 0);
+      issue1(rb, 1);
+#pragma unroll
+      for (int k = 0; k < NIMG; ++k) {
+        const int idx = k * 1024 + tid, R = idx >> 5, c = idx & 31;
+        if (R < IMG_ROWS) *(u32x4*)(img + img_off(R, c)) = iv[k];
+      }
     }
     store1(ra, 0);
     __syncthreads();
+    stamp(5);   // tile image and the first weight stage landed
 #pragma nounroll
     for (int s = 0; s < NSTG - 2; s += 2) {
       issue1(ra, s + 2);
@@ -368,7 +536,14 @@ extern "C" int jr_gru_fused(const GruFusedParams* p, hipStream_t stream) {
   if (p->ntiles <= 0) return 0;
   // GEMM 2 on all 16 waves with z through LDS (the engine's choice) or on the 8 z waves with z
   // in registers (p->g2all = 0; profiles/r3_gru_fused_ab.txt)
-  if (p->g2all) hipLaunchKernelGGL(gru_fused_kernel<true>, dim3(p->ntiles), dim3(1024), 0, stream, *p);
-  else hipLaunchKernelGGL(gru_fused_kernel<false>, dim3(p->ntiles), dim3(1024), 0, stream, *p);
+  if (p->g2all) hipLaunchKernelGGL((gru_fused_kernel<true>), dim3(p->ntiles), dim3(1024), 0, stream, *p);
+  else hipLaunchKernelGGL((gru_fused_kernel<false>), dim3(p->ntiles), dim3(1024), 0, stream, *p);
+  return (int)hipGetLastError();
+}
+
+extern "C" int jr_gru_fused_me(const GruFusedMeParams* p, hipStream_t stream) {
+  if (p->g.ntiles <= 0) return 0;
+  if (p->g.vertical || !p->g.g2all || p->g.J != 1 || p->cout < 1 || p->cout > HD) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL((gru_fused_kernel<true, true>), dim3(p->g.ntiles), dim3(1024), 0, stream, *p);
   return (int)hipGetLastError();
 }

@@ -454,9 +454,24 @@ struct GruFusedParams {
   int L, J, tiles_per_img, ntiles;    // run length (W or H), runs per tile (J * L <= 128)
   int g2all;                          // 1: GEMM 2 on all 16 waves (z through LDS); 0: on the 8 z waves
   long hx_bytes, wa_bytes, wb_bytes;
-  long long* dbg;                     // optional [ntiles][6] phase timestamps (s_memrealtime, tools/gru_phases.py)
+  long long* dbg;                     // optional [ntiles][6] ([8] with the motion conv) phase timestamps (tools/gru_phases.py)
 };
 int jr_gru_fused(const GruFusedParams* p, hipStream_t stream);
+
+// The 1x5 stage above with the motion encoder's output conv in front of it (one launch): the row
+// workgroup first computes x[:, 0:cout) = relu(conv3x3(cf) + bias) of its own row from cf rows
+// y - 1 .. y + 1 (K order and accumulation of conv_halo.hip, so the same bf16 values), writes it
+// into its tile image and to hx channels [128, 128 + cout), and reads x channels [cout, 128) (the
+// flow) from hx.  g.vertical == 0, g.g2all == 1.
+struct GruFusedMeParams {
+  GruFusedParams g;
+  const void* cf; int cf_cs;          // bf16 [M][cf_cs]: the motion conv's input, channels [0, 256)
+  const void* wm;                     // pack_weight of the 3x3 conv: [128][9 * 256]
+  const float* bias;                  // fp32 [cout]
+  int cout;                           // 1 .. 128 motion channels
+  long cf_bytes, wm_bytes;
+};
+int jr_gru_fused_me(const GruFusedMeParams* p, hipStream_t stream);
 
 // Halo-tiled fused ConvGRU stage (gru_halo.hip) for ANY /8 map size and both RAFT
 // recurrent blocks: raft_large's 1x5 / 5x1 stages (mode 0: a run of L pixels along the

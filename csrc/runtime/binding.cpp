@@ -655,13 +655,15 @@ bool gru_fused_fits(int64_t H, int64_t W, int64_t vertical) {
 // i = [N, H, W, vertical(, g2all)].  Tiles: a row (1x5, W <= 128) or J = 2 / 1 columns (5x1, J * H <= 128).
 // g2all (default 1): GEMM 2 on all 16 waves with z through LDS; 0: on the 8 z waves, z in registers
 // (measured 334-341 vs 335 pairs/s at the headline, profiles/r3_gru_fused_ab.txt; kept for the tests).
-static Launch make_gru_fused(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+// the checked operands t[0 .. 7] of a stage; dbg_slots: phase timestamps per tile
+static GruFusedParams gru_fused_params(const TList& t, int N, int H, int W, int vertical, int g2all, int dbg_slots,
+                                       std::vector<at::Tensor>& keep) {
   at::Tensor hx = opt(t, 0), wa = opt(t, 1), wb = opt(t, 2), bmap = opt(t, 3), h32 = opt(t, 4), y = opt(t, 5),
              y2 = opt(t, 6), dbg = opt(t, 7);
   check_bf16(hx, "hx"); check_bf16(wa, "wa"); check_bf16(wb, "wb"); check_f32(h32, "h32"); check_bf16(y, "y");
   GruFusedParams p{};
-  p.N = (int)i[0]; p.H = (int)i[1]; p.W = (int)i[2]; p.vertical = (int)i[3];
-  p.g2all = i.size() == 5 ? (int)(i[4] != 0) : 1;
+  p.N = N; p.H = H; p.W = W; p.vertical = vertical;
+  p.g2all = g2all;
   const int64_t M = (int64_t)p.N * p.H * p.W;
   TORCH_CHECK(gru_fused_fits(p.H, p.W, p.vertical), "gru_fused: the tile geometry does not fit (", p.H, "x", p.W, ")");
   TORCH_CHECK(cs(hx) == 256 && hx.numel() >= M * 256 && reinterpret_cast<uintptr_t>(hx.data_ptr()) % 16 == 0,
@@ -689,12 +691,19 @@ static Launch make_gru_fused(const TList& t, const IList& i, std::vector<at::Ten
   else { p.L = p.H; p.J = 2 * p.H <= 128 && p.W % 2 == 0 ? 2 : 1; p.tiles_per_img = p.W / p.J; }
   p.ntiles = p.N * p.tiles_per_img;
   if (dbg.defined()) {   // phase timestamps (tools/gru_phases.py)
-    TORCH_CHECK(dbg.is_cuda() && dbg.scalar_type() == at::kLong && dbg.numel() >= (int64_t)p.ntiles * 6, "gru_fused: dbg");
+    TORCH_CHECK(dbg.is_cuda() && dbg.scalar_type() == at::kLong && dbg.numel() >= (int64_t)p.ntiles * dbg_slots, "gru_fused: dbg");
     p.dbg = (long long*)dbg.data_ptr();
   }
   p.hx_bytes = (long)hx.numel() * 2; p.wa_bytes = (long)wa.numel() * 2; p.wb_bytes = (long)wb.numel() * 2;
   TORCH_CHECK(p.hx_bytes < (1LL << 31), "gru_fused: hx larger than 2 GiB");
   for (auto& v : {hx, wa, wb, bmap, h32, y, y2}) if (v.defined()) keep.push_back(v);
+  return p;
+}
+
+static Launch make_gru_fused(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  const GruFusedParams p = gru_fused_params(t, (int)i[0], (int)i[1], (int)i[2], (int)i[3],
+                                            i.size() == 5 ? (int)(i[4] != 0) : 1, 6, keep);
+  at::Tensor y2 = opt(t, 6);
   // optional t[8]: the y2 copy of ODD loop iterations (a parity-buffered h copy for the mask lane,
   // runtime/engine.py: the lane reads iteration i's copy while iteration i+1 writes the other one)
   at::Tensor y2b = opt(t, 8);
@@ -709,6 +718,31 @@ static Launch make_gru_fused(const TList& t, const IList& i, std::vector<at::Ten
     return [p, q](hipStream_t s, int it) { return jr_gru_fused((it & 1) ? &q : &p, s); };
   }
   return [p](hipStream_t s, int) { return jr_gru_fused(&p, s); };
+}
+
+// The 1x5 fused ConvGRU stage with the motion encoder's output conv in front (gru_fused.hip, ME).
+// t = gru_fused's [hx, wa, wb, bmap, h32, y, y2?, dbg? ([tiles][8])] + [cf (bf16 [M][>=256]: the 3x3
+// conv's input), wm (pack_weight of the (3, 3, 256, cout) kernel: [128][2304]), bias (fp32 [cout])],
+// i = [N, H, W, cout].  Writes x = relu(conv3x3(cf) + bias) to hx channels [128, 128 + cout) (and
+// leaves [128 + cout, 256), the flow, as it is), then runs the stage on [h | x].
+static Launch make_gru_fused_me(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  GruFusedMeParams p{};
+  p.g = gru_fused_params(t, (int)i[0], (int)i[1], (int)i[2], 0, 1, 8, keep);
+  at::Tensor cf = opt(t, 8), wm = opt(t, 9), bias = opt(t, 10);
+  check_bf16(cf, "cf"); check_bf16(wm, "wm"); check_f32(bias, "bias");
+  p.cout = (int)i[3];
+  const int64_t M = (int64_t)p.g.N * p.g.H * p.g.W;
+  TORCH_CHECK(p.cout >= 1 && p.cout <= 128 && bias.numel() >= p.cout, "gru_fused_me: 1 .. 128 output channels with a bias each");
+  TORCH_CHECK(cs(cf) >= 256 && cs(cf) % 8 == 0 && cf.numel() >= M * cs(cf) && reinterpret_cast<uintptr_t>(cf.data_ptr()) % 16 == 0,
+              "gru_fused_me: cf must be [M][>=256]");
+  TORCH_CHECK(wm.numel() == 128 * 2304 && reinterpret_cast<uintptr_t>(wm.data_ptr()) % 16 == 0,
+              "gru_fused_me: packed 3x3 weights [128][2304]");
+  TORCH_CHECK(p.g.y == p.g.hx, "gru_fused_me: the stage runs in place (y is hx)");
+  p.cf = cf.data_ptr(); p.cf_cs = cs(cf); p.wm = wm.data_ptr(); p.bias = bias.data_ptr<float>();
+  p.cf_bytes = (long)cf.numel() * 2; p.wm_bytes = (long)wm.numel() * 2;
+  TORCH_CHECK(p.cf_bytes < (1LL << 31), "gru_fused_me: cf larger than 2 GiB");
+  keep.push_back(cf); keep.push_back(wm); keep.push_back(bias);
+  return [p](hipStream_t s, int) { return jr_gru_fused_me(&p, s); };
 }
 
 // Halo-tiled fused ConvGRU stage (gru_halo.hip).
@@ -2262,6 +2296,7 @@ static const std::vector<OpRow>& op_table() {
       row_ti("flow_taps", 5, 5, make_flow_taps),
       row_ti("taps_gemm", 3, 3, make_taps_gemm),
       row_ti("gru_fused", 4, 5, make_gru_fused),
+      row_ti("gru_fused_me", 4, 4, make_gru_fused_me),
       row_ti("gru_halo", 9, 9, make_gru_halo),
       row_ti("conv1x1", 6, 6, make_conv1x1),
       row_ti("conv_direct", 11, 11, make_conv_direct),

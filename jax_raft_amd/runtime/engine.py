@@ -276,6 +276,7 @@ class RaftEngine:
     # can cover the alternative lowering against the same oracle (monkeypatch.setattr on the
     # class, before the plan is built).  Operational environment variables: jax_raft_amd/knobs.py.
     GRU = "auto"          # ConvGRU stage lowering: "auto" | "halo" | "fused" | "unfused" (_gru_path)
+    GRU_ME = "auto"       # motion conv inside the first fused ConvGRU stage: "auto" | "on" | "off" (_gru_me_ok)
     PRO_LANES = "auto"    # prologue branches on lanes at one-lane loops: "auto" | "on" | "off"
     HALO_NORM = True      # encoder instance norms fused into the halo 3x3 convs
     MERGED_UP = True      # one-lane loop: 7x7 flow conv merged with the x8 upsampling (merged.hip)
@@ -1115,6 +1116,24 @@ class RaftEngine:
         tiles = min(nat.gru_fused_tiles(B, h, w, 0), nat.gru_fused_tiles(B, h, w, 1))
         return tiles > 0 and (env == "1" or tiles >= 3 * nat.NUM_CUS // 4)
 
+    def _gru_me_ok(self, B: int, h: int, w: int) -> bool:
+        """With the "fused" ConvGRU lowering: whether the motion encoder's output conv runs
+        inside the first stage's kernel (gru_fused.hip, op ``gru_fused_me``) instead of as a
+        launch of its own.  The row workgroup then does the whole 3x3 conv of its row, so it
+        needs a 3x3 / pad-1 conv from 256 to <= 128 channels in front of a 1x5 stage, and it
+        pays where the rows fill the GPU (``GRU_ME = "auto"``: the >= 3/4-of-the-CUs rule of
+        _gru_fused_ok; with fewer rows the conv's own 64-pixel tiles spread over more CUs).
+        ``"on"`` forces it where it fits, ``"off"`` keeps the two launches."""
+        assert self.GRU_ME in ("auto", "on", "off"), self.GRU_ME
+        if self.GRU_ME == "off" or self.cp:
+            return False
+        sp = self._specs["me.conv"]
+        ks = tuple(self.model.update_block.recurrent_block.kernel_size[0])
+        if (not (sp.halo_ks == 3 and sp.cin8 == 256 and sp.cout <= 128 and self.mot_off == 128 and self.hx_cs == 256)
+                or ks != (1, 5) or not 1 <= w <= 128):
+            return False
+        return self.GRU_ME == "on" or nat.gru_fused_tiles(B, h, w, 0) >= 3 * nat.NUM_CUS // 4
+
     def uses_lanes(self, B: int, all_iters: bool = True) -> bool:
         """Whether the plan for batch ``B`` runs the model's branches on several
         lanes (``streams`` / its "auto" rule).  Graph-pipelined steps
@@ -1447,6 +1466,8 @@ class RaftEngine:
         if gru_path == "fused" and self.cp:
             gru_path = "unfused"
         self.gru_path = gru_path
+        # the motion conv inside the first fused stage's kernel (gru_fused_me)
+        gru_me = gru_path == "fused" and self._gru_me_ok(B, h, w)
         ngru = len(m.update_block.recurrent_block.kernel_size)
         # the halo kernel cannot update h in place (neighbouring tiles read it): raft_large's
         # stage 1 writes h' into qx, stage 2 reads it there and writes hx; raft_small's single
@@ -1570,8 +1591,9 @@ class RaftEngine:
                 self._conv(plan, *last[:6], **last[6])
             if wait_flow:
                 plan.add_wait(E_FLOW)
-            self._conv(plan, sp["me.conv"], cf, B, h, w, hx, y_coff=self.mot_off, act=ACT_RELU,
-                       y2=qx if qx_x else None, y2_coff=self.mot_off)
+            if not gru_me:
+                self._conv(plan, sp["me.conv"], cf, B, h, w, hx, y_coff=self.mot_off, act=ACT_RELU,
+                           y2=qx if qx_x else None, y2_coff=self.mot_off)
             if gru_path == "halo":
                 _, stages = self._halo_geom()
                 for gi, (mode, axis) in enumerate(stages):
@@ -1594,6 +1616,11 @@ class RaftEngine:
                     if wait_mask and not parity and (last if hm is not None else gi == 0):
                         plan.add_wait(E_MASK)  # the previous iteration's mask head has read hm / h (and flow32)
                     ks = m.update_block.recurrent_block.kernel_size[gi]
+                    if gi == 0 and gru_me:   # stage 1 computes its own motion features (nothing reads qx's copy)
+                        mc = sp["me.conv"]
+                        plan.add_gru_fused_me([hx, sp["gru0.a"].w, sp["gru0.b"].w, gbias[0], h32, hx,
+                                               hm if last else None, None, cf, mc.w, mc.b], [B, h, w, mc.cout])
+                        continue
                     plan.add_gru_fused([hx, sp[f"gru{gi}.a"].w, sp[f"gru{gi}.b"].w, gbias[gi], h32, hx,
                                         hm if last else None] + ([None, hm2] if last and parity else []),
                                        [B, h, w, int(ks[0] > 1)])
