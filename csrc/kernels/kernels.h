@@ -367,6 +367,18 @@ int jr_augment_mixed(const void* img1, const void* img2, const float* flow, cons
 // [B][6] is written, acc fp64 [8] is added to.  Two launches; no atomics, no memset.
 int jr_flow_metrics(const float* pred, const float* gt, const void* valid, const int* sizes, double* part,
                     double* rows, double* acc, int B, int Hp, int Wp, int Hg, int Wg, int NB, hipStream_t stream);
+// Label-free training loss (unsup.hip; train/unsup.py:unsup_loss_reference).  pred fp32 [N][B][H][W][2]
+// (8-byte aligned), img1 / img2 fp32 [B][H][W][3], mask (optional) fp32 [B][H][W], prm fp32 [4] = (eps,
+// eps_s, edge_kappa, out_penalty) on the device; 1 <= N <= 32, B * H * W < 2^31.  jr_unsup_loss writes
+// part fp32 [jr_unsup_loss_blocks(P)][N][4] (16-byte aligned): per block and iteration the sum of
+// mask * pix, the smoothness sum, the count of masked pixels that land outside and, for iteration
+// N - 1, the sum of pix over the inside masked pixels.  jr_unsup_loss_bwd writes grad fp32
+// [N][B][H][W][2] (8-byte aligned) from scale fp32 [N][2] = (photometric, smoothness) factors.
+int jr_unsup_loss_blocks(long P);
+int jr_unsup_loss(const float* pred, const float* img1, const float* img2, const float* mask, const float* prm,
+                  float* part, int B, int H, int W, int N, hipStream_t stream);
+int jr_unsup_loss_bwd(const float* pred, const float* img1, const float* img2, const float* mask, const float* prm,
+                      const float* scale, float* grad, int B, int H, int W, int N, hipStream_t stream);
 // Conv of a 2-channel input (the flow branch's 7x7 / 3x3): x bf16 NHWC
 // [N][H][W][x_cstride] (channels 0, 1 used), stride 1, output H x W; w bf16
 // MFMA A fragments [cout/16][NKC][64 lanes][8] (jax_raft_amd/ops/native.py:

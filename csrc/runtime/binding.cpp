@@ -2140,6 +2140,61 @@ static Launch make_flow_metrics(const TList& t, const IList& i, std::vector<at::
   };
 }
 
+// ---------------------------------------------------------- label-free loss
+// (kernels unsup.hip).  unsup_loss: t = [pred (fp32 [N][B][H][W][2]), image1, image2 (fp32 [B][H][W][3]),
+// mask? (fp32 [B][H][W]), prm (fp32 [4] = eps, eps_s, edge_kappa, out_penalty), part (fp32 [blocks][N][4])];
+// unsup_loss_bwd: t = [pred, image1, image2, mask?, prm, scale (fp32 [N][2]), grad (fp32 like pred)];
+// i = [B, H, W, N] for both.
+static Launch make_unsup(const TList& t, const IList& i, std::vector<at::Tensor>& keep, bool bwd) {
+  const std::string op = bwd ? "unsup_loss_bwd" : "unsup_loss";
+  at::Tensor pred = opt(t, 0), img1 = opt(t, 1), img2 = opt(t, 2), mask = opt(t, 3), prm = opt(t, 4);
+  at::Tensor scale = bwd ? opt(t, 5) : at::Tensor(), out = opt(t, bwd ? 6 : 5);
+  const int64_t B = i[0], H = i[1], W = i[2], N = i[3];
+  TORCH_CHECK(N >= 1 && N <= 32, op, ": 1..32 predictions, got ", N);
+  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && B <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX &&
+                  B * H <= INT32_MAX && B * H * W <= INT32_MAX, op, ": sizes (B * H * W must be below 2^31)");
+  const int64_t P = B * H * W;
+  const std::pair<const at::Tensor*, const char*> f32s[] = {{&pred, ": pred"}, {&img1, ": image1"}, {&img2, ": image2"},
+                                                             {&prm, ": prm"}, {&out, bwd ? ": grad" : ": part"}};
+  for (const auto& v : f32s) check_f32(*v.first, (op + v.second).c_str());
+  TORCH_CHECK(pred.numel() == N * P * 2, op, ": pred must hold [N][B][H][W][2] = ", N * P * 2, " elements");
+  TORCH_CHECK(img1.numel() == P * 3 && img2.numel() == P * 3, op, ": image1 and image2 must hold [B][H][W][3] = ", P * 3,
+              " elements");
+  TORCH_CHECK(prm.numel() == 4, op, ": prm must hold (eps, eps_s, edge_kappa, out_penalty)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(pred.data_ptr()) % 8 == 0, op, ": pred must be 8-byte aligned");
+  std::vector<at::Tensor> inputs = {pred, img1, img2, prm};
+  if (mask.defined()) {
+    check_f32(mask, (op + ": mask").c_str());
+    TORCH_CHECK(mask.numel() == P, op, ": mask must hold [B][H][W] = ", P, " elements");
+    inputs.push_back(mask);
+  }
+  if (bwd) {
+    check_f32(scale, (op + ": scale").c_str());
+    TORCH_CHECK(scale.numel() == 2 * N, op, ": scale must hold [N][2] = ", 2 * N, " elements");
+    inputs.push_back(scale);
+    TORCH_CHECK(out.numel() == N * P * 2, op, ": grad must hold [N][B][H][W][2] = ", N * P * 2, " elements");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0, op, ": grad must be 8-byte aligned");
+  } else {
+    const int64_t need = (int64_t)jr_unsup_loss_blocks(P) * N * 4;
+    TORCH_CHECK(out.numel() == need, op, ": part must hold [blocks][N][4] = ", need, " elements");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0, op, ": part must be 16-byte aligned");
+  }
+  for (const at::Tensor& v : inputs) {
+    const char *a0 = (const char*)out.data_ptr(), *b0 = (const char*)v.data_ptr();
+    TORCH_CHECK(!(a0 < b0 + v.nbytes() && b0 < a0 + out.nbytes()), op, bwd ? ": grad" : ": part", " aliases an input");
+    keep.push_back(v);
+  }
+  keep.push_back(out);
+  const float *pp = pred.data_ptr<float>(), *p1 = img1.data_ptr<float>(), *p2 = img2.data_ptr<float>();
+  const float *mp = (const float*)ptr(mask), *rp = prm.data_ptr<float>(), *sp = (const float*)ptr(scale);
+  float* op_ = out.data_ptr<float>();
+  const int b = (int)B, h = (int)H, w = (int)W, n = (int)N;
+  if (bwd) return [=](hipStream_t s, int) { return jr_unsup_loss_bwd(pp, p1, p2, mp, rp, sp, op_, b, h, w, n, s); };
+  return [=](hipStream_t s, int) { return jr_unsup_loss(pp, p1, p2, mp, rp, op_, b, h, w, n, s); };
+}
+static Launch make_unsup_loss(const TList& t, const IList& i, std::vector<at::Tensor>& keep) { return make_unsup(t, i, keep, false); }
+static Launch make_unsup_loss_bwd(const TList& t, const IList& i, std::vector<at::Tensor>& keep) { return make_unsup(t, i, keep, true); }
+
 // ------------------------------------------------------------- sequence loss
 // t = [pred (fp32 [N][P][2]), gt (fp32 [P][2]), valid? (fp32 [P]), part (fp32 [blocks][37])], i = [P, N]
 void seq_loss_op(const TList& t, IList i, double max_flow) {
@@ -2317,6 +2372,8 @@ static const std::vector<OpRow>& op_table() {
       row_ti("augment_mixed_sums", 2, 2, make_augment_mixed_sums),
       row_ti("augment_mixed", 4, 4, make_augment_mixed),
       row_ti("flow_metrics", 6, 6, make_flow_metrics),
+      row_ti("unsup_loss", 4, 4, make_unsup_loss),
+      row_ti("unsup_loss_bwd", 4, 4, make_unsup_loss_bwd),
       // fp32 parity mode
       row_tia("conv_f32", "alpha", 22, 22, make_conv_f32),
       row_ti("stats_f32", 3, 3, make_stats_f32),

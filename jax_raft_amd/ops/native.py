@@ -850,6 +850,92 @@ def flow_metrics(pred: torch.Tensor, gt: torch.Tensor, valid: Optional[torch.Ten
     return rows, acc
 
 
+UNSUP_BLOCK, UNSUP_GRID_X = 256, 1024    # threads per block and the loss kernel's blocks per round (unsup.hip)
+_unsup_prm = {}
+
+
+def unsup_loss_blocks(P: int) -> int:
+    """Rows of block partials that ``unsup_loss`` writes for P pixels."""
+    return min(UNSUP_GRID_X, (P + UNSUP_BLOCK - 1) // UNSUP_BLOCK)
+
+
+def unsup_params(eps: float, eps_s: float, edge_kappa: float, out_penalty: float, device) -> torch.Tensor:
+    """``(eps, eps_s, edge_kappa, out_penalty)`` as the fp32 device tensor the kernels read; uploaded
+    once per device and set of values, so that a training step does not copy from the host."""
+    key = (str(device), float(eps), float(eps_s), float(edge_kappa), float(out_penalty))
+    if key not in _unsup_prm:
+        if len(_unsup_prm) >= 64:
+            _unsup_prm.clear()
+        _unsup_prm[key] = torch.tensor(key[1:], dtype=torch.float32, device=device)
+    return _unsup_prm[key]
+
+
+def _unsup_args(op, preds, image1, image2, mask, eps, eps_s, edge_kappa, out_penalty, prm):
+    from ..train import unsup as U
+
+    N, B, H, W = U._check(preds, image1, image2, mask)
+    if not preds.is_cuda:
+        return None
+    for name, t in (("flow_preds", preds), ("image1", image1), ("image2", image2), ("mask", mask)):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"{op}: {name} must be fp32 on the GPU, got {t.dtype}")
+    if N > 32 or B * H * W >= 2 ** 31:
+        raise ValueError(f"{op}: 1..32 predictions of fewer than 2^31 pixels, got N = {N}, P = {B * H * W}")
+    if prm is None:
+        prm = unsup_params(eps, eps_s, edge_kappa, out_penalty, preds.device)
+    preds = preds.contiguous()
+    if preds.data_ptr() % 8:   # the kernels' 8-byte loads
+        preds = preds.clone()
+    return [preds, image1.contiguous(), image2.contiguous(), None if mask is None else mask.contiguous(), prm], [B, H, W, N]
+
+
+def unsup_loss_partials(flow_preds: torch.Tensor, image1: torch.Tensor, image2: torch.Tensor,
+                        mask: Optional[torch.Tensor] = None, eps: float = 0.01, eps_s: float = 0.001,
+                        edge_kappa: float = 10.0, out_penalty: float = 0.5, prm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The partial sums of the label-free loss, fp32 (blocks, N, 4): per iteration ``sum(mask pix)``,
+    the smoothness sum, the count of masked pixels that land outside and, for the last iteration,
+    the sum of pix over the inside masked pixels -- ``train/unsup.py:unsup_sums`` itself on CPU
+    tensors (one row of partials), the HIP kernel on GPU tensors (``csrc/kernels/unsup.hip``; one
+    launch, bitwise repeatable).  ``prm``: :func:`unsup_params`, in place of the four floats."""
+    args = _unsup_args("unsup_loss", flow_preds, image1, image2, mask, eps, eps_s, edge_kappa, out_penalty, prm)
+    if args is None:
+        from ..train.unsup import unsup_sums
+
+        with torch.no_grad():
+            return unsup_sums(flow_preds, image1, image2, mask, eps, eps_s, edge_kappa, out_penalty)[None]
+    t, i = args
+    B, H, W, N = i
+    part = torch.empty((unsup_loss_blocks(B * H * W), N, 4), dtype=torch.float32, device=flow_preds.device)
+    ops().unsup_loss(t + [part], i)
+    return part
+
+
+def unsup_loss_grad(flow_preds: torch.Tensor, image1: torch.Tensor, image2: torch.Tensor, mask: Optional[torch.Tensor],
+                    scale: torch.Tensor, eps: float = 0.01, eps_s: float = 0.001, edge_kappa: float = 10.0,
+                    out_penalty: float = 0.5, prm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of ``sum_i scale[i, 0] sum(mask pix_i) + scale[i, 1] (smoothness sum)_i`` in the
+    predictions, (N, B, H, W, 2): autograd through ``train/unsup.py:unsup_sums`` on CPU tensors, the
+    gather kernel on GPU tensors (one launch, no atomics).  scale: (N, 2)."""
+    args = _unsup_args("unsup_loss_bwd", flow_preds, image1, image2, mask, eps, eps_s, edge_kappa, out_penalty, prm)
+    N = flow_preds.shape[0]
+    if tuple(scale.shape) != (N, 2) or scale.device != flow_preds.device:
+        raise ValueError(f"unsup_loss_bwd: scale must be {(N, 2)} on {flow_preds.device}, got {tuple(scale.shape)} on {scale.device}")
+    if args is None:
+        from ..train.unsup import unsup_sums
+
+        with torch.enable_grad():
+            f = flow_preds.detach().requires_grad_(True)
+            s = unsup_sums(f, image1, image2, mask, eps, eps_s, edge_kappa, out_penalty)
+            total = (s[:, :2] * scale.to(s.dtype)).sum()
+            return torch.autograd.grad(total, f)[0]
+    t, i = args
+    if scale.dtype != torch.float32:
+        raise ValueError(f"unsup_loss_bwd: scale must be fp32 on the GPU, got {scale.dtype}")
+    grad = torch.empty(flow_preds.shape, dtype=torch.float32, device=flow_preds.device)
+    ops().unsup_loss_bwd(t + [scale.contiguous(), grad], i)
+    return grad
+
+
 def conv2d(spec: ConvSpec, x: torch.Tensor, act: int = ACT_NONE, out_dtype=torch.bfloat16, alpha: float = 1.0,
            res: Optional[torch.Tensor] = None, res_post: int = 0, cfg: Optional[int] = None) -> torch.Tensor:
     """Eager NHWC conv of a contiguous bf16 tensor [N, H, W, C] (C == cin8)."""

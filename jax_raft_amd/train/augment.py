@@ -145,6 +145,14 @@ def _draw_sparse(g, st: Stage, p_hflip: float, src, h: int, w: int, augment: boo
     return (Hr, Wr), (y0, x0), hflip, False, colour, colour, rects
 
 
+def _constancy_safe(draws):
+    """The same draws with what breaks brightness constancy taken out (label-free training,
+    train/unsup.py): image 2 gets image 1's colour and no eraser rectangle.  Every draw has
+    been consumed, so every other word of the record is that of the unrestricted one."""
+    size, origin, hflip, vflip, c1, _c2, _rects = draws
+    return size, origin, hflip, vflip, c1, c1, []
+
+
 class AugmentParams:
     """The records of one batch, on the host: ``ints`` (B, 16) int32 and ``floats`` (B, 32) fp32."""
 
@@ -193,9 +201,11 @@ class AugmentParams:
 
     @classmethod
     def sample(cls, batch: int, src: Tuple[int, int], stage: str = "chairs", crop: Optional[Tuple[int, int]] = None,
-               seed: int = 0, step: int = 0, rank: int = 0, augment: bool = True) -> "AugmentParams":
+               seed: int = 0, step: int = 0, rank: int = 0, augment: bool = True,
+               constancy: bool = False) -> "AugmentParams":
         """``batch`` records drawn from RAFT's dense-augmentor distributions, a pure function of
-        (seed, step, rank, sample index).  ``augment=False``: identity records with a random crop."""
+        (seed, step, rank, sample index).  ``augment=False``: identity records with a random crop.
+        ``constancy=True``: the same draws, but colour 2 = colour 1 and no eraser rectangles."""
         if stage not in STAGES:
             raise ValueError(f"unknown augmentation stage {stage!r} (one of {sorted(STAGES)})")
         st = STAGES[stage]
@@ -203,8 +213,9 @@ class AugmentParams:
         Hs, Ws = src
         if Hs < h or Ws < w:
             raise ValueError(f"source {Hs}x{Ws} is smaller than the crop {h}x{w}")
-        return cls.cat([AugmentParams.record(src, *_draw_dense(np.random.default_rng([int(seed), int(step), int(rank), n]),
-                                                               st, src, h, w, augment)) for n in range(batch)])
+        safe = _constancy_safe if constancy else (lambda d: d)
+        return cls.cat([AugmentParams.record(src, *safe(_draw_dense(np.random.default_rng([int(seed), int(step), int(rank), n]),
+                                                                    st, src, h, w, augment))) for n in range(batch)])
 
     # -------------------------------------------------------------- validation
     def validate(self, src: Tuple[int, int], crop: Tuple[int, int]) -> None:
@@ -445,13 +456,13 @@ class SparseAugmentParams(AugmentParams):
 
 def sample_sparse(batch: int, sizes: Sequence[Tuple[int, int]], stage: str = "kitti",
                   crop: Optional[Tuple[int, int]] = None, seed: int = 0, step: int = 0, rank: int = 0,
-                  augment: bool = True) -> SparseAugmentParams:
+                  augment: bool = True, constancy: bool = False) -> SparseAugmentParams:
     """``batch`` records for samples of ``sizes`` from RAFT's sparse-augmentor distributions, a pure
     function of its arguments: spatial augmentation with probability 0.8 -- one scale for both
     axes, never below ``max((h + 1) / Hs, (w + 1) / Ws)`` --, an h-flip where the preset has one,
     a crop origin drawn with margins and clipped (which pulls crops to the borders), symmetric
     colour, the eraser of ``AugmentParams.sample``.  ``augment=False``: identity records with a
-    random crop."""
+    random crop.  ``constancy=True``: the same draws without the eraser rectangles."""
     if stage not in SPARSE_STAGES:
         raise ValueError(f"unknown sparse augmentation stage {stage!r} (one of {sorted(SPARSE_STAGES)})")
     if len(sizes) != batch:
@@ -463,7 +474,8 @@ def sample_sparse(batch: int, sizes: Sequence[Tuple[int, int]], stage: str = "ki
         if Hs < h or Ws < w:
             raise ValueError(f"source {Hs}x{Ws} is smaller than the crop {h}x{w}")
         g = np.random.default_rng([int(seed), int(step), int(rank), n])
-        out.append(SparseAugmentParams.record((Hs, Ws), *_draw_sparse(g, st, _SPARSE_HFLIP[stage], (Hs, Ws), h, w, augment)))
+        draws = _draw_sparse(g, st, _SPARSE_HFLIP[stage], (Hs, Ws), h, w, augment)
+        out.append(SparseAugmentParams.record((Hs, Ws), *(_constancy_safe(draws) if constancy else draws)))
     return SparseAugmentParams.cat(out)
 
 
@@ -608,12 +620,13 @@ class MixedAugmentParams(SparseAugmentParams):
 
 def sample_mixed(batch: int, sizes: Sequence[Tuple[int, int]], dense_flags: Sequence[bool], stage: str = "sintel",
                  crop: Optional[Tuple[int, int]] = None, seed: int = 0, step: int = 0, rank: int = 0,
-                 augment: bool = True) -> MixedAugmentParams:
+                 augment: bool = True, constancy: bool = False) -> MixedAugmentParams:
     """``batch`` records for a mixed batch, a pure function of its arguments.  Sample ``n`` is drawn
     from ``default_rng([seed, step, rank, n])``: a dense one with exactly the draws of
     ``AugmentParams.sample`` (stretch, v-flip, asymmetric colour; ``STAGES[stage]``), a sparse one with
     exactly those of :func:`sample_sparse` (``SPARSE_STAGES[stage]``), so an all-dense or all-sparse
-    batch has the existing samplers' records word for word.  ``stage`` must be in both tables."""
+    batch has the existing samplers' records word for word.  ``stage`` must be in both tables.
+    ``constancy=True``: the same draws, colour 2 = colour 1 and no eraser rectangles."""
     if stage not in STAGES or stage not in SPARSE_STAGES:
         raise ValueError(f"unknown mixed augmentation stage {stage!r} (one of {sorted(set(STAGES) & set(SPARSE_STAGES))})")
     if len(sizes) != batch or len(dense_flags) != batch:
@@ -628,6 +641,8 @@ def sample_mixed(batch: int, sizes: Sequence[Tuple[int, int]], dense_flags: Sequ
             draws = _draw_dense(g, STAGES[stage], (Hs, Ws), h, w, augment)
         else:
             draws = _draw_sparse(g, SPARSE_STAGES[stage], _SPARSE_HFLIP[stage], (Hs, Ws), h, w, augment)
+        if constancy:
+            draws = _constancy_safe(draws)
         out.append(MixedAugmentParams.record((Hs, Ws), dense, *draws))
     return MixedAugmentParams.cat(out)
 

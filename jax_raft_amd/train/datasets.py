@@ -129,6 +129,8 @@ def read_chairs_split(root: str, pairs: int, split_file: Optional[str] = None) -
 class FlowPairs:
     """``ds[i] -> (image1 uint8 (H, W, 3), image2, flow fp32 (H, W, 2))`` over a list of file triples."""
 
+    labelled = True     # the flow is ground truth (False: FramePairs, whose flow is a placeholder)
+
     def __init__(self, items: Sequence[Tuple[str, str, str]]):
         self.items: List[Tuple[str, str, str]] = [tuple(t) for t in items]
         if not self.items:
@@ -198,6 +200,23 @@ class FlowPairs:
         return cls(items)
 
     @classmethod
+    def frames(cls, root: str) -> "FramePairs":
+        """Video without ground truth, for label-free training: every directory under ``root`` (``root``
+        itself included) that holds image files is one sequence, its files in sorted order; consecutive
+        frames of a sequence are a pair and no pair crosses sequences.  ``labelled`` is False and
+        the flow of every item is a shared all-zero array."""
+        if not osp.isdir(root):
+            raise FileNotFoundError(f"{root}: not a directory")
+        items = []
+        for d, subdirs, files in os.walk(root):
+            subdirs.sort()                          # os.walk then visits them in this order
+            seq = sorted(osp.join(d, f) for f in files if f.lower().endswith(FRAME_EXTENSIONS))
+            items += [(a, b, "") for a, b in zip(seq, seq[1:])]
+        if not items:
+            raise FileNotFoundError(f"no two consecutive image files in one directory under {root}")
+        return FramePairs(items)
+
+    @classmethod
     def open(cls, root: str, dataset: str = "chairs", parts=None):
         """The list of ``dataset`` under ``root``.  ``mix``: RAFT's Sintel-stage mixture, ``parts`` a
         sequence of names or ``(name, weight)`` (default :data:`MIX_DEFAULT`), each part in its
@@ -216,6 +235,8 @@ class FlowPairs:
             return MixedFlowPairs(opened)
         if parts is not None:
             raise ValueError("FlowPairs.open: parts belong to dataset 'mix'")
+        if dataset == "frames":
+            return cls.frames(root)
         if dataset == "chairs":
             return cls.chairs(root)
         if dataset in ("chairs-train", "chairs-val"):
@@ -231,7 +252,7 @@ class FlowPairs:
         if dataset in ("things-clean", "things-final"):
             return cls.things(root, dataset.split("-")[1])
         raise ValueError(f"unknown dataset {dataset!r} (chairs, chairs-train, chairs-val, sintel-clean, sintel-final, kitti, hd1k, things, "
-                         "things-clean, things-final, mix)")
+                         "things-clean, things-final, mix, frames)")
 
     @classmethod
     def kitti(cls, root: str) -> "SparseFlowPairs":
@@ -282,6 +303,31 @@ class FlowPairs:
         if flow is None:
             raise ValueError(f"unreadable .flo file {f}: bad magic")
         return read_frame(a), read_frame(b), flow
+
+
+FRAME_EXTENSIONS = (".png", ".ppm", ".jpg", ".jpeg", ".bmp")
+
+
+class FramePairs(FlowPairs):
+    """Consecutive frames of video, without ground truth (``FlowPairs.frames``): ``ds[i] -> (image1,
+    image2, zeros fp32 (H, W, 2))``.  The flow is ONE shared all-zero array of the first frame's
+    size, there only so that the loader and the augmentation ops stay as they are; nothing may
+    write to it or read a label out of it (``labelled`` is False).  The loader rejects a frame of
+    another size."""
+
+    labelled = False
+
+    def __init__(self, items):
+        super().__init__(items)
+        self._zero = None
+
+    def __getitem__(self, i: int):
+        a, b, _ = self.items[i]
+        if self._zero is None:
+            zero = np.zeros(frame_size(self.items[0][0]) + (2,), dtype=np.float32)
+            zero.setflags(write=False)
+            self._zero = zero
+        return read_frame(a), read_frame(b), self._zero
 
 
 class SparseFlowPairs(FlowPairs):

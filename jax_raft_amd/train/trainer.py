@@ -26,6 +26,13 @@ Validation on held-out data: ``--val name=root[,name=root...]`` (names ``chairs-
 line with a ``"val"`` key; with ``--ckpt-dir`` the lines also go to ``<dir>/val.jsonl``.  ``--chairs-split FILE``
 trains ``--dataset chairs`` on the label-1 pairs of FlyingChairs' split file only, which ``chairs-val`` asks for.
 
+Without ground truth: ``--loss unsup`` trains on the photometric + edge-aware smoothness loss of
+``train/unsup.py`` (``--unsup-eps``, ``--unsup-eps-s``, ``--unsup-edge-kappa``, ``--unsup-smooth-weight``,
+``--unsup-out-penalty``; ``--gamma`` weights the iterations as ever), with augmentation records that keep
+brightness constancy.  ``--dataset frames`` lists the consecutive frames of every directory under ``--data``
+(no flow files; ``--loss unsup`` only).  On a labelled set the step also reports ``epe`` / ``1px`` / ``3px`` /
+``5px``, which take no part in the gradient.
+
 Checkpoints: ``<dir>/step_<n>.msgpack`` (Flax-format weights, loadable with
 ``raft_large(weights=...)``) + ``step_<n>.opt.pt`` (optimizer / scheduler
 state, tensors only) + ``latest.json``; ``--resume`` continues from latest.
@@ -47,6 +54,7 @@ from ..parallel import dp
 from ..utils import checkpoint as ckpt
 from .data import SyntheticFlow
 from .loss import sequence_loss
+from .unsup import unsup_loss
 
 
 @dataclass
@@ -98,8 +106,23 @@ class TrainConfig:
     val_max_pairs: Optional[int] = None
     # a FlyingChairs split file: dataset="chairs" then lists its label-1 (training) pairs only
     chairs_split: Optional[str] = None
+    # The training loss: "sequence" (supervised, as ever) | "unsup" (train/unsup.py: photometric + edge-aware
+    # smoothness on every iteration's prediction, weighted by gamma; the batch's flow and valid take no part
+    # in the gradient).  The unsup_* defaults are placeholders: nothing here to tune them on.
+    loss: str = "sequence"
+    unsup_eps: float = 0.01
+    unsup_eps_s: float = 0.001
+    unsup_edge_kappa: float = 10.0
+    unsup_smooth_weight: float = 0.05
+    unsup_out_penalty: float = 0.5
 
     def __post_init__(self):
+        if self.loss not in ("sequence", "unsup"):
+            raise ValueError(f"unknown loss {self.loss!r} (sequence or unsup)")
+        if self.loss == "unsup" and self.graph_step:
+            raise ValueError("loss 'unsup' is not supported together with graph_step")
+        if self.data is not None and self.dataset == "frames" and self.loss == "sequence":
+            raise ValueError("dataset 'frames' has no ground truth: the sequence loss cannot train on it (loss='unsup' can)")
         self.val = (self.val,) if isinstance(self.val, str) else tuple(self.val)
         if self.val:
             from ..eval.validate import parse_val
@@ -141,6 +164,8 @@ class TrainConfig:
 
 
 VAL_FIELDS = ("val", "val_every", "val_iters", "val_batch", "val_max_pairs", "chairs_split")
+# likewise left out of latest.json while they are at their defaults
+UNSUP_FIELDS = ("loss", "unsup_eps", "unsup_eps_s", "unsup_edge_kappa", "unsup_smooth_weight", "unsup_out_penalty")
 
 
 def _adamw(params, cfg: TrainConfig, device, capturable: bool = False):
@@ -190,6 +215,7 @@ class Trainer:
             anneal_strategy="linear")
         self.data = SyntheticFlow(size=tuple(cfg.size), seed=cfg.seed, device=self.device)
         self.loader = None
+        self.labelled = True       # the batches carry ground truth (False: a frames-only list)
         if cfg.data is not None:
             from .datasets import FlowPairs, PairLoader
 
@@ -199,6 +225,7 @@ class Trainer:
                 ds = FlowPairs.chairs(cfg.data, "training", cfg.chairs_split)
             else:
                 ds = FlowPairs.open(cfg.data, cfg.dataset)
+            self.labelled = bool(getattr(ds, "labelled", True))
             self.loader = PairLoader(ds, cfg.batch, seed=cfg.seed, rank=self.rank, world=self.world, device=self.device)
             if self.loader.frame_min[0] < cfg.size[0] or self.loader.frame_min[1] < cfg.size[1]:
                 raise ValueError(f"{cfg.data}: frames {self.loader.frame_min} are smaller than the crop {tuple(cfg.size)}")
@@ -270,7 +297,15 @@ class Trainer:
         self.opt.zero_grad(set_to_none=True)
         train_bn = not cfg.freeze_bn
         preds = self.model(img1, img2, train=train_bn, num_flow_updates=cfg.iters, autograd=True)
-        loss, metrics = sequence_loss(preds, flow, valid, cfg.gamma, cfg.max_flow)
+        if cfg.loss == "unsup":
+            loss, metrics = unsup_loss(preds, img1, img2, None, cfg.gamma, cfg.unsup_eps, cfg.unsup_eps_s,
+                                       cfg.unsup_edge_kappa, cfg.unsup_smooth_weight, cfg.unsup_out_penalty)
+            if self.labelled:      # a labelled set monitors the label-free run: metrics only, no gradient
+                with torch.no_grad():
+                    _, sup = sequence_loss(preds.detach(), flow, valid, cfg.gamma, cfg.max_flow)
+                metrics = {**metrics, **sup}
+        else:
+            loss, metrics = sequence_loss(preds, flow, valid, cfg.gamma, cfg.max_flow)
         if self.step + 1 == cfg.fault_nan_step:
             loss = loss * float("nan")
         with self._comm():
@@ -347,19 +382,20 @@ class Trainer:
             from .augment import AugmentParams, sample_mixed, sample_sparse
 
             crop = (int(cfg.size[0]), int(cfg.size[1]))
+            safe = {"constancy": True} if cfg.loss == "unsup" else {}   # keep brightness constancy (augment.py)
             if self.loader.mixed:
                 img1, img2, flow, valid, sizes, dense = self.loader.fetch(step)
                 params = sample_mixed(cfg.batch, sizes, dense, cfg.stage, crop, seed=cfg.seed, step=step, rank=self.rank,
-                                      augment=cfg.augment)
+                                      augment=cfg.augment, **safe)
                 return nat.augment_pairs_mixed(img1, img2, flow, valid, params, crop)
             if self.loader.sparse:
                 img1, img2, flow, valid, sizes = self.loader.fetch(step)
                 params = sample_sparse(cfg.batch, sizes, cfg.stage, crop, seed=cfg.seed, step=step, rank=self.rank,
-                                       augment=cfg.augment)
+                                       augment=cfg.augment, **safe)
                 return nat.augment_pairs_sparse(img1, img2, flow, valid, params, crop)
             img1, img2, flow = self.loader.fetch(step)
             params = AugmentParams.sample(cfg.batch, self.loader.frame, cfg.stage, crop, seed=cfg.seed, step=step,
-                                          rank=self.rank, augment=cfg.augment)
+                                          rank=self.rank, augment=cfg.augment, **safe)
             return nat.augment_pairs(img1, img2, flow, params, crop)
         base = (step * self.world + self.rank) * cfg.batch
         return self.data.batch(list(range(base, base + cfg.batch)))
@@ -440,7 +476,7 @@ class Trainer:
         fields = type(self.cfg).__dataclass_fields__
         config = {k: (list(v) if isinstance(v, tuple) else v) for k, v in asdict(self.cfg).items()
                   # a run without validation writes the file it always wrote
-                  if k not in VAL_FIELDS or v != fields[k].default}
+                  if k not in VAL_FIELDS + UNSUP_FIELDS or v != fields[k].default}
         with open(os.path.join(d, "latest.json"), "w") as f:
             json.dump({"step": self.step, "weights": name + ".msgpack", "opt": name + ".opt.pt", "config": config}, f)
         if dp.is_dist():

@@ -1,0 +1,177 @@
+#!/usr/bin/env python3
+"""What the label-free loss (train/unsup.py, csrc/kernels/unsup.hip) costs, in one fresh process
+on one GPU, at the ``chairs`` shape (N, B, H, W) = (12, 6, 368, 496):
+
+(a) the GPU time of the two launches (``unsup_loss``, ``unsup_loss_bwd``) from device events over
+    ``--reps`` repetitions each, buffers preallocated, next to the bytes each must move at least
+    (every operand read once, every result written once);
+(b) the native forward + backward (``unsup_loss(...)[0].backward()``) against the golden op
+    ``unsup_loss_reference`` run on the same GPU tensors under autograd, i.e. the PyTorch
+    composition: the arms alternate in one process, each runs twice, ``--pair-reps`` repetitions
+    per run.  The condition: native is faster by more than the larger difference between the two
+    runs of either arm;
+(c) the raft_large training step (384 x 512, batch 6, 12 iterations, ``SyntheticFlow``) with
+    ``loss="unsup"`` against ``loss="sequence"``: two trainers in one process, blocks of
+    ``--block`` steps alternated for ``--rounds`` rounds after a warm-up of both.  No target: the
+    difference and the spread between blocks of one arm are reported.
+
+  python tools/unsup_bench.py [--out profiles/unsup_loss_overhead.txt]
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from jax_raft_amd.ops import native as nat  # noqa: E402
+from jax_raft_amd.train import unsup_loss, unsup_loss_reference  # noqa: E402
+from jax_raft_amd.train.data import SyntheticFlow  # noqa: E402
+from jax_raft_amd.train.trainer import TrainConfig, Trainer  # noqa: E402
+
+N, B, H, W = 12, 6, 368, 496
+BATCH = 6
+
+
+def inputs(dev):
+    """Frames of SyntheticFlow and predictions around its ground truth (most pixels land inside)."""
+    i1, i2, flow, _ = SyntheticFlow((H, W), seed=0, device=dev).batch(list(range(B)))
+    g = torch.Generator(device=dev).manual_seed(0)
+    preds = flow[None] + torch.randn(N, B, H, W, 2, generator=g, device=dev) * torch.linspace(3.0, 0.3, N, device=dev).view(N, 1, 1, 1, 1)
+    return preds.contiguous(), i1.contiguous(), i2.contiguous()
+
+
+def events(fn, dev, reps, warm=5):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize(dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize(dev)
+    return 1000 * e0.elapsed_time(e1) / reps            # us
+
+
+def launches(dev, reps):
+    preds, i1, i2 = inputs(dev)
+    P = B * H * W
+    prm = nat.unsup_params(0.01, 0.001, 10.0, 0.5, dev)
+    part = torch.empty(nat.unsup_loss_blocks(P), N, 4, device=dev)
+    grad = torch.empty_like(preds)
+    scale = torch.full((N, 2), 1.0 / P, device=dev)
+    fwd = lambda: nat.ops().unsup_loss([preds, i1, i2, None, prm, part], [B, H, W, N])
+    bwd = lambda: nat.ops().unsup_loss_bwd([preds, i1, i2, None, prm, scale, grad], [B, H, W, N])
+    mb = lambda *ts: sum(t.numel() * t.element_size() for t in ts) / 1e6
+    return {"fwd": events(fwd, dev, reps), "bwd": events(bwd, dev, reps),
+            "fwd_mb": mb(preds, i1, i2, part), "bwd_mb": mb(preds, i1, i2, grad)}
+
+
+def pair(dev, reps):
+    preds, i1, i2 = inputs(dev)
+    f = preds.clone().requires_grad_(True)
+
+    def run(loss_fn):
+        def step():
+            f.grad = None
+            loss_fn(f, i1, i2)[0].backward()
+        return step
+
+    arms = {"native": run(unsup_loss), "torch": run(unsup_loss_reference)}
+    times = {k: [] for k in arms}
+    peak = {}
+    for _ in range(2):
+        for name, step in arms.items():
+            f.grad = None                                # the other arm's gradient is not this arm's baseline
+            torch.cuda.reset_peak_memory_stats(dev)
+            base = torch.cuda.memory_allocated(dev)
+            times[name].append(events(step, dev, reps, warm=2) / 1000)     # ms
+            peak[name] = (torch.cuda.max_memory_allocated(dev) - base) / 1e6
+    return times, peak
+
+
+def training(args, dev):
+    total = args.warmup + args.block * args.rounds
+    kw = dict(arch=args.arch, steps=total, batch=BATCH, iters=args.iters, size=(384, 512), log_every=10 ** 9)
+    arms = {"unsup": Trainer(TrainConfig(loss="unsup", **kw)), "sequence": Trainer(TrainConfig(**kw))}
+    for name, tr in arms.items():
+        t0 = time.perf_counter()
+        for _ in range(args.warmup):
+            tr.train_step(tr.batch_for(tr.step))
+        tr.flush()
+        torch.cuda.synchronize(dev)
+        print(f"warm-up of {name}: {time.perf_counter() - t0:.1f} s", flush=True)
+    rate = {k: [] for k in arms}
+    for _ in range(args.rounds):
+        for name, tr in arms.items():
+            t0 = time.perf_counter()
+            for _ in range(args.block):
+                m = tr.train_step(tr.batch_for(tr.step))
+            tr.flush()
+            torch.cuda.synchronize(dev)
+            rate[name].append(BATCH * args.block / (time.perf_counter() - t0))
+            assert torch.isfinite(m["loss"]).item(), name
+    return rate, {k: tr.skipped for k, tr in arms.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="profiles/unsup_loss_overhead.txt")
+    ap.add_argument("--reps", type=int, default=500)
+    ap.add_argument("--pair-reps", type=int, default=20)
+    ap.add_argument("--block", type=int, default=20, help="steps per block")
+    ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("--warmup", type=int, default=6)
+    ap.add_argument("--arch", default="raft_large")
+    ap.add_argument("--iters", type=int, default=12)
+    ap.add_argument("--skip-training", action="store_true", help="(a) and (b) only")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "unsup_bench measures on the GPU"
+    dev = torch.device("cuda", 0)
+    mean = lambda v: sum(v) / len(v)
+    lines = [f"label-free loss (photometric + edge-aware smoothness), {torch.cuda.get_device_name(dev)}",
+             f"predictions (N, B, H, W) = ({N}, {B}, {H}, {W}), fp32; no mask", ""]
+    kt = launches(dev, args.reps)
+    lines += [f"(a) GPU time per launch, device events over {args.reps} repetitions:",
+              f"    unsup_loss     {kt['fwd']:8.1f} us   {kt['fwd_mb']:6.1f} MB at least (predictions, both images, partials)"
+              f"  -> {kt['fwd_mb'] / kt['fwd'] * 1e3:6.0f} GB/s of them",
+              f"    unsup_loss_bwd {kt['bwd']:8.1f} us   {kt['bwd_mb']:6.1f} MB at least (predictions, both images, gradient)"
+              f"  -> {kt['bwd_mb'] / kt['bwd'] * 1e3:6.0f} GB/s of them",
+              "    (neighbouring flows and the texel gathers are re-reads that the caches serve; they are not in the byte counts)", ""]
+    print("\n".join(lines), flush=True)
+    times, peak = pair(dev, args.pair_reps)
+    spread = max(abs(v[0] - v[1]) for v in times.values())
+    gain = mean(times["torch"]) - mean(times["native"])
+    lines += [f"(b) loss forward + backward, {args.pair_reps} repetitions per run, arms alternated native / torch x 2:"]
+    for k, v in times.items():
+        lines.append(f"    {k:7s} {mean(v):8.3f} ms   [runs: {v[0]:.3f}, {v[1]:.3f}]   peak extra memory {peak[k]:8.0f} MB")
+    lines += [f"    torch - native: {gain:+.3f} ms ({mean(times['torch']) / mean(times['native']):.1f} x); larger difference "
+              f"between the two runs of one arm: {spread:.3f} ms",
+              "    -> " + ("native is faster by more than that spread" if gain > spread else
+                           "NOT faster by more than that spread: the condition does not hold"), ""]
+    print("\n".join(lines[-len(times) - 4:]), flush=True)
+    if not args.skip_training:
+        rate, skipped = training(args, dev)
+        ms = lambda x: 1000 * BATCH / x
+        u, s = mean(rate["unsup"]), mean(rate["sequence"])
+        lines += [f"(c) training step, {args.arch}, 384x512, batch {BATCH}, {args.iters} iterations, SyntheticFlow; {args.block} steps per "
+                  f"block, blocks alternated unsup / sequence x {args.rounds} in one process after {args.warmup} warm-up steps each"]
+        for k in rate:
+            lines.append(f"    {k:8s} {mean(rate[k]):7.1f} pairs/s  {ms(mean(rate[k])):6.2f} ms/step  [per block: "
+                         + ", ".join(f"{v:.1f}" for v in rate[k]) + f"]   skipped steps: {skipped[k]}")
+        lines += [f"    unsup - sequence: {ms(u) - ms(s):+.2f} ms/step ({100 * (u - s) / s:+.1f} % pairs/s); largest spread between "
+                  f"blocks of one arm {max(max(v) - min(v) for v in rate.values()):.1f} pairs/s",
+                  "    (the unsup step also runs the sequence loss's forward kernel for the EPE metrics of the labelled synthetic set)", ""]
+    lines += ["Not measured: accuracy.  There is no checkpoint and no real data here, and the loss's default weights are placeholders.", ""]
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
