@@ -379,6 +379,19 @@ int jr_unsup_loss(const float* pred, const float* img1, const float* img2, const
                   float* part, int B, int H, int W, int N, hipStream_t stream);
 int jr_unsup_loss_bwd(const float* pred, const float* img1, const float* img2, const float* mask, const float* prm,
                       const float* scale, float* grad, int B, int H, int W, int N, hipStream_t stream);
+// Soft census photometric term of the label-free loss (census.hip; train/unsup.py:census_sums).  Sizes
+// and pred as above.  jr_census_gray writes gray fp32 [2][B][H][W], the grey planes of img1 / img2.
+// jr_census_loss writes part fp32 [jr_census_tiles(B, H, W)][N][4] (16-byte aligned): per pixel tile and
+// iteration the sum of mask * term, the masked pixels that are not inside, the masked pixels inside but
+// in the 3-pixel border band and, for iteration N - 1, the sum of cen over the valid masked pixels; and
+// coef fp32 [N][B][H][W], the backward's per-pixel coefficient.  jr_census_loss_bwd writes (add = 0) or
+// adds (add = 1) the gradient to grad fp32 [N][B][H][W][2] (8-byte aligned) with scale fp32 [N].
+long jr_census_tiles(int B, int H, int W);
+int jr_census_gray(const float* img1, const float* img2, float* gray, int B, int H, int W, hipStream_t stream);
+int jr_census_loss(const float* pred, const float* gray, const float* mask, const float* prm, float* part, float* coef,
+                   int B, int H, int W, int N, hipStream_t stream);
+int jr_census_loss_bwd(const float* pred, const float* gray, const float* coef, const float* scale, float* grad, int B,
+                       int H, int W, int N, int add, hipStream_t stream);
 // Conv of a 2-channel input (the flow branch's 7x7 / 3x3): x bf16 NHWC
 // [N][H][W][x_cstride] (channels 0, 1 used), stride 1, output H x W; w bf16
 // MFMA A fragments [cout/16][NKC][64 lanes][8] (jax_raft_amd/ops/native.py:

@@ -2195,6 +2195,97 @@ static Launch make_unsup(const TList& t, const IList& i, std::vector<at::Tensor>
 static Launch make_unsup_loss(const TList& t, const IList& i, std::vector<at::Tensor>& keep) { return make_unsup(t, i, keep, false); }
 static Launch make_unsup_loss_bwd(const TList& t, const IList& i, std::vector<at::Tensor>& keep) { return make_unsup(t, i, keep, true); }
 
+// -------------------------------------------------- census photometric term
+// (kernels census.hip).  census_gray: t = [image1, image2 (fp32 [B][H][W][3]), gray (fp32 [2][B][H][W])],
+// i = [B, H, W].  census_loss: t = [pred (fp32 [N][B][H][W][2]), gray, mask? (fp32 [B][H][W]), prm (fp32 [4]),
+// part (fp32 [tiles][N][4]), coef (fp32 [N][B][H][W])], i = [B, H, W, N].  census_loss_bwd: t = [pred, gray,
+// coef, scale (fp32 [N]), grad (fp32 like pred)], i = [B, H, W, N, add (0: write, 1: add into grad)].
+static int64_t census_sizes(const std::string& op, const IList& i, bool with_n) {
+  const int64_t B = i[0], H = i[1], W = i[2];
+  if (with_n) TORCH_CHECK(i[3] >= 1 && i[3] <= 32, op, ": 1..32 predictions, got ", i[3]);
+  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && B <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX && B * H <= INT32_MAX &&
+                  B * H * W <= INT32_MAX, op, ": sizes (B * H * W must be below 2^31)");
+  return B * H * W;
+}
+static void census_no_alias(const std::string& op, const char* what, const at::Tensor& out, const std::vector<at::Tensor>& ins) {
+  for (const at::Tensor& v : ins) {
+    const char *a0 = (const char*)out.data_ptr(), *b0 = (const char*)v.data_ptr();
+    TORCH_CHECK(!(a0 < b0 + v.nbytes() && b0 < a0 + out.nbytes()), op, what, " aliases another operand");
+  }
+}
+static Launch make_census_gray(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  const std::string op = "census_gray";
+  at::Tensor img1 = opt(t, 0), img2 = opt(t, 1), gray = opt(t, 2);
+  const int64_t P = census_sizes(op, i, false);
+  check_f32(img1, "census_gray: image1");
+  check_f32(img2, "census_gray: image2");
+  check_f32(gray, "census_gray: gray");
+  TORCH_CHECK(img1.numel() == P * 3 && img2.numel() == P * 3, op, ": image1 and image2 must hold [B][H][W][3] = ", P * 3,
+              " elements");
+  TORCH_CHECK(gray.numel() == 2 * P, op, ": gray must hold [2][B][H][W] = ", 2 * P, " elements");
+  census_no_alias(op, ": gray", gray, {img1, img2});
+  keep.insert(keep.end(), {img1, img2, gray});
+  const float *p1 = img1.data_ptr<float>(), *p2 = img2.data_ptr<float>();
+  float* gp = gray.data_ptr<float>();
+  const int b = (int)i[0], h = (int)i[1], w = (int)i[2];
+  return [=](hipStream_t s, int) { return jr_census_gray(p1, p2, gp, b, h, w, s); };
+}
+static Launch make_census_loss(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  const std::string op = "census_loss";
+  at::Tensor pred = opt(t, 0), gray = opt(t, 1), mask = opt(t, 2), prm = opt(t, 3), part = opt(t, 4), coef = opt(t, 5);
+  const int64_t P = census_sizes(op, i, true), N = i[3];
+  const std::pair<const at::Tensor*, const char*> f32s[] = {{&pred, ": pred"}, {&gray, ": gray"}, {&prm, ": prm"},
+                                                             {&part, ": part"}, {&coef, ": coef"}};
+  for (const auto& v : f32s) check_f32(*v.first, (op + v.second).c_str());
+  TORCH_CHECK(pred.numel() == N * P * 2, op, ": pred must hold [N][B][H][W][2] = ", N * P * 2, " elements");
+  TORCH_CHECK(gray.numel() == 2 * P, op, ": gray must hold [2][B][H][W] = ", 2 * P, " elements");
+  TORCH_CHECK(prm.numel() == 4, op, ": prm must hold (eps, eps_s, edge_kappa, out_penalty)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(pred.data_ptr()) % 8 == 0, op, ": pred must be 8-byte aligned");
+  std::vector<at::Tensor> inputs = {pred, gray, prm};
+  if (mask.defined()) {
+    check_f32(mask, "census_loss: mask");
+    TORCH_CHECK(mask.numel() == P, op, ": mask must hold [B][H][W] = ", P, " elements");
+    inputs.push_back(mask);
+  }
+  const int64_t need = (int64_t)jr_census_tiles((int)i[0], (int)i[1], (int)i[2]) * N * 4;
+  TORCH_CHECK(part.numel() == need, op, ": part must hold [tiles][N][4] = ", need, " elements");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(part.data_ptr()) % 16 == 0, op, ": part must be 16-byte aligned");
+  TORCH_CHECK(coef.numel() == N * P, op, ": coef must hold [N][B][H][W] = ", N * P, " elements");
+  census_no_alias(op, ": part", part, inputs);
+  inputs.push_back(part);
+  census_no_alias(op, ": coef", coef, inputs);
+  inputs.push_back(coef);
+  keep.insert(keep.end(), inputs.begin(), inputs.end());
+  const float *pp = pred.data_ptr<float>(), *gp = gray.data_ptr<float>(), *mp = (const float*)ptr(mask);
+  const float* rp = prm.data_ptr<float>();
+  float *op_ = part.data_ptr<float>(), *cp = coef.data_ptr<float>();
+  const int b = (int)i[0], h = (int)i[1], w = (int)i[2], n = (int)N;
+  return [=](hipStream_t s, int) { return jr_census_loss(pp, gp, mp, rp, op_, cp, b, h, w, n, s); };
+}
+static Launch make_census_loss_bwd(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  const std::string op = "census_loss_bwd";
+  at::Tensor pred = opt(t, 0), gray = opt(t, 1), coef = opt(t, 2), scale = opt(t, 3), grad = opt(t, 4);
+  const int64_t P = census_sizes(op, i, true), N = i[3], add = i[4];
+  TORCH_CHECK(add == 0 || add == 1, op, ": add must be 0 or 1, got ", add);
+  const std::pair<const at::Tensor*, const char*> f32s[] = {{&pred, ": pred"}, {&gray, ": gray"}, {&coef, ": coef"},
+                                                             {&scale, ": scale"}, {&grad, ": grad"}};
+  for (const auto& v : f32s) check_f32(*v.first, (op + v.second).c_str());
+  TORCH_CHECK(pred.numel() == N * P * 2, op, ": pred must hold [N][B][H][W][2] = ", N * P * 2, " elements");
+  TORCH_CHECK(gray.numel() == 2 * P, op, ": gray must hold [2][B][H][W] = ", 2 * P, " elements");
+  TORCH_CHECK(coef.numel() == N * P, op, ": coef must hold [N][B][H][W] = ", N * P, " elements");
+  TORCH_CHECK(scale.numel() == N, op, ": scale must hold [N] = ", N, " elements");
+  TORCH_CHECK(grad.numel() == N * P * 2, op, ": grad must hold [N][B][H][W][2] = ", N * P * 2, " elements");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(pred.data_ptr()) % 8 == 0, op, ": pred must be 8-byte aligned");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(grad.data_ptr()) % 8 == 0, op, ": grad must be 8-byte aligned");
+  census_no_alias(op, ": grad", grad, {pred, gray, coef, scale});
+  keep.insert(keep.end(), {pred, gray, coef, scale, grad});
+  const float *pp = pred.data_ptr<float>(), *gp = gray.data_ptr<float>(), *cp = coef.data_ptr<float>();
+  const float* sp = scale.data_ptr<float>();
+  float* op_ = grad.data_ptr<float>();
+  const int b = (int)i[0], h = (int)i[1], w = (int)i[2], n = (int)N, a = (int)add;
+  return [=](hipStream_t s, int) { return jr_census_loss_bwd(pp, gp, cp, sp, op_, b, h, w, n, a, s); };
+}
+
 // ------------------------------------------------------------- sequence loss
 // t = [pred (fp32 [N][P][2]), gt (fp32 [P][2]), valid? (fp32 [P]), part (fp32 [blocks][37])], i = [P, N]
 void seq_loss_op(const TList& t, IList i, double max_flow) {
@@ -2374,6 +2465,9 @@ static const std::vector<OpRow>& op_table() {
       row_ti("flow_metrics", 6, 6, make_flow_metrics),
       row_ti("unsup_loss", 4, 4, make_unsup_loss),
       row_ti("unsup_loss_bwd", 4, 4, make_unsup_loss_bwd),
+      row_ti("census_gray", 3, 3, make_census_gray),
+      row_ti("census_loss", 4, 4, make_census_loss),
+      row_ti("census_loss_bwd", 5, 5, make_census_loss_bwd),
       // fp32 parity mode
       row_tia("conv_f32", "alpha", 22, 22, make_conv_f32),
       row_ti("stats_f32", 3, 3, make_stats_f32),

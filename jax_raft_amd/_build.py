@@ -57,6 +57,7 @@ KERNEL_SOURCES = [
     CSRC / "kernels" / "augment_mixed.hip",
     CSRC / "kernels" / "metrics.hip",
     CSRC / "kernels" / "unsup.hip",
+    CSRC / "kernels" / "census.hip",
 ]
 HOST_SOURCES = [CSRC / "runtime" / "binding.cpp", CSRC / "runtime" / "png.cpp"]
 # every header of csrc/ is a dependency of every object (a missed header left stale objects in

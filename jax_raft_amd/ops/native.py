@@ -936,6 +936,129 @@ def unsup_loss_grad(flow_preds: torch.Tensor, image1: torch.Tensor, image2: torc
     return grad
 
 
+CENSUS_TILE, CENSUS_ITERS = (32, 8), 4   # the pixel tile (x, y) and the iterations of a block (census.hip)
+
+
+def census_tiles(B: int, H: int, W: int) -> int:
+    """Rows of tile partials that ``census_loss`` writes."""
+    tx, ty = CENSUS_TILE
+    return B * ((H + ty - 1) // ty) * ((W + tx - 1) // tx)
+
+
+def _census_args(op, preds, gray, mask):
+    """Host checks shared by the census front ends; (N, B, H, W).  Nothing is launched before they pass."""
+    if preds.ndim != 5 or preds.shape[-1] != 2 or not preds.is_floating_point() or 0 in preds.shape:
+        raise ValueError(f"{op}: flow_preds must be a non-empty (N, B, H, W, 2) floating point tensor, got "
+                         f"{tuple(preds.shape)} {preds.dtype}")
+    N, B, H, W, _ = preds.shape
+    named = ([] if gray is None else [("gray", gray, (2, B, H, W))]) + ([] if mask is None else [("mask", mask, (B, H, W))])
+    for name, t, shape in named:
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.device != preds.device:
+            raise ValueError(f"{op}: {name} must be {shape} on {preds.device}, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else t} on {getattr(t, 'device', None)}")
+    if preds.is_cuda:
+        for name, t in (("flow_preds", preds), ("gray", gray), ("mask", mask)):
+            if t is not None and t.dtype != torch.float32:
+                raise ValueError(f"{op}: {name} must be fp32 on the GPU, got {t.dtype}")
+            if t is not None and not t.is_contiguous():
+                raise ValueError(f"{op}: {name} must be contiguous")
+        if preds.data_ptr() % 8:
+            raise ValueError(f"{op}: flow_preds must be 8-byte aligned")
+        if N > 32 or B * H * W >= 2 ** 31:
+            raise ValueError(f"{op}: 1..32 predictions of fewer than 2^31 pixels, got N = {N}, P = {B * H * W}")
+    return N, B, H, W
+
+
+def census_gray_planes(image1: torch.Tensor, image2: torch.Tensor) -> torch.Tensor:
+    """The grey planes of both images in 8-bit levels, (2, B, H, W): ``train/unsup.py:census_gray``
+    on CPU tensors, one launch of ``csrc/kernels/census.hip`` on GPU tensors."""
+    ok = lambda t: isinstance(t, torch.Tensor) and t.ndim == 4 and t.shape[-1] == 3 and t.is_floating_point() and t.numel() > 0
+    if not (ok(image1) and ok(image2) and image1.shape == image2.shape and image1.device == image2.device):
+        raise ValueError("census_gray: image1 and image2 must be non-empty (B, H, W, 3) floating point tensors of one "
+                         "shape on one device")
+    if not image1.is_cuda:
+        from ..train.unsup import census_gray
+
+        return torch.stack([census_gray(image1), census_gray(image2)])
+    B, H, W, _ = image1.shape
+    for name, t in (("image1", image1), ("image2", image2)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"census_gray: {name} must be contiguous fp32 on the GPU, got {t.dtype}")
+    if B * H * W >= 2 ** 31:
+        raise ValueError(f"census_gray: fewer than 2^31 pixels, got {B * H * W}")
+    gray = torch.empty((2, B, H, W), dtype=torch.float32, device=image1.device)
+    ops().census_gray([image1, image2, gray], [B, H, W])
+    return gray
+
+
+def _census_images(op, preds, image1, image2, mask, gray):
+    from ..train import unsup as U
+
+    N, B, H, W = U._check(preds, image1, image2, mask)
+    if preds.is_cuda:
+        _census_args(op, preds, gray, mask)
+        if gray is None:
+            gray = census_gray_planes(image1, image2)
+    return N, B, H, W, gray
+
+
+def census_loss_partials(flow_preds: torch.Tensor, image1: torch.Tensor, image2: torch.Tensor,
+                         mask: Optional[torch.Tensor] = None, out_penalty: float = 0.5, prm: Optional[torch.Tensor] = None,
+                         gray: Optional[torch.Tensor] = None):
+    """The census term's partial sums, fp32 (tiles, N, 4) -- per pixel tile and iteration
+    ``sum(mask term)``, the masked pixels that are not inside, the masked pixels inside but in the
+    border band and, for the last iteration, the sum of cen over the valid masked pixels -- and the
+    backward's coefficient plane ``mask valid 0.4 (h + 0.01)^-0.6``, fp32 (N, B, H, W):
+    ``(train/unsup.py:census_sums[None], None)`` on CPU tensors, the HIP kernel on GPU tensors
+    (``csrc/kernels/census.hip``; one launch, bitwise repeatable).  ``prm``: :func:`unsup_params`, in
+    place of ``out_penalty``; ``gray``: :func:`census_gray_planes` of the images, if at hand."""
+    N, B, H, W, gray = _census_images("census_loss", flow_preds, image1, image2, mask, gray)
+    if not flow_preds.is_cuda:
+        from ..train.unsup import census_sums
+
+        with torch.no_grad():
+            return census_sums(flow_preds, image1, image2, mask, out_penalty)[None], None
+    if prm is None:
+        prm = unsup_params(0.01, 0.001, 10.0, out_penalty, flow_preds.device)
+    part = torch.empty((census_tiles(B, H, W), N, 4), dtype=torch.float32, device=flow_preds.device)
+    coef = torch.empty((N, B, H, W), dtype=torch.float32, device=flow_preds.device)
+    ops().census_loss([flow_preds, gray, mask, prm, part, coef], [B, H, W, N])
+    return part, coef
+
+
+def census_loss_grad(flow_preds: torch.Tensor, image1: torch.Tensor, image2: torch.Tensor, mask: Optional[torch.Tensor],
+                     scale: torch.Tensor, out_penalty: float = 0.5, prm: Optional[torch.Tensor] = None,
+                     gray: Optional[torch.Tensor] = None, coef: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of ``sum_i scale[i] sum(mask term_i)`` in the predictions, (N, B, H, W, 2):
+    autograd through ``train/unsup.py:census_sums`` on CPU tensors, the gather kernel of
+    ``csrc/kernels/census.hip`` on GPU tensors (one launch, no atomics).  scale: (N,); ``gray`` and
+    ``coef``: what :func:`census_gray_planes` and :func:`census_loss_partials` returned for the same
+    operands (computed here when missing); ``out``: a gradient tensor to add into, in place of a new one."""
+    N, B, H, W, gray = _census_images("census_loss_bwd", flow_preds, image1, image2, mask, gray)
+    dev = flow_preds.device
+    named = (("scale", scale, (N,)),) + (() if out is None else (("out", out, tuple(flow_preds.shape)),)) + (
+        () if coef is None else (("coef", coef, (N, B, H, W)),))
+    for name, t, shape in named:
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.device != dev:
+            raise ValueError(f"census_loss_bwd: {name} must be {shape} on {dev}")
+        if dev.type == "cuda" and (t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 8):
+            raise ValueError(f"census_loss_bwd: {name} must be contiguous, 8-byte aligned fp32 on the GPU, got {t.dtype}")
+    if not flow_preds.is_cuda:
+        from ..train.unsup import census_sums
+
+        with torch.enable_grad():
+            f = flow_preds.detach().requires_grad_(True)
+            c = census_sums(f, image1, image2, mask, out_penalty)
+            g = torch.autograd.grad((c[:, 0] * scale.to(c.dtype)).sum(), f)[0]
+        return g if out is None else out.add_(g)
+    if coef is None:
+        coef = census_loss_partials(flow_preds, image1, image2, mask, out_penalty, prm, gray)[1]
+    grad = torch.empty(flow_preds.shape, dtype=torch.float32, device=dev) if out is None else out
+    ops().census_loss_bwd([flow_preds, gray, coef, scale, grad], [B, H, W, N, 0 if out is None else 1])
+    return grad
+
+
 def conv2d(spec: ConvSpec, x: torch.Tensor, act: int = ACT_NONE, out_dtype=torch.bfloat16, alpha: float = 1.0,
            res: Optional[torch.Tensor] = None, res_post: int = 0, cfg: Optional[int] = None) -> torch.Tensor:
     """Eager NHWC conv of a contiguous bf16 tensor [N, H, W, C] (C == cin8)."""

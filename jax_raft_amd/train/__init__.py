@@ -3,8 +3,8 @@ real datasets with the fused GPU augmentation) and the data-parallel trainer."""
 from .augment import (AugmentParams, MixedAugmentParams, SparseAugmentParams, augment_pairs, augment_pairs_mixed,
                       augment_pairs_sparse, sample_mixed, sample_sparse)
 from .datasets import FlowPairs, MixedFlowPairs, PairLoader, SequentialLoader, SparseFlowPairs
-from .unsup import unsup_loss, unsup_loss_reference
+from .unsup import census_sums, unsup_loss, unsup_loss_reference
 
 __all__ = ("augment_pairs", "AugmentParams", "FlowPairs", "PairLoader", "augment_pairs_sparse", "SparseAugmentParams",
            "sample_sparse", "SparseFlowPairs", "MixedFlowPairs", "MixedAugmentParams", "sample_mixed",
-           "augment_pairs_mixed", "SequentialLoader", "unsup_loss", "unsup_loss_reference")
+           "augment_pairs_mixed", "SequentialLoader", "unsup_loss", "unsup_loss_reference", "census_sums")

@@ -28,7 +28,8 @@ trains ``--dataset chairs`` on the label-1 pairs of FlyingChairs' split file onl
 
 Without ground truth: ``--loss unsup`` trains on the photometric + edge-aware smoothness loss of
 ``train/unsup.py`` (``--unsup-eps``, ``--unsup-eps-s``, ``--unsup-edge-kappa``, ``--unsup-smooth-weight``,
-``--unsup-out-penalty``; ``--gamma`` weights the iterations as ever), with augmentation records that keep
+``--unsup-out-penalty``; ``--unsup-photo census`` replaces the colour difference by the soft census term of
+UnFlow / SMURF; ``--gamma`` weights the iterations as ever), with augmentation records that keep
 brightness constancy.  ``--dataset frames`` lists the consecutive frames of every directory under ``--data``
 (no flow files; ``--loss unsup`` only).  On a labelled set the step also reports ``epe`` / ``1px`` / ``3px`` /
 ``5px``, which take no part in the gradient.
@@ -115,8 +116,11 @@ class TrainConfig:
     unsup_edge_kappa: float = 10.0
     unsup_smooth_weight: float = 0.05
     unsup_out_penalty: float = 0.5
+    unsup_photo: str = "charbonnier"   # the photometric term: "charbonnier" | "census" (7x7 soft census, SMURF's constants)
 
     def __post_init__(self):
+        if self.unsup_photo not in ("charbonnier", "census"):
+            raise ValueError(f"unknown unsup_photo {self.unsup_photo!r} (charbonnier or census)")
         if self.loss not in ("sequence", "unsup"):
             raise ValueError(f"unknown loss {self.loss!r} (sequence or unsup)")
         if self.loss == "unsup" and self.graph_step:
@@ -166,6 +170,7 @@ class TrainConfig:
 VAL_FIELDS = ("val", "val_every", "val_iters", "val_batch", "val_max_pairs", "chairs_split")
 # likewise left out of latest.json while they are at their defaults
 UNSUP_FIELDS = ("loss", "unsup_eps", "unsup_eps_s", "unsup_edge_kappa", "unsup_smooth_weight", "unsup_out_penalty")
+# (unsup_photo is recorded always: the tuple above is pinned by tests/test_unsup.py, which reads its tail as the five floats)
 
 
 def _adamw(params, cfg: TrainConfig, device, capturable: bool = False):
@@ -299,7 +304,8 @@ class Trainer:
         preds = self.model(img1, img2, train=train_bn, num_flow_updates=cfg.iters, autograd=True)
         if cfg.loss == "unsup":
             loss, metrics = unsup_loss(preds, img1, img2, None, cfg.gamma, cfg.unsup_eps, cfg.unsup_eps_s,
-                                       cfg.unsup_edge_kappa, cfg.unsup_smooth_weight, cfg.unsup_out_penalty)
+                                       cfg.unsup_edge_kappa, cfg.unsup_smooth_weight, cfg.unsup_out_penalty,
+                                       **({} if cfg.unsup_photo == "charbonnier" else {"photo": cfg.unsup_photo}))
             if self.labelled:      # a labelled set monitors the label-free run: metrics only, no gradient
                 with torch.no_grad():
                     _, sup = sequence_loss(preds.detach(), flow, valid, cfg.gamma, cfg.max_flow)

@@ -28,6 +28,23 @@ For iteration i and pixel (y, x) with ``f = flow_preds[i, b, y, x]`` (P = B H W)
    ``smooth`` = smooth_{N-1}, ``inside`` the share of the masked pixels (all pixels without a
    mask) that are inside.
 
+``photo="census"`` replaces steps 2-3 by the soft census term of UnFlow / SMURF (SMURF's constants,
+module constants here: a 7x7 patch, 0.81, 0.1, 0.01, 0.4), which compares the local ordering of
+intensities, not the colours, and so survives exposure, shadow and compression changes:
+
+2c. Grey planes in 8-bit levels, once per call: ``g(img) = 127.5 ((0.299 r + 0.587 g) + 0.114 b)``,
+    ``G1 = g(image1)``, ``G2 = g(image2)``.  The landing point is clamped instead of tested:
+    ``pxc = min(px >= 0 ? px : 0, W-1)`` (NaN becomes 0), ``x0 = floor(pxc)``, ``x1 = min(x0+1, W-1)``,
+    ``wx = pxc - x0``, y alike, and ``w = t + wy (b - t)`` as in step 2 on G2: a pixel that lands outside
+    has the border's grey.  The gradient flows through wx and wy only where ``inside``.
+3c. ``tau(D) = D / sqrt(0.81 + D^2)``; over the 48 offsets d != 0 of the patch
+    ``e_d = (tau(G1(p+d) - G1(p)) - tau(w(p+d) - w(p)))^2``, ``h(p) = sum_d e_d / (0.1 + e_d)``,
+    ``cen(p) = (h(p) + 0.01)^0.4``.  ``valid(p)`` = inside(p) and the patch lies in the frame
+    (3 <= x < W-3, 3 <= y < H-3).  The pixel's term is ``cen`` where valid, ``out_penalty`` where not
+    inside (no gradient), 0 inside but in the border band; every pixel adds ``0 (f.x + f.y)``.
+    ``photo_i = sum(mask term) / P``; the ``photo`` metric is the mean of cen over the valid masked
+    pixels of the last iteration.  ``eps`` is not used.
+
 The default parameter values are placeholders: this repository ships no data to tune them on.
 """
 from __future__ import annotations
@@ -38,6 +55,18 @@ import torch
 
 DEFAULTS = dict(gamma=0.8, eps=0.01, eps_s=0.001, edge_kappa=10.0, smooth_weight=0.05, out_penalty=0.5)
 MAX_NATIVE_N = 32
+PHOTO = ("charbonnier", "census")
+# the soft census term: SMURF's published constants, not configuration
+CENSUS_R = 3           # 7x7 patch, 48 offsets
+CENSUS_TAU = 0.81      # tau(D) = D / sqrt(0.81 + D^2)
+CENSUS_K = 0.1         # k(e) = e / (0.1 + e)
+CENSUS_H = 0.01        # cen = (h + 0.01)^0.4
+CENSUS_POW = 0.4
+
+
+def _check_photo(photo):
+    if photo not in PHOTO:
+        raise ValueError(f"unsup_loss: unknown photo {photo!r} (charbonnier or census)")
 
 
 def _check(flow_preds, image1, image2, mask):
@@ -127,14 +156,116 @@ def unsup_sums(flow_preds, image1, image2, mask=None, eps: float = 0.01, eps_s: 
     return torch.stack(rows)
 
 
-def _assemble(s: torch.Tensor, cnt, P: int, gamma: float, smooth_weight: float):
-    """(N, 4) sums and the number of masked pixels -> (loss, [photo, smooth, inside], weights (N,))."""
+def census_gray(img: torch.Tensor) -> torch.Tensor:
+    """Step 2c's grey plane (B, H, W) of an image (B, H, W, 3) in [-1, 1], in 8-bit levels."""
+    return 127.5 * ((0.299 * img[..., 0] + 0.587 * img[..., 1]) + 0.114 * img[..., 2])
+
+
+def sample_gray(flow: torch.Tensor, G2: torch.Tensor):
+    """Step 2c for one prediction (B, H, W, 2): ``(inside (B, H, W) bool, w (B, H, W))`` in G2's dtype;
+    w is differentiable in the flow through wx and wy where inside."""
+    B, H, W, _ = flow.shape
+    dev = flow.device
+    f = flow.detach().float()                          # the coordinates are fp32 whatever the input is
+    px = torch.arange(W, device=dev, dtype=torch.float32).view(1, 1, W) + f[..., 0]
+    py = torch.arange(H, device=dev, dtype=torch.float32).view(1, H, 1) + f[..., 1]
+    inside = (px >= 0) & (px <= W - 1) & (py >= 0) & (py <= H - 1)   # NaN fails
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    pxc = torch.where(px >= 0, px, zero).clamp(max=W - 1)            # NaN -> 0
+    pyc = torch.where(py >= 0, py, zero).clamp(max=H - 1)
+    x0f, y0f = torch.floor(pxc), torch.floor(pyc)
+    g = flow.to(G2.dtype)
+    slope = torch.where(inside.unsqueeze(-1), g - g.detach(), torch.zeros((), dtype=G2.dtype, device=dev))
+    wx = (pxc - x0f).to(G2.dtype) + slope[..., 0]
+    wy = (pyc - y0f).to(G2.dtype) + slope[..., 1]
+    x0, y0 = x0f.long(), y0f.long()
+    x1, y1 = torch.clamp(x0 + 1, max=W - 1), torch.clamp(y0 + 1, max=H - 1)
+    flat = G2.reshape(B, H * W)
+    tap = lambda yy, xx: torch.gather(flat, 1, (yy * W + xx).reshape(B, H * W)).view(B, H, W)
+    c00, c01, c10, c11 = tap(y0, x0), tap(y0, x1), tap(y1, x0), tap(y1, x1)
+    t = c00 + wx * (c01 - c00)
+    b = c10 + wx * (c11 - c10)
+    return inside, t + wy * (b - t)
+
+
+def census_patch(G1: torch.Tensor, w: torch.Tensor, radius: int = CENSUS_R) -> torch.Tensor:
+    """Step 3c's ``cen`` on the pixels whose patch lies in the frame, (B, H - 2 radius, W - 2 radius)
+    (H, W > 2 radius), by shifted slices."""
+    B, H, W = G1.shape
+    r = radius
+    tau = lambda D: D / torch.sqrt(CENSUS_TAU + D * D)
+    c1, cw = G1[:, r:H - r, r:W - r], w[:, r:H - r, r:W - r]
+    h = torch.zeros_like(cw)
+    for dy in range(-r, r + 1):
+        for dx in range(-r, r + 1):
+            if dx == 0 and dy == 0:
+                continue
+            n1, nw = G1[:, r + dy:H - r + dy, r + dx:W - r + dx], w[:, r + dy:H - r + dy, r + dx:W - r + dx]
+            e = (tau(n1 - c1) - tau(nw - cw)) ** 2
+            h = h + e / (CENSUS_K + e)
+    return (h + CENSUS_H) ** CENSUS_POW
+
+
+def census_sums(flow_preds, image1, image2, mask=None, out_penalty: float = 0.5) -> torch.Tensor:
+    """The sums the census term is assembled from, (N, 4), differentiable in ``flow_preds`` (column
+    0): ``sum(mask term)``, the count of masked pixels that are not inside, the count of masked
+    pixels inside but in the border band and -- last iteration only, 0 elsewhere -- the sum of cen
+    over the valid masked pixels.  fp64 inputs are computed in fp64 (the coordinates stay fp32)."""
+    N, B, H, W = _check(flow_preds, image1, image2, mask)
+    cdt = torch.float64 if flow_preds.dtype == torch.float64 else torch.float32
+    G1, G2 = census_gray(image1.to(cdt)), census_gray(image2.to(cdt))
+    dev = flow_preds.device
+    on = torch.ones((B, H, W), dtype=torch.bool, device=dev) if mask is None else mask >= 0.5
+    m = on.to(cdt)
+    r = CENSUS_R
+    geom = torch.zeros((B, H, W), dtype=torch.bool, device=dev)
+    if H > 2 * r and W > 2 * r:
+        geom[:, r:H - r, r:W - r] = True
+    zero = torch.zeros((), dtype=cdt, device=dev)
+    rows = []
+    for i in range(N):
+        f = flow_preds[i].to(cdt)
+        inside, w = sample_gray(f, G2)
+        if H > 2 * r and W > 2 * r:
+            cen = torch.nn.functional.pad(census_patch(G1, w), (r, r, r, r))
+        else:
+            cen = torch.zeros((B, H, W), dtype=cdt, device=dev)
+        valid = inside & geom
+        term = torch.where(valid, cen, torch.where(inside, zero, zero + out_penalty)) + 0.0 * (f[..., 0] + f[..., 1])
+        sel = on & valid
+        last = cen.detach()[sel].sum() if i == N - 1 else cen.new_zeros(())
+        rows.append(torch.stack([(m * term).sum(), (on & ~inside).sum().to(cdt), (on & inside & ~geom).sum().to(cdt), last]))
+    return torch.stack(rows)
+
+
+def smooth_sums(flow_preds, image1, eps_s: float = 0.001, edge_kappa: float = 10.0) -> torch.Tensor:
+    """Step 4's sums (before the division by 2P), (N,), differentiable in ``flow_preds``."""
+    cdt = torch.float64 if flow_preds.dtype == torch.float64 else torch.float32
+    ax, ay = edge_weights(image1.to(cdt), edge_kappa)
+    rows = []
+    for i in range(flow_preds.shape[0]):
+        f = flow_preds[i].to(cdt)
+        rows.append((ax.unsqueeze(-1) * torch.sqrt((f[:, :, 1:] - f[:, :, :-1]) ** 2 + eps_s * eps_s)).sum()
+                    + (ay.unsqueeze(-1) * torch.sqrt((f[:, 1:] - f[:, :-1]) ** 2 + eps_s * eps_s)).sum())
+    return torch.stack(rows)
+
+
+def _census_columns(c: torch.Tensor, smooth: torch.Tensor):
+    """Census sums (N, 4) and smoothness sums (N,) -> the (N, 4) layout of ``_assemble`` and the band count."""
+    return torch.stack([c[:, 0], smooth, c[:, 1], c[:, 3]], dim=-1), c[-1, 2].detach()
+
+
+def _assemble(s: torch.Tensor, cnt, P: int, gamma: float, smooth_weight: float, band=None):
+    """(N, 4) sums and the number of masked pixels -> (loss, [photo, smooth, inside], weights (N,)).
+    ``band`` (census): the last iteration's masked pixels inside but without a term of their own,
+    left out of the photo metric's mean."""
     n = s.shape[0]
     w = (gamma ** torch.arange(n - 1, -1, -1, device=s.device, dtype=torch.float64)).to(s.dtype)
     loss = (w * (s[:, 0] / P + smooth_weight * (s[:, 1] / (2.0 * P)))).sum()
     nan = torch.full((), float("nan"), dtype=s.dtype, device=s.device)
     ins = cnt - s[-1, 2].detach()
-    photo = torch.where(ins > 0, s[-1, 3].detach() / ins.clamp_min(1.0), nan)
+    den = ins if band is None else ins - band
+    photo = torch.where(den > 0, s[-1, 3].detach() / den.clamp_min(1.0), nan)
     inside = torch.where(cnt > 0, ins / cnt.clamp_min(1.0), nan)
     return loss, torch.stack([photo, s[-1, 1].detach() / (2.0 * P), inside]), w
 
@@ -147,11 +278,18 @@ def _count(mask, P: int, device, dtype):
 
 def unsup_loss_reference(flow_preds, image1, image2, mask=None, gamma: float = 0.8, eps: float = 0.01,
                          eps_s: float = 0.001, edge_kappa: float = 10.0, smooth_weight: float = 0.05,
-                         out_penalty: float = 0.5) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+                         out_penalty: float = 0.5, photo: str = "charbonnier") -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """The golden op (module docstring).  flow_preds (N, B, H, W, 2), channel 0 = x, in pixels;
-    image1 / image2 (B, H, W, 3) in [-1, 1]; mask (B, H, W), used where >= 0.5, or None."""
-    s = unsup_sums(flow_preds, image1, image2, mask, eps, eps_s, edge_kappa, out_penalty)
+    image1 / image2 (B, H, W, 3) in [-1, 1]; mask (B, H, W), used where >= 0.5, or None;
+    photo: "charbonnier" (steps 2-3) | "census" (steps 2c-3c)."""
+    _check_photo(photo)
     P = flow_preds[0].numel() // 2
+    if photo == "census":
+        c = census_sums(flow_preds, image1, image2, mask, out_penalty)
+        s, band = _census_columns(c, smooth_sums(flow_preds, image1, eps_s, edge_kappa))
+        loss, mets, _ = _assemble(s, _count(mask, P, s.device, s.dtype), P, gamma, smooth_weight, band)
+        return loss, {"photo": mets[0], "smooth": mets[1], "inside": mets[2]}
+    s = unsup_sums(flow_preds, image1, image2, mask, eps, eps_s, edge_kappa, out_penalty)
     loss, mets, _ = _assemble(s, _count(mask, P, s.device, s.dtype), P, gamma, smooth_weight)
     return loss, {"photo": mets[0], "smooth": mets[1], "inside": mets[2]}
 
@@ -181,17 +319,56 @@ class _UnsupLoss(torch.autograd.Function):
         return (grad,) + (None,) * 9
 
 
+class _CensusLoss(torch.autograd.Function):
+    """The census term from csrc/kernels/census.hip, the smoothness term from the two kernels of
+    unsup.hip called with a zero photometric scale."""
+
+    @staticmethod
+    def forward(ctx, preds, image1, image2, mask, gamma, eps, eps_s, edge_kappa, smooth_weight, out_penalty):
+        from ..ops import native as nat
+
+        P = preds[0].numel() // 2
+        prm = nat.unsup_params(eps, eps_s, edge_kappa, out_penalty, preds.device)
+        gray = nat.census_gray_planes(image1, image2)
+        part, coef = nat.census_loss_partials(preds, image1, image2, mask, prm=prm, gray=gray)
+        smooth = nat.unsup_loss_partials(preds, image1, image2, mask, prm=prm).double().sum(0)[:, 1]
+        s, band = _census_columns(part.double().sum(0), smooth)      # tile order; the counts stay exact
+        loss, mets, w = _assemble(s, _count(mask, P, preds.device, torch.float64), P, gamma, smooth_weight, band)
+        scale = torch.stack([torch.zeros_like(w), w * (smooth_weight / (2.0 * P)), w / P], dim=-1)
+        ctx.save_for_backward(preds, image1, image2, mask, prm, gray, coef, scale)
+        mets = mets.float()
+        ctx.mark_non_differentiable(mets)
+        return loss.float(), mets
+
+    @staticmethod
+    def backward(ctx, gl, _gm):
+        from ..ops import native as nat
+
+        preds, image1, image2, mask, prm, gray, coef, scale = ctx.saved_tensors
+        scale = (scale * gl.double()).float()
+        grad = nat.unsup_loss_grad(preds, image1, image2, mask, scale[:, :2].contiguous(), prm=prm)
+        nat.census_loss_grad(preds, image1, image2, mask, scale[:, 2].contiguous(), prm=prm, gray=gray, coef=coef, out=grad)
+        return (grad,) + (None,) * 9
+
+
 def unsup_loss(flow_preds, image1, image2, mask=None, gamma: float = 0.8, eps: float = 0.01, eps_s: float = 0.001,
                edge_kappa: float = 10.0, smooth_weight: float = 0.05,
-               out_penalty: float = 0.5) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+               out_penalty: float = 0.5, photo: str = "charbonnier") -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """``unsup_loss_reference`` for training: GPU tensors with N <= 32 run the native kernels
     (csrc/kernels/unsup.hip: the partial sums in one pass over the predictions, the gradient in one
-    more, no host synchronisation, bitwise repeatable); everything else runs the golden op."""
+    more; ``photo="census"``: the tiled stencil kernels of csrc/kernels/census.hip for the
+    photometric term; no host synchronisation, bitwise repeatable); everything else runs the golden op."""
+    _check_photo(photo)
     if not (flow_preds.is_cuda and flow_preds.shape[0] <= MAX_NATIVE_N and flow_preds.dtype != torch.float64):
         return unsup_loss_reference(flow_preds, image1, image2, mask, gamma, eps, eps_s, edge_kappa, smooth_weight,
-                                    out_penalty)
+                                    out_penalty, photo)
     _check(flow_preds, image1, image2, mask)
     m = None if mask is None else mask.float().contiguous()
+    if photo == "census":
+        loss, mets = _CensusLoss.apply(flow_preds.float().contiguous(), image1.float().contiguous(),
+                                       image2.float().contiguous(), m, float(gamma), float(eps), float(eps_s),
+                                       float(edge_kappa), float(smooth_weight), float(out_penalty))
+        return loss, {"photo": mets[0], "smooth": mets[1], "inside": mets[2]}
     loss, mets = _UnsupLoss.apply(flow_preds.float().contiguous(), image1.float().contiguous(),
                                   image2.float().contiguous(), m, float(gamma), float(eps), float(eps_s),
                                   float(edge_kappa), float(smooth_weight), float(out_penalty))

@@ -15,7 +15,12 @@ on one GPU, at the ``chairs`` shape (N, B, H, W) = (12, 6, 368, 496):
     ``--block`` steps alternated for ``--rounds`` rounds after a warm-up of both.  No target: the
     difference and the spread between blocks of one arm are reported.
 
-  python tools/unsup_bench.py [--out profiles/unsup_loss_overhead.txt]
+``--photo census`` measures the census photometric term (csrc/kernels/census.hip) the same way: (a)
+its three launches, (b) ``unsup_loss(..., photo="census")`` against the golden op with
+``photo="census"``, (c) the training step with ``unsup_photo="census"`` against
+``unsup_photo="charbonnier"``; the default output is then ``profiles/census_loss_overhead.txt``.
+
+  python tools/unsup_bench.py [--photo census] [--out profiles/unsup_loss_overhead.txt]
 """
 import argparse
 import os
@@ -70,14 +75,35 @@ def launches(dev, reps):
             "fwd_mb": mb(preds, i1, i2, part), "bwd_mb": mb(preds, i1, i2, grad)}
 
 
-def pair(dev, reps):
+def census_launches(dev, reps):
+    preds, i1, i2 = inputs(dev)
+    P = B * H * W
+    prm = nat.unsup_params(0.01, 0.001, 10.0, 0.5, dev)
+    gray = torch.empty(2, B, H, W, device=dev)
+    part, coef = torch.empty(nat.census_tiles(B, H, W), N, 4, device=dev), torch.empty(N, B, H, W, device=dev)
+    grad = torch.zeros_like(preds)
+    scale = torch.full((N,), 1.0 / P, device=dev)
+    ops = {"census_gray": (lambda: nat.ops().census_gray([i1, i2, gray], [B, H, W]), (i1, i2, gray), "both images, grey planes"),
+           "census_loss": (lambda: nat.ops().census_loss([preds, gray, None, prm, part, coef], [B, H, W, N]),
+                           (preds, gray, part, coef), "predictions, grey planes, partials, coefficients"),
+           "census_loss_bwd": (lambda: nat.ops().census_loss_bwd([preds, gray, coef, scale, grad], [B, H, W, N, 0]),
+                               (preds, gray, coef, grad), "predictions, grey planes, coefficients, gradient")}
+    mb = lambda ts: sum(t.numel() * t.element_size() for t in ts) / 1e6
+    out = []
+    for name, (fn, ts, what) in ops.items():                # in this order: each needs the one before
+        out.append((name, events(fn, dev, reps), mb(ts), what))
+    return out
+
+
+def pair(dev, reps, photo="charbonnier"):
     preds, i1, i2 = inputs(dev)
     f = preds.clone().requires_grad_(True)
+    kw = {} if photo == "charbonnier" else {"photo": photo}
 
     def run(loss_fn):
         def step():
             f.grad = None
-            loss_fn(f, i1, i2)[0].backward()
+            loss_fn(f, i1, i2, **kw)[0].backward()
         return step
 
     arms = {"native": run(unsup_loss), "torch": run(unsup_loss_reference)}
@@ -96,7 +122,11 @@ def pair(dev, reps):
 def training(args, dev):
     total = args.warmup + args.block * args.rounds
     kw = dict(arch=args.arch, steps=total, batch=BATCH, iters=args.iters, size=(384, 512), log_every=10 ** 9)
-    arms = {"unsup": Trainer(TrainConfig(loss="unsup", **kw)), "sequence": Trainer(TrainConfig(**kw))}
+    if args.photo == "census":
+        arms = {"census": Trainer(TrainConfig(loss="unsup", unsup_photo="census", **kw)),
+                "charbonnier": Trainer(TrainConfig(loss="unsup", **kw))}
+    else:
+        arms = {"unsup": Trainer(TrainConfig(loss="unsup", **kw)), "sequence": Trainer(TrainConfig(**kw))}
     for name, tr in arms.items():
         t0 = time.perf_counter()
         for _ in range(args.warmup):
@@ -119,7 +149,8 @@ def training(args, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/unsup_loss_overhead.txt")
+    ap.add_argument("--photo", default="charbonnier", choices=("charbonnier", "census"))
+    ap.add_argument("--out", default=None, help="default: profiles/unsup_loss_overhead.txt, census_loss_overhead.txt with --photo census")
     ap.add_argument("--reps", type=int, default=500)
     ap.add_argument("--pair-reps", type=int, default=20)
     ap.add_argument("--block", type=int, default=20, help="steps per block")
@@ -129,20 +160,29 @@ def main():
     ap.add_argument("--iters", type=int, default=12)
     ap.add_argument("--skip-training", action="store_true", help="(a) and (b) only")
     args = ap.parse_args()
+    census = args.photo == "census"
+    args.out = args.out or ("profiles/census_loss_overhead.txt" if census else "profiles/unsup_loss_overhead.txt")
     assert torch.cuda.is_available(), "unsup_bench measures on the GPU"
     dev = torch.device("cuda", 0)
     mean = lambda v: sum(v) / len(v)
-    lines = [f"label-free loss (photometric + edge-aware smoothness), {torch.cuda.get_device_name(dev)}",
+    lines = [f"label-free loss ({'census' if census else 'photometric'} + edge-aware smoothness), {torch.cuda.get_device_name(dev)}",
              f"predictions (N, B, H, W) = ({N}, {B}, {H}, {W}), fp32; no mask", ""]
-    kt = launches(dev, args.reps)
-    lines += [f"(a) GPU time per launch, device events over {args.reps} repetitions:",
-              f"    unsup_loss     {kt['fwd']:8.1f} us   {kt['fwd_mb']:6.1f} MB at least (predictions, both images, partials)"
-              f"  -> {kt['fwd_mb'] / kt['fwd'] * 1e3:6.0f} GB/s of them",
-              f"    unsup_loss_bwd {kt['bwd']:8.1f} us   {kt['bwd_mb']:6.1f} MB at least (predictions, both images, gradient)"
-              f"  -> {kt['bwd_mb'] / kt['bwd'] * 1e3:6.0f} GB/s of them",
-              "    (neighbouring flows and the texel gathers are re-reads that the caches serve; they are not in the byte counts)", ""]
+    if census:
+        lines += [f"(a) GPU time per launch, device events over {args.reps} repetitions:"]
+        for name, us, mbytes, what in census_launches(dev, args.reps):
+            lines.append(f"    {name:16s} {us:8.1f} us   {mbytes:6.1f} MB at least ({what})  -> {mbytes / us * 1e3:6.0f} GB/s of them")
+        lines += ["    (the halo's samples and the texel gathers are re-reads that the caches serve; they are not in the byte counts;",
+                  "     the census loss also runs unsup_loss and unsup_loss_bwd for the smoothness term: profiles/unsup_loss_overhead.txt)", ""]
+    kt = None if census else launches(dev, args.reps)
+    if kt:
+        lines += [f"(a) GPU time per launch, device events over {args.reps} repetitions:",
+                  f"    unsup_loss     {kt['fwd']:8.1f} us   {kt['fwd_mb']:6.1f} MB at least (predictions, both images, partials)"
+                  f"  -> {kt['fwd_mb'] / kt['fwd'] * 1e3:6.0f} GB/s of them",
+                  f"    unsup_loss_bwd {kt['bwd']:8.1f} us   {kt['bwd_mb']:6.1f} MB at least (predictions, both images, gradient)"
+                  f"  -> {kt['bwd_mb'] / kt['bwd'] * 1e3:6.0f} GB/s of them",
+                  "    (neighbouring flows and the texel gathers are re-reads that the caches serve; they are not in the byte counts)", ""]
     print("\n".join(lines), flush=True)
-    times, peak = pair(dev, args.pair_reps)
+    times, peak = pair(dev, args.pair_reps, args.photo)
     spread = max(abs(v[0] - v[1]) for v in times.values())
     gain = mean(times["torch"]) - mean(times["native"])
     lines += [f"(b) loss forward + backward, {args.pair_reps} repetitions per run, arms alternated native / torch x 2:"]
@@ -156,15 +196,17 @@ def main():
     if not args.skip_training:
         rate, skipped = training(args, dev)
         ms = lambda x: 1000 * BATCH / x
-        u, s = mean(rate["unsup"]), mean(rate["sequence"])
+        first, second = list(rate)
+        u, s = mean(rate[first]), mean(rate[second])
         lines += [f"(c) training step, {args.arch}, 384x512, batch {BATCH}, {args.iters} iterations, SyntheticFlow; {args.block} steps per "
-                  f"block, blocks alternated unsup / sequence x {args.rounds} in one process after {args.warmup} warm-up steps each"]
+                  f"block, blocks alternated {first} / {second} x {args.rounds} in one process after {args.warmup} warm-up steps each"]
         for k in rate:
             lines.append(f"    {k:8s} {mean(rate[k]):7.1f} pairs/s  {ms(mean(rate[k])):6.2f} ms/step  [per block: "
                          + ", ".join(f"{v:.1f}" for v in rate[k]) + f"]   skipped steps: {skipped[k]}")
-        lines += [f"    unsup - sequence: {ms(u) - ms(s):+.2f} ms/step ({100 * (u - s) / s:+.1f} % pairs/s); largest spread between "
+        lines += [f"    {first} - {second}: {ms(u) - ms(s):+.2f} ms/step ({100 * (u - s) / s:+.1f} % pairs/s); largest spread between "
                   f"blocks of one arm {max(max(v) - min(v) for v in rate.values()):.1f} pairs/s",
-                  "    (the unsup step also runs the sequence loss's forward kernel for the EPE metrics of the labelled synthetic set)", ""]
+                  "    (both arms also run the sequence loss's forward kernel for the EPE metrics of the labelled synthetic set)" if census
+                  else "    (the unsup step also runs the sequence loss's forward kernel for the EPE metrics of the labelled synthetic set)", ""]
     lines += ["Not measured: accuracy.  There is no checkpoint and no real data here, and the loss's default weights are placeholders.", ""]
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
