@@ -392,6 +392,17 @@ int jr_census_loss(const float* pred, const float* gray, const float* mask, cons
                    int B, int H, int W, int N, hipStream_t stream);
 int jr_census_loss_bwd(const float* pred, const float* gray, const float* coef, const float* scale, float* grad, int B,
                        int H, int W, int N, int add, hipStream_t stream);
+// Range-map occlusion estimate (occlusion.hip; train/occlusion.py:range_map / visibility_masks, bitwise).
+// flow_fw / flow_bw fp32 [B][H][W][2], 8-byte aligned; H * W <= JR_RANGE_MAX_PIXELS, so that no flow
+// field can overflow an int32 cell (256 per source pixel); at most 65535 maps per launch.
+// jr_range_splat ADDS every source pixel's four integer bilinear weights (1/256 of a pixel) into acc int32
+// [D][B][H][W] with integer atomics, so the caller clears it first; flow_bw = nullptr: D = 1, else D = 2
+// and acc[d] is the range map of flow d.  jr_range_visible writes vis fp32 [2][B][H][W]: 1 where the
+// pixel's own flow lands outside the frame or the OPPOSITE direction's acc is at least T, else 0.
+#define JR_RANGE_MAX_PIXELS (1L << 23)
+int jr_range_splat(const float* flow_fw, const float* flow_bw, int* acc, int B, int H, int W, hipStream_t stream);
+int jr_range_visible(const float* flow_fw, const float* flow_bw, const int* acc, float* vis, int B, int H, int W,
+                     int T, hipStream_t stream);
 // Conv of a 2-channel input (the flow branch's 7x7 / 3x3): x bf16 NHWC
 // [N][H][W][x_cstride] (channels 0, 1 used), stride 1, output H x W; w bf16
 // MFMA A fragments [cout/16][NKC][64 lanes][8] (jax_raft_amd/ops/native.py:

@@ -2377,6 +2377,67 @@ void pyr_bwd_dc_op(const TList& t, IList i, double scale) {
   JR_CHECK_OK(jr_pyr_bwd_dc(g[0], g[1], g[2], g[3], L, M, h, w, (float)scale, dc.data_ptr(), cur_stream()));
 }
 
+// ------------------------------------------------ range-map occlusion estimate
+// (kernels occlusion.hip).  range_splat: t = [flow_fw, flow_bw? (fp32 [B][H][W][2]), acc (int32 [D][B][H][W],
+// D = 2 with flow_bw, else 1; cleared by the caller)], i = [B, H, W].  range_visible: t = [flow_fw, flow_bw,
+// acc (int32 [2][B][H][W]), vis (fp32 [2][B][H][W])], i = [B, H, W, T] (visible: the opposite acc >= T).
+static int64_t range_sizes(const std::string& op, const IList& i) {
+  const int64_t B = i[0], H = i[1], W = i[2];
+  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && H <= JR_RANGE_MAX_PIXELS && W <= JR_RANGE_MAX_PIXELS &&
+                  H * W <= JR_RANGE_MAX_PIXELS, op, ": sizes (H * W must be at most 2^23: an int32 cell holds 256 per source)");
+  TORCH_CHECK(2 * B <= 65535, op, ": at most 32767 samples, got ", B);
+  return B * H * W;
+}
+static void range_flow(const std::string& op, const char* what, const at::Tensor& f, int64_t P) {
+  check_f32(f, (op + what).c_str());
+  TORCH_CHECK(f.numel() == 2 * P && reinterpret_cast<uintptr_t>(f.data_ptr()) % 8 == 0, op, what,
+              " must hold [B][H][W][2] = ", 2 * P, " elements, 8-byte aligned");
+}
+static void range_acc(const std::string& op, const at::Tensor& acc, int64_t n) {
+  TORCH_CHECK(acc.defined() && acc.is_cuda() && acc.scalar_type() == at::kInt && acc.is_contiguous() && acc.numel() == n,
+              op, ": acc must be a contiguous device int32 tensor of ", n, " elements");
+}
+static Launch make_range_splat(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  const std::string op = "range_splat";
+  at::Tensor fw = opt(t, 0), bw = opt(t, 1), acc = opt(t, 2);
+  const int64_t P = range_sizes(op, i);
+  range_flow(op, ": flow_fw", fw, P);
+  if (bw.defined()) {
+    range_flow(op, ": flow_bw", bw, P);
+    TORCH_CHECK(bw.device() == fw.device(), op, ": flow_bw is on another device");
+  }
+  range_acc(op, acc, (bw.defined() ? 2 : 1) * P);
+  TORCH_CHECK(acc.device() == fw.device(), op, ": acc is on another device");
+  census_no_alias(op, ": acc", acc, bw.defined() ? std::vector<at::Tensor>{fw, bw} : std::vector<at::Tensor>{fw});
+  keep.push_back(fw); keep.push_back(acc);
+  if (bw.defined()) keep.push_back(bw);
+  const float* fp = fw.data_ptr<float>();
+  const float* bp = bw.defined() ? bw.data_ptr<float>() : nullptr;
+  int* ap = acc.data_ptr<int>();
+  const int b = (int)i[0], h = (int)i[1], w = (int)i[2];
+  return [=](hipStream_t s, int) { return jr_range_splat(fp, bp, ap, b, h, w, s); };
+}
+static Launch make_range_visible(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  const std::string op = "range_visible";
+  at::Tensor fw = opt(t, 0), bw = opt(t, 1), acc = opt(t, 2), vis = opt(t, 3);
+  const int64_t P = range_sizes(op, i);
+  TORCH_CHECK(i[3] >= INT32_MIN && i[3] <= INT32_MAX, op, ": the threshold T must fit an int32");
+  range_flow(op, ": flow_fw", fw, P);
+  range_flow(op, ": flow_bw", bw, P);
+  range_acc(op, acc, 2 * P);
+  check_f32(vis, "range_visible: vis");
+  TORCH_CHECK(vis.numel() == 2 * P, op, ": vis must hold [2][B][H][W] = ", 2 * P, " elements");
+  for (const at::Tensor* v : {&bw, &acc, &vis}) TORCH_CHECK(v->device() == fw.device(), op, ": operands on several devices");
+  census_no_alias(op, ": vis", vis, {fw, bw, acc});
+  census_no_alias(op, ": acc", acc, {fw, bw});
+  keep.insert(keep.end(), {fw, bw, acc, vis});
+  const float *fp = fw.data_ptr<float>(), *bp = bw.data_ptr<float>();
+  const int* ap = acc.data_ptr<int>();
+  float* vp = vis.data_ptr<float>();
+  const int b = (int)i[0], h = (int)i[1], w = (int)i[2], T = (int)i[3];
+  return [=](hipStream_t s, int) { return jr_range_visible(fp, bp, ap, vp, b, h, w, T, s); };
+}
+
 // ----------------------------------------------------------------- op table
 // One row per launch op: its name, signature class, the int-list lengths it accepts and its
 // maker.  Both front-ends are generated from the row (register_ops): the eager op
@@ -2468,6 +2529,8 @@ static const std::vector<OpRow>& op_table() {
       row_ti("census_gray", 3, 3, make_census_gray),
       row_ti("census_loss", 4, 4, make_census_loss),
       row_ti("census_loss_bwd", 5, 5, make_census_loss_bwd),
+      row_ti("range_splat", 3, 3, make_range_splat),
+      row_ti("range_visible", 4, 4, make_range_visible),
       // fp32 parity mode
       row_tia("conv_f32", "alpha", 22, 22, make_conv_f32),
       row_ti("stats_f32", 3, 3, make_stats_f32),

@@ -58,6 +58,7 @@ KERNEL_SOURCES = [
     CSRC / "kernels" / "metrics.hip",
     CSRC / "kernels" / "unsup.hip",
     CSRC / "kernels" / "census.hip",
+    CSRC / "kernels" / "occlusion.hip",
 ]
 HOST_SOURCES = [CSRC / "runtime" / "binding.cpp", CSRC / "runtime" / "png.cpp"]
 # every header of csrc/ is a dependency of every object (a missed header left stale objects in

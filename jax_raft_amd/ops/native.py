@@ -1059,6 +1059,78 @@ def census_loss_grad(flow_preds: torch.Tensor, image1: torch.Tensor, image2: tor
     return grad
 
 
+_fb_thr = {}
+
+
+def _range_flows(op: str, flow_fw, flow_bw):
+    """Host checks of a flow pair (flow_bw may be None), before any launch -> (B, H, W)."""
+    from ..train import occlusion as O
+
+    B, H, W = O._check_flow(op, flow_fw)
+    if flow_bw is not None:
+        O._check_flow(op, flow_bw)
+        if flow_bw.shape != flow_fw.shape or flow_bw.device != flow_fw.device:
+            raise ValueError(f"{op}: flow_fw and flow_bw must have the same shape and device")
+    if flow_fw.is_cuda:
+        for name, f in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
+            if f is not None and (not f.is_contiguous() or f.data_ptr() % 8):
+                raise ValueError(f"{op}: {name} must be contiguous and 8-byte aligned on the GPU")
+        if 2 * B > 65535:
+            raise ValueError(f"{op}: at most 32767 samples, got {B}")
+    return B, H, W
+
+
+def range_map(flow_fw: torch.Tensor, flow_bw: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The range map of a (B, H, W, 2) fp32 flow, int32 (B, H, W) in 1/256 of a source pixel -- with
+    ``flow_bw`` both directions' maps, (2, B, H, W), from one launch: ``train/occlusion.py:range_map``
+    on CPU tensors, the clear + the integer-atomic splat of ``csrc/kernels/occlusion.hip`` on GPU tensors
+    (bitwise equal, any width, no host synchronisation)."""
+    from ..train import occlusion as O
+
+    B, H, W = _range_flows("range_map", flow_fw, flow_bw)
+    O.check_pixels("range_map", H, W)
+    if not flow_fw.is_cuda:
+        return O.range_map(flow_fw) if flow_bw is None else torch.stack([O.range_map(flow_fw), O.range_map(flow_bw)])
+    fw, bw = flow_fw.detach(), None if flow_bw is None else flow_bw.detach()
+    acc = torch.empty((B, H, W) if bw is None else (2, B, H, W), dtype=torch.int32, device=fw.device)
+    acc.zero_()
+    ops().range_splat([fw, bw, acc], [B, H, W])
+    return acc
+
+
+def visibility_masks(flow_fw: torch.Tensor, flow_bw: torch.Tensor, kind: str, thr: float = 0.5, alpha: float = 0.01,
+                     beta: float = 0.5) -> torch.Tensor:
+    """The visibility masks of a (B, H, W, 2) fp32 flow pair, fp32 (2, B, H, W) (0: fw, 1: bw; 1.0 = use
+    the pixel), so that ``masks.view(2 * B, H, W)`` is the mask of the stacked batch:
+    ``train/occlusion.py:visibility_masks`` on CPU tensors; on GPU tensors ``kind="range"`` runs the
+    clear, the splat and the mask launch of ``csrc/kernels/occlusion.hip``, ``kind="fb"`` :func:`fb_check`
+    plus elementwise ops on its output (both bitwise equal, no gradient)."""
+    from ..train import occlusion as O
+
+    if kind not in O.KINDS:
+        raise ValueError(f"visibility_masks: unknown kind {kind!r} (range or fb)")
+    if flow_bw is None:
+        raise ValueError("visibility_masks: both flows are needed")
+    B, H, W = _range_flows("visibility_masks", flow_fw, flow_bw)
+    if kind == "range":
+        O.check_pixels("visibility_masks", H, W)
+    if not flow_fw.is_cuda:
+        return torch.stack(O.visibility_masks(flow_fw, flow_bw, kind, thr, alpha, beta))
+    fw, bw = flow_fw.detach(), flow_bw.detach()
+    if kind == "range":
+        acc = range_map(fw, bw)
+        vis = torch.empty((2, B, H, W), dtype=torch.float32, device=fw.device)
+        ops().range_visible([fw, bw, acc, vis], [B, H, W, O.range_threshold(thr)])
+        return vis
+    key = (str(fw.device), float(alpha), float(beta))       # uploaded once, as unsup_params
+    if key not in _fb_thr:
+        if len(_fb_thr) >= 64:
+            _fb_thr.clear()
+        _fb_thr[key] = torch.tensor(key[1:], dtype=torch.float32, device=fw.device)
+    occ_fw, occ_bw = fb_check(fw, bw, thr=_fb_thr[key])
+    return torch.stack([~O.lands_inside(fw) | ~occ_fw, ~O.lands_inside(bw) | ~occ_bw]).float()
+
+
 def conv2d(spec: ConvSpec, x: torch.Tensor, act: int = ACT_NONE, out_dtype=torch.bfloat16, alpha: float = 1.0,
            res: Optional[torch.Tensor] = None, res_post: int = 0, cfg: Optional[int] = None) -> torch.Tensor:
     """Eager NHWC conv of a contiguous bf16 tensor [N, H, W, C] (C == cin8)."""

@@ -30,7 +30,9 @@ Without ground truth: ``--loss unsup`` trains on the photometric + edge-aware sm
 ``train/unsup.py`` (``--unsup-eps``, ``--unsup-eps-s``, ``--unsup-edge-kappa``, ``--unsup-smooth-weight``,
 ``--unsup-out-penalty``; ``--unsup-photo census`` replaces the colour difference by the soft census term of
 UnFlow / SMURF; ``--gamma`` weights the iterations as ever), with augmentation records that keep
-brightness constancy.  ``--dataset frames`` lists the consecutive frames of every directory under ``--data``
+brightness constancy.  ``--unsup-occlusion fb | range`` runs both directions in the step (2 x batch pairs
+through the model) and leaves the occluded pixels out of the photometric term (train/occlusion.py;
+``--unsup-occ-thr``: the range map's threshold, ``--unsup-occ-after``: the first step with masks).  ``--dataset frames`` lists the consecutive frames of every directory under ``--data``
 (no flow files; ``--loss unsup`` only).  On a labelled set the step also reports ``epe`` / ``1px`` / ``3px`` /
 ``5px``, which take no part in the gradient.
 
@@ -117,8 +119,18 @@ class TrainConfig:
     unsup_smooth_weight: float = 0.05
     unsup_out_penalty: float = 0.5
     unsup_photo: str = "charbonnier"   # the photometric term: "charbonnier" | "census" (7x7 soft census, SMURF's constants)
+    # Occlusion masks for the photometric term (train/occlusion.py): "none" | "fb" (forward-backward consistency) |
+    # "range" (the range map; unsup_occ_thr = the share of a pixel that must map back onto it).  The model then runs
+    # both directions as one batch of 2 * batch pairs; the masks apply from step unsup_occ_after on.
+    unsup_occlusion: str = "none"
+    unsup_occ_thr: float = 0.5
+    unsup_occ_after: int = 0
 
     def __post_init__(self):
+        if self.unsup_occlusion not in ("none", "fb", "range"):
+            raise ValueError(f"unknown unsup_occlusion {self.unsup_occlusion!r} (none, fb or range)")
+        if self.loss != "unsup" and (self.unsup_occlusion, self.unsup_occ_thr, self.unsup_occ_after) != ("none", 0.5, 0):
+            raise ValueError("unsup_occlusion, unsup_occ_thr and unsup_occ_after take loss='unsup'")
         if self.unsup_photo not in ("charbonnier", "census"):
             raise ValueError(f"unknown unsup_photo {self.unsup_photo!r} (charbonnier or census)")
         if self.loss not in ("sequence", "unsup"):
@@ -170,7 +182,8 @@ class TrainConfig:
 VAL_FIELDS = ("val", "val_every", "val_iters", "val_batch", "val_max_pairs", "chairs_split")
 # likewise left out of latest.json while they are at their defaults
 UNSUP_FIELDS = ("loss", "unsup_eps", "unsup_eps_s", "unsup_edge_kappa", "unsup_smooth_weight", "unsup_out_penalty")
-# (unsup_photo is recorded always: the tuple above is pinned by tests/test_unsup.py, which reads its tail as the five floats)
+# (unsup_photo and the unsup_occ* fields are recorded always: the tuple above is pinned by tests/test_unsup.py, which
+# reads its tail as the five floats)
 
 
 def _adamw(params, cfg: TrainConfig, device, capturable: bool = False):
@@ -301,8 +314,10 @@ class Trainer:
         cfg = self.cfg
         self.opt.zero_grad(set_to_none=True)
         train_bn = not cfg.freeze_bn
-        preds = self.model(img1, img2, train=train_bn, num_flow_updates=cfg.iters, autograd=True)
-        if cfg.loss == "unsup":
+        if cfg.loss == "unsup" and cfg.unsup_occlusion != "none":
+            loss, metrics = self._occlusion_loss(img1, img2, flow, valid)
+        elif cfg.loss == "unsup":
+            preds = self.model(img1, img2, train=train_bn, num_flow_updates=cfg.iters, autograd=True)
             loss, metrics = unsup_loss(preds, img1, img2, None, cfg.gamma, cfg.unsup_eps, cfg.unsup_eps_s,
                                        cfg.unsup_edge_kappa, cfg.unsup_smooth_weight, cfg.unsup_out_penalty,
                                        **({} if cfg.unsup_photo == "charbonnier" else {"photo": cfg.unsup_photo}))
@@ -311,6 +326,7 @@ class Trainer:
                     _, sup = sequence_loss(preds.detach(), flow, valid, cfg.gamma, cfg.max_flow)
                 metrics = {**metrics, **sup}
         else:
+            preds = self.model(img1, img2, train=train_bn, num_flow_updates=cfg.iters, autograd=True)
             loss, metrics = sequence_loss(preds, flow, valid, cfg.gamma, cfg.max_flow)
         if self.step + 1 == cfg.fault_nan_step:
             loss = loss * float("nan")
@@ -347,6 +363,34 @@ class Trainer:
         self.step += 1
         out = {"loss": loss.detach(), "grad_norm": gnorm.detach(), **{k: v.detach() for k, v in metrics.items()}}
         return out
+
+    def _occlusion_loss(self, img1, img2, flow, valid):
+        """The label-free loss with occlusion masks: both directions as one batch of 2B pairs (forward flows
+        in ``preds[:, :B]``, backward flows in ``preds[:, B:]``), the visibility masks of the final prediction
+        (detached; ``ops/native.py:visibility_masks``) applied to every iteration's photometric term.  Before
+        step ``unsup_occ_after`` there is no mask, but both directions run all the same, so that the batch
+        shape and the cached plans do not change mid-run."""
+        from ..ops import native as nat
+
+        cfg = self.cfg
+        B = img1.shape[0]
+        a, b = torch.cat([img1, img2]), torch.cat([img2, img1])
+        preds = self.model(a, b, train=not cfg.freeze_bn, num_flow_updates=cfg.iters, autograd=True)
+        mask = None
+        if self.step >= cfg.unsup_occ_after:
+            last = preds[-1].detach()
+            mask = nat.visibility_masks(last[:B].float().contiguous(), last[B:].float().contiguous(), cfg.unsup_occlusion,
+                                        cfg.unsup_occ_thr).view(2 * B, *last.shape[1:3])
+        loss, metrics = unsup_loss(preds, a, b, mask, cfg.gamma, cfg.unsup_eps, cfg.unsup_eps_s,
+                                   cfg.unsup_edge_kappa, cfg.unsup_smooth_weight, cfg.unsup_out_penalty,
+                                   **({} if cfg.unsup_photo == "charbonnier" else {"photo": cfg.unsup_photo}))
+        visible = torch.ones((), dtype=torch.float32, device=preds.device) if mask is None else mask.mean()
+        metrics = {**metrics, "visible": visible}
+        if self.labelled:          # metrics only, from the forward direction
+            with torch.no_grad():
+                _, sup = sequence_loss(preds[:, :B].detach(), flow, valid, cfg.gamma, cfg.max_flow)
+            metrics = {**metrics, **sup}
+        return loss, metrics
 
     def _comm(self):
         """The fused native backward's flat-arena all-reduce, registered for

@@ -20,7 +20,14 @@ its three launches, (b) ``unsup_loss(..., photo="census")`` against the golden o
 ``photo="census"``, (c) the training step with ``unsup_photo="census"`` against
 ``unsup_photo="charbonnier"``; the default output is then ``profiles/census_loss_overhead.txt``.
 
-  python tools/unsup_bench.py [--photo census] [--out profiles/unsup_loss_overhead.txt]
+``--occlusion fb | range`` measures the occlusion masks of the training step instead (train/occlusion.py,
+csrc/kernels/occlusion.hip; default output ``profiles/occlusion_overhead.txt``): (a) the two launches
+``range_splat`` and ``range_visible`` (+ the clear) at 12 maps of 368 x 496 per direction, with the bytes
+they move and the atomics they issue; (c) the training step in three arms, blocks alternated in one
+process: ``unsup_occlusion="none"`` at batch 6 (the step as it was), ``"none"`` at batch 12 (what the second
+direction costs: as many images through the model) and the chosen kind at batch 6 (12 images + the masks).
+
+  python tools/unsup_bench.py [--photo census | --occlusion range] [--out profiles/unsup_loss_overhead.txt]
 """
 import argparse
 import os
@@ -147,8 +154,107 @@ def training(args, dev):
     return rate, {k: tr.skipped for k, tr in arms.items()}
 
 
+def occlusion_launches(dev, reps, Bm=12):
+    """The range-map launches at (Bm, H, W) per direction, flows around SyntheticFlow's ground truth."""
+    _, _, flow, _ = SyntheticFlow((H, W), seed=0, device=dev).batch(list(range(Bm)))
+    g = torch.Generator(device=dev).manual_seed(0)
+    fw = (flow + 0.3 * torch.randn(Bm, H, W, 2, generator=g, device=dev)).contiguous()
+    bw = (-flow + 0.3 * torch.randn(Bm, H, W, 2, generator=g, device=dev)).contiguous()
+    acc = torch.zeros(2, Bm, H, W, dtype=torch.int32, device=dev)
+    vis = torch.empty(2, Bm, H, W, device=dev)
+    mb = lambda *ts: sum(t.numel() * t.element_size() for t in ts) / 1e6
+    # the atomics the splat issues: the taps inside the map with a weight that is not zero
+    taps = 0
+    for f in (fw, bw):
+        px = torch.arange(W, device=dev, dtype=torch.float32).view(1, 1, W) + f[..., 0]
+        py = torch.arange(H, device=dev, dtype=torch.float32).view(1, H, 1) + f[..., 1]
+        ok = (px > -1) & (px < W) & (py > -1) & (py < H)
+        x0, y0 = torch.floor(px), torch.floor(py)
+        qx, qy = torch.round((px - x0) * 16), torch.round((py - y0) * 16)
+        for dy in (0, 1):
+            for dx in (0, 1):
+                w = (qx if dx else 16 - qx) * (qy if dy else 16 - qy)
+                taps += int((ok & (w != 0) & (x0 + dx >= 0) & (x0 + dx < W) & (y0 + dy >= 0) & (y0 + dy < H)).sum())
+
+    def splat():
+        acc.zero_()
+        nat.ops().range_splat([fw, bw, acc], [Bm, H, W])
+
+    out = [("clear + range_splat", events(splat, dev, reps), mb(fw, bw, acc, acc),
+            f"both flows read, acc cleared and added to; {taps} integer atomics, {taps / (2 * Bm * H * W):.2f} per source"),
+           ("clear", events(acc.zero_, dev, reps), mb(acc), "acc written"),
+           ("range_visible", events(lambda: nat.ops().range_visible([fw, bw, acc, vis], [Bm, H, W, 128]), dev, reps),
+            mb(fw, bw, acc, vis), "both flows and acc read, masks written")]
+    return Bm, out
+
+
+def occlusion_training(args, dev):
+    total = args.warmup + args.block * args.rounds
+    kw = dict(arch=args.arch, steps=total, iters=args.iters, size=(384, 512), log_every=10 ** 9, loss="unsup")
+    arms = {"none b6": Trainer(TrainConfig(batch=BATCH, **kw)),
+            "none b12": Trainer(TrainConfig(batch=2 * BATCH, **kw)),
+            f"{args.occlusion} b6": Trainer(TrainConfig(batch=BATCH, unsup_occlusion=args.occlusion, **kw))}
+    for name, tr in arms.items():
+        t0 = time.perf_counter()
+        for _ in range(args.warmup):
+            tr.train_step(tr.batch_for(tr.step))
+        tr.flush()
+        torch.cuda.synchronize(dev)
+        print(f"warm-up of {name}: {time.perf_counter() - t0:.1f} s", flush=True)
+    step_ms = {k: [] for k in arms}
+    visible = []
+    for _ in range(args.rounds):
+        for name, tr in arms.items():
+            t0 = time.perf_counter()
+            for _ in range(args.block):
+                m = tr.train_step(tr.batch_for(tr.step))
+            tr.flush()
+            torch.cuda.synchronize(dev)
+            step_ms[name].append(1000 * (time.perf_counter() - t0) / args.block)
+            assert torch.isfinite(m["loss"]).item(), name
+            if "visible" in m:
+                visible.append(float(m["visible"]))
+    return step_ms, {k: tr.skipped for k, tr in arms.items()}, visible
+
+
+def occlusion_main(args, dev):
+    mean = lambda v: sum(v) / len(v)
+    lines = [f"occlusion masks of the label-free training step (kind {args.occlusion!r}), {torch.cuda.get_device_name(dev)}", ""]
+    Bm, rows = occlusion_launches(dev, args.reps)
+    lines += [f"(a) GPU time per launch, device events over {args.reps} repetitions, {Bm} maps of {H} x {W} per direction "
+              f"(flows (B, H, W) = ({Bm}, {H}, {W}) x 2 directions):"]
+    for name, us, mbytes, what in rows:
+        lines.append(f"    {name:20s} {us:8.1f} us   {mbytes:6.1f} MB at least ({what})  -> {mbytes / us * 1e3:6.0f} GB/s of them")
+    lines += ["    (the splat uses global integer atomics; the block-local LDS image of the target tile was not built, so there is no A/B of it)",
+              "    (kind 'fb' runs the existing fb_check kernel and elementwise torch ops instead of these two launches)", ""]
+    print("\n".join(lines), flush=True)
+    if not args.skip_training:
+        step_ms, skipped, visible = occlusion_training(args, dev)
+        a, b, c = list(step_ms)
+        lines += [f"(c) training step, {args.arch}, 384x512, {args.iters} iterations, SyntheticFlow, loss='unsup'; {args.block} steps per block, "
+                  f"blocks alternated {a} / {b} / {c} x {args.rounds} in one process after {args.warmup} warm-up steps each"]
+        for k, v in step_ms.items():
+            lines.append(f"    {k:9s} {mean(v):7.2f} ms/step  [per block: " + ", ".join(f"{x:.2f}" for x in v)
+                         + f"]  spread {max(v) - min(v):.2f} ms   skipped steps: {skipped[k]}")
+        lines += [f"    {a} is the step as it was (the parent commit's step: unsup_occlusion='none' changes nothing in it)",
+                  f"    second direction ({b} - {a}): {mean(step_ms[b]) - mean(step_ms[a]):+.2f} ms/step "
+                  f"({mean(step_ms[b]) / mean(step_ms[a]):.2f} x)",
+                  f"    masks ({c} - {b}): {mean(step_ms[c]) - mean(step_ms[b]):+.2f} ms/step; largest spread between blocks of one arm "
+                  f"{max(max(v) - min(v) for v in step_ms.values()):.2f} ms",
+                  f"    share of visible pixels in the masked arm, last step of each block: " + ", ".join(f"{v:.3f}" for v in visible),
+                  "    (all arms also run the sequence loss's forward kernel for the EPE metrics of the labelled synthetic set)", ""]
+    lines += ["No accuracy figure follows from this: the weights are random and there is no dataset here, so whether the masks "
+              "help is not measured.", ""]
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--occlusion", default=None, choices=("fb", "range"), help="measure the occlusion masks instead of the loss")
     ap.add_argument("--photo", default="charbonnier", choices=("charbonnier", "census"))
     ap.add_argument("--out", default=None, help="default: profiles/unsup_loss_overhead.txt, census_loss_overhead.txt with --photo census")
     ap.add_argument("--reps", type=int, default=500)
@@ -161,6 +267,10 @@ def main():
     ap.add_argument("--skip-training", action="store_true", help="(a) and (b) only")
     args = ap.parse_args()
     census = args.photo == "census"
+    if args.occlusion:
+        assert torch.cuda.is_available(), "unsup_bench measures on the GPU"
+        args.out = args.out or "profiles/occlusion_overhead.txt"
+        return occlusion_main(args, torch.device("cuda", 0))
     args.out = args.out or ("profiles/census_loss_overhead.txt" if census else "profiles/unsup_loss_overhead.txt")
     assert torch.cuda.is_available(), "unsup_bench measures on the GPU"
     dev = torch.device("cuda", 0)
