@@ -57,13 +57,10 @@ from ..models.layers import (
 )
 from .. import knobs
 from ..ops import native as nat
-from . import tunedb
+from . import lowering, tunedb
 from ..ops.native import (
     ACT_NONE,
     ACT_RELU,
-    ACT_SPLIT_TANH_RELU,
-    EPI_GRU_A,
-    EPI_GRU_B,
     EPI_STD,
     EPI_TAPS,
     ConvSpec,
@@ -124,17 +121,10 @@ def _fold_bn(cna: ConvNormActivation) -> Tuple[torch.Tensor, torch.Tensor]:
 
 
 @dataclass
-class _Shape:
-    B: int
-    H: int
-    W: int
-    N: int
-
-
-@dataclass
 class _PlanState:
     plan: object                      # plans[0]
     plans: List[object] = field(default_factory=list)   # one native Plan (one hipGraph) per batch part
+    choices: List[object] = field(default_factory=list)   # ... and its lowering.PartChoices
     bufs: Dict[str, torch.Tensor] = field(default_factory=dict)
     inp1: Optional[torch.Tensor] = None
     inp2: Optional[torch.Tensor] = None
@@ -244,9 +234,10 @@ class RaftEngine:
             (the reference's own precision end to end on the f32 MFMA:
             :class:`~jax_raft_amd.runtime.engine_f32.RaftEngineF32`).
 
-    Schedules (chosen per plan, see :meth:`_build_part`): the lane schedule
-    above; one in-order lane with every iteration upsampled (batch < 4,
-    raft_small); and the final-only serving mode.  In all of them the flow
+    Schedules (chosen per plan part, ``runtime/lowering.py``: ``PartChoices.schedule`` and the
+    ``PartRecorder.schedule_*`` methods): "lanes", the lane schedule above; "one_lane", one
+    in-order lane with every iteration upsampled (batch < 4, raft_small); the final-only serving
+    mode, "final_merged" below batch 4 and "final"; and "cp" (``cp_group``).  In all of them the flow
     update of iteration i runs inside iteration i+1's lookup kernel and the
     FlowHead's second conv is an MFMA epilogue of its first (raft_large) or a
     skinny taps GEMM (raft_small).  Variants measured and removed in round 3
@@ -310,14 +301,14 @@ class RaftEngine:
         self._init_cp(cp_group)
         assert streams in (True, False, "auto"), streams
         self.streams_mode = streams
-        self.streams = bool(streams)
         # instance norms of the encoders fused into halo 3x3 convs (statistics partials in the
         # producer's epilogue, normalise + relu in the consumer's footprint load; a residual
         # block's output built -- residual + its norm -- inside the next block's first halo conv;
         # profiles/r4_in_fusion_ab.txt); HALO_NORM = False: the separate statistics / norm_act passes
         self.halo_norm = bool(self.HALO_NORM)
         self.halo_res = self.halo_norm
-        self.mask_head = "split"      # per plan: "split" (mask lane) | "fused" (one lane, 128 -> 512 conv)
+        # of the most recently built plan (set by runtime/lowering.py:_finish; a plan's own: st.choices)
+        self.gru_path = self.corr_blocked = None
         self.gate_dtype = gate_dtype
         self.split = split
         self.cfg_override = dict(cfg_override or {})
@@ -400,13 +391,13 @@ class RaftEngine:
         assert H % 8 == 0 and W % 8 == 0, "input image H and W should be divisible by 8"
         return (B, H, W, n_iters, bool(all_iters))
 
-    def _build_key(self, key: tuple) -> _PlanState:
+    def _build_key(self, key: tuple, *, parts: Optional[int] = None, slot: bool = False) -> _PlanState:
         """Key layout: (B, H, W, n, all)[ + ("u8", H0, W0, pt, pl)][ + ("warm",) | ("bidir",) | ("bidir", "warp")]
-        [ + ("pslot", slot)]."""
+        [ + ("pslot", slot)].  ``parts`` / ``slot``: see :meth:`_build` (a bidirectional plan is one part)."""
         src = tuple(key[6:10]) if len(key) >= 10 and key[5] == "u8" else None
         if "bidir" in key[5:]:
-            return self._build_bidir(*key[:5], src, warp="warp" in key[5:])
-        return self._build(*key[:5], src=src, warm="warm" in key[5:])
+            return self._build_bidir(*key[:5], src, warp="warp" in key[5:], slot=slot)
+        return self._build(*key[:5], src=src, warm="warm" in key[5:], parts=parts, slot=slot)
 
     @staticmethod
     def _crop(st: _PlanState, out: torch.Tensor) -> torch.Tensor:
@@ -1134,9 +1125,13 @@ class RaftEngine:
             return False
         return self.GRU_ME == "on" or nat.gru_fused_tiles(B, h, w, 0) >= 3 * nat.NUM_CUS // 4
 
-    def uses_lanes(self, B: int, all_iters: bool = True) -> bool:
-        """Whether the plan for batch ``B`` runs the model's branches on several
-        lanes (``streams`` / its "auto" rule).  Graph-pipelined steps
+    def _parts(self, B: int) -> int:
+        """Independent part-forwards of a batch-``B`` plan: ``split`` where it divides the batch."""
+        return self.split if (self.split > 1 and B % self.split == 0 and not self.cp) else 1
+
+    def uses_lanes(self, B: int, all_iters: bool = True, *, parts: Optional[int] = None) -> bool:
+        """Whether the plan for batch ``B`` (in ``parts`` parts; default: :meth:`_parts`) runs the
+        model's branches on several lanes (``streams`` / its "auto" rule).  Graph-pipelined steps
         (:meth:`pipelined`) measured faster only on one-lane plans: batch 1
         145 -> 157 pairs/s, raft_small batch 4 559 -> 602, final-only 326 -> 346;
         with lanes (raft_large batch 4) 319 -> 289 (profiles/r2_pipelined_graph_ab.txt)."""
@@ -1144,604 +1139,18 @@ class RaftEngine:
             return False
         if self.streams_mode != "auto":
             return bool(self.streams_mode)
-        nb = B // self.split if (self.split > 1 and B % self.split == 0) else B
-        return nb >= self.AUTO_STREAMS_MIN_BATCH
+        return B // (self._parts(B) if parts is None else parts) >= self.AUTO_STREAMS_MIN_BATCH
 
     def _build(self, B: int, H: int, W: int, n_iters: int, all_iters: bool = True,
-               src: Optional[Tuple[int, int, int, int]] = None, warm: bool = False) -> _PlanState:
-        if warm and self.cp:
-            raise NotImplementedError("warm start (flow_init) is not lowered under context parallelism")
-        parts = self.split if (self.split > 1 and B % self.split == 0 and not self.cp) else 1
-        nb = B // parts
-        st, lanes = self._new_state(B, H, W, n_iters, all_iters, src, self.uses_lanes(B, all_iters), parts, B)
-        if warm:
-            st.flow_init = torch.zeros((B, H // 8, W // 8, 2), dtype=F32, device=self.device)
-        for part, plan in enumerate(st.plans):
-            self._build_part(st, plan, part * nb, nb, H, W, n_iters, f"p{part}.", lanes, 0, all_iters, warm)
-            plan.set_lane(0)
-            plan.set_segment(2)
-        return st
-
-    def _new_state(self, B: int, H: int, W: int, n_iters: int, all_iters: bool,
-                   src: Optional[Tuple[int, int, int, int]], on: bool, parts: int, out_batch: int):
-        """What every plan of this engine starts from, cold, warm or bidirectional: the size guard
-        of the correlation pyramid, the lane decision ``on`` taken over, ``parts`` empty native
-        plans, the input buffers of ``B`` image pairs and the output of ``out_batch`` flows per
-        iteration with its slot.  Returns ``(state, (main, side, side2) lanes)``."""
-        self.streams = on
-        self.mask_head = "split" if on else "fused"
-        h, w = H // 8, W // 8
-        min_sz = 2 * (2 ** (self.num_levels - 1))
-        assert h >= min_sz and w >= min_sz, (
-            f"Feature maps are too small to be down-sampled by the correlation pyramid: need >= {min_sz}, got {(h, w)}; "
-            f"input images should be at least {8 * min_sz}.")
-        dev = self.device
-        # Each part is an independent forward with its own Plan; with use_graph
-        # their captures are copied into ONE hipGraph (Plan.merge_*), so the
-        # parts' kernels fill each other's idle CUs.
-        plans = [nat.new_plan() for _ in range(parts)]
-        st = _PlanState(plan=plans[0], plans=plans, n_iters=n_iters, src=src)
-        if src is not None:   # raw frames: the prep kernel normalises + pads them (K14)
-            st.inp1 = torch.zeros((B, src[0], src[1], 3), dtype=torch.uint8, device=dev)
-            st.inp2 = torch.zeros((B, src[0], src[1], 3), dtype=torch.uint8, device=dev)
-        else:
-            st.inp1 = torch.zeros((B, H, W, 3), dtype=F32, device=dev)
-            st.inp2 = torch.zeros((B, H, W, 3), dtype=F32, device=dev)
-        st.out = torch.zeros((n_iters if all_iters else 1, out_batch, H, W, 2), dtype=F32, device=dev)
-        st.slot_ptr = st.out.data_ptr()
-        st.out_slot = torch.tensor([st.slot_ptr], dtype=torch.int64, device=dev)
-        return st, ((0, 1, 2) if on else (0, 0, 0))
+               src: Optional[Tuple[int, int, int, int]] = None, warm: bool = False, *,
+               parts: Optional[int] = None, slot: bool = False) -> _PlanState:
+        """The cold / warm plan (lowering.build) in ``parts`` parts (default :meth:`_parts`); ``slot``: a pipelined slot's."""
+        return lowering.build(self, B, H, W, n_iters, all_iters, src, warm, parts=parts, slot=slot)
 
     def _build_bidir(self, B: int, H: int, W: int, n_iters: int, all_iters: bool,
-                     src: Optional[Tuple[int, int, int, int]], warp: bool = False) -> _PlanState:
-        """The plan of ``forward(bidirectional=True)``: one part whose loop runs both directions at
-        batch 2B (:meth:`_build_part` with ``bidir``), so the lane decision, the ConvGRU lowering
-        and every tile choice are those of loop batch 2B; ``out`` is (N, 2B, H, W, 2) with 1 -> 2
-        in ``[:, :B]`` and 2 -> 1 in ``[:, B:]``.  The epilogue ends with the forward-backward
-        check (fbcheck.hip) of the final iteration's two flows, on lane 0 after the last
-        upsampling; it reads them through the output slot, where that replay wrote them.
-
-        ``warp`` (uint8 frames): the same recording followed, on lane 0 after the check, by the
-        ``memset`` of the photometric sums and one ``warp_frames`` over both directions
-        (framewarp.hip): it samples the frames as uploaded (``inp1`` / ``inp2``) with the same
-        two flows, masked by ``occ``, into the plan's ``warped`` and ``photo``."""
-        if self.cp:
-            raise NotImplementedError("bidirectional flow is not lowered under context parallelism")
-        assert not warp or src is not None, "warp: uint8 frames only"
-        saved, self.split = self.split, 1   # one part (``split`` lays ``out`` by part)
-        try:
-            on = self.uses_lanes(2 * B, all_iters)
-        finally:
-            self.split = saved
-        st, lanes = self._new_state(B, H, W, n_iters, all_iters, src, on, 1, 2 * B)
-        plan = st.plan
-        st.occ = torch.zeros((2, B, H, W), dtype=torch.uint8, device=self.device)
-        st.thr = torch.zeros(2, dtype=F32, device=self.device)
-        self._build_part(st, plan, 0, B, H, W, n_iters, "p0.", lanes, 0, all_iters, bidir=True)
-        plan.set_lane(0)
-        plan.set_segment(2)
-        # the final iteration's flows: the last slice of ``out``, its two batch halves
-        last = st.out[-1]
-        window = [H, W, 0, 0] if src is None else list(src)
-        if st.slot_ok:
-            off = (last.data_ptr() - st.out.data_ptr()) // 4
-            plan.add_fb_check([None, None, st.occ, None, st.thr, st.out_slot],
-                              [B, H, W] + window + [off, off + B * H * W * 2])
-        else:   # a generic mask head writes the captured buffer itself
-            plan.add_fb_check([last[:B], last[B:], st.occ, None, st.thr], [B, H, W] + window)
-        if warp:
-            st.warped = torch.zeros((2, B, src[0], src[1], 3), dtype=torch.uint8, device=self.device)
-            st.photo = torch.zeros((2, B, 2), dtype=torch.int64, device=self.device)
-            plan.add_memset([st.photo])
-            frames = [st.inp2, st.inp1, st.inp1, st.inp2]   # src (fw, bw), own (fw, bw)
-            if st.slot_ok:
-                plan.add_warp_frames(frames + [None, None, st.occ, st.warped, st.photo, st.out_slot],
-                                     [B, H, W] + window + [2, off, off + B * H * W * 2])
-            else:
-                plan.add_warp_frames(frames + [last[:B], last[B:], st.occ, st.warped, st.photo], [B, H, W] + window + [2])
-        return st
-
-    def _build_part(self, st: _PlanState, plan, b0: int, B: int, H: int, W: int, n_iters: int, pt: str,
-                    lanes: Tuple[int, int, int], ev0: int, all_iters: bool = True, warm: bool = False,
-                    bidir: bool = False):
-        """Lower one forward over images [b0, b0 + B) onto ``plan`` using lanes
-        (main, side, side2) and events ev0 .. ev0 + 8.  ``warm``: the loop starts from the
-        plan's ``flow_init`` slice instead of zero flow (``init_flow`` in place of
-        ``init_coords``; everything else, and every cold plan, is unchanged).
-
-        ``bidir``: both directions in one loop of batch 2B -- samples [0, B) refine the flow
-        1 -> 2, samples [B, 2B) the flow 2 -> 1.  ``prep`` and the feature encoder are the cold
-        plan's (``fmap`` already holds both frames' features); the context encoder, the GRU
-        context biases and ``init_coords`` run over all 2B images of ``x0``, a second ``corr``
-        launch with the ``fmap`` halves swapped fills the second half of every pyramid level,
-        and everything from the loop body on runs at the loop batch 2B.
-
-        Three loop schedules (``model.py:495-510`` per iteration):
-
-        * lanes (``main != side``): the critical lane runs lookup (+ the
-          previous iteration's flow update) -> convcorr1/2 -> motion conv ->
-          2 x ConvGRU -> FlowHead conv1 with the taps epilogue; the mask lane,
-          forked after the lookup, runs the flow-feature convs of this
-          iteration and the mask head + convex upsampling of the previous one
-          (deferred ops, skipped in iteration 0).  Three cross-lane edges per
-          iteration (E_FH, E_FLOW, E_MASK): each costs ~6-12 us in a captured
-          graph on this ROCm.
-        * one lane, every iteration upsampled: the same deferral in order:
-          lookup (+ update), flow features, upsampling of iteration i-1,
-          correlation / motion / GRU convs, FlowHead conv1 (fused with the mask
-          predictor's 3x3 conv as one 128 -> 512 GEMM when there is a mask
-          head) + the taps GEMM.
-        * final-only (``all_iters=False``, serving): the loop runs the flow head
-          alone; the mask head + x8 upsampling run once in the epilogue on the
-          final hidden state and flow."""
-        m = self.model
-        dev = self.device
-        bufs = st.bufs
-        sp = self._specs
-        h, w = H // 8, W // 8
-        Bi = B                 # image pairs: prep, the feature encoder, each correlation launch
-        if bidir:
-            assert b0 == 0 and not warm and not self.cp, "bidirectional plans: one part, cold, no context parallelism"
-            B = 2 * B          # the loop batch: context encoder, pyramid rows, loop body, upsampling
-        M = B * h * w
-        L = self.num_levels
-
-        def alloc(name, shape, dtype=BF16):
-            t = torch.zeros(shape, dtype=dtype, device=dev)
-            bufs[pt + name] = t
-            return t
-
-        inp1 = st.inp1[b0:b0 + Bi]
-        inp2 = st.inp2[b0:b0 + Bi]
-        out = st.out[:, b0:b0 + B]
-        out_off = (out.data_ptr() - st.out.data_ptr()) // 4   # in floats, from the slot's base
-
-        # ---------------- prologue: encoders + correlation pyramid
-        # lanes: 0 = feature encoder (image 1) + correlation pyramid, 1 = context
-        # encoder, 2 = feature encoder (image 2)
-        E_PREP, E_CTX, E_FLOW, E_FH, E_MASK, E_FE2 = range(ev0, ev0 + 6)
-        main, side, side2 = lanes
-        lanes_on = main != side
-        # the prologue's branches (context encoder, feature encoder per image) run on their own
-        # lanes even when the loop runs on one, up to Sintel-size batch 4 worth of pixels.  At
-        # batch 1 ("auto") the feature encoder runs as ONE batch-2 chain next to the context
-        # encoder's lane (round 6, profiles/r6_prolanes_ab.txt, r6_ce_lane_b1_ab.txt): per-image
-        # lanes of its ~70 short kernels only added dispatch cost (the replayed branches ran one
-        # after another, r6_graph_branches.txt); raft_small sync 297 -> 330-344 pairs/s, its
-        # 12-iteration stream 662-758 -> 782-805, raft_large sync 216 -> 218-223.  (1088x1920
-        # frames: 67.6 -> 63.7 with lanes, round 4, so off there.)
-        # PRO_LANES = "off": never, "on": always (per-image feature-encoder lanes at batch 1 too).
-        pl = self.PRO_LANES
-        assert pl in ("auto", "on", "off"), pl
-        pro_on = pl == "on" or (pl == "auto" and Bi * h * w <= 4 * 55 * 128)
-        p_main, p_side, p_side2 = lanes if lanes_on or self.cp or not pro_on else (main, 1, 2)
-        p_on = p_main != p_side
-        # the per-image feature-encoder split (lane 2) -- never at batch 1 under "auto", also not in
-        # a pipelined slot's multi-lane plan, so that its kernels (tile configs of the batch-2
-        # chain) and results equal the synchronous forward's bit for bit
-        fe_split = p_on and not (pl == "auto" and Bi == 1)
-
-        def lane(l):
-            plan.set_lane(l)
-
-        plan.set_segment(0)
-        lane(p_main)
-        hx = alloc("hx", (M, self.hx_cs))
-        qx = alloc("qx", (M, self.hx_cs))
-        h32 = alloc("h32", (M, self.hidden), F32)
-        zb = alloc("z", (M, self.hidden), self.gate_dtype)
-        # bf16 flow for the flow branch: compact 2 channels for the 2-channel conv
-        # kernel (4 taps = one 16-B load), 8-channel rows for the implicit GEMM
-        flow8 = alloc("flow8", (M, 2 if self._cf1_w is not None else 8))
-        coords = alloc("coords", (M, 2), F32)
-        flow32 = alloc("flow32", (M, 2), F32)
-        for t in (hx, qx, flow8, flow32):
-            plan.add_memset([t])
-        s2d = "fe.stem_s2d" in sp and "ce.stem_s2d" in sp and H % 2 == 0 and W % 2 == 0
-        x0 = alloc("x0", (2 * Bi, H // 2, W // 2, 16) if s2d else (2 * Bi, H, W, 8))
-        if st.src is not None:   # uint8 frames: normalise + replicate pad + layout in one kernel (K14)
-            H0, W0, pad_t, pad_l = st.src   # (pt is this part's buffer prefix)
-            plan.add_prep([inp1, inp2, x0, u8_table(dev)], [Bi, H, W, int(s2d), H0, W0, pad_t, pad_l])
-        elif s2d:   # 2x2 space-to-depth images for the 4x4 form of the 7x7 / stride-2 stems
-            plan.add_prep([inp1, inp2, x0], [Bi, H, W, 1])
-        else:
-            plan.add_prep([inp1, inp2, x0], [Bi, H, W])
-        plan.add_record(E_PREP)
-
-        lane(p_side)
-        plan.add_wait(E_PREP)
-        # the context of the loop's first frames: image 1 of every pair; bidirectional: both frames
-        ctx_in = x0 if bidir else x0[:Bi]
-        ctxf, ch_, cw_ = self._encoder(st, plan, "ce", m.context_encoder, ctx_in, B, H, W, bt=pt)
-        assert (ch_, cw_) == (h, w), "The context encoder should downsample H and W by 8"
-        # [tanh(h) | relu(context)] (model.py:582-584); h also as fp32 state
-        ce_out = alloc("ce_out", (M, round_up(self.hidden + self.ctx_ch, 8)))
-        self._conv(plan, sp["ce.conv"], ctxf, B, h, w, ce_out, act=ACT_SPLIT_TANH_RELU, split=self.hidden,
-                   h32=h32, hidden=self.hidden)
-        plan.add_copy_channels([ce_out, hx], [0, 0, M, self.hidden])
-        # loop-invariant context share of every GRU gate (+ gate biases)
-        gbias = []
-        for gi in range(len(m.update_block.recurrent_block.kernel_size)):
-            gb = alloc(f"gru{gi}.cbias", (M, self.gate_cs), self.gate_dtype)
-            self._conv(plan, sp[f"gru{gi}.ctx"], ce_out, B, h, w, gb, x_coff=self.hidden)
-            gbias.append(gb)
-        if warm:
-            # the seed sits where init_coords sits: on the context lane, which waited for E_PREP
-            # (recorded on the main lane after the memsets of hx / qx / flow8 / flow32 above, so
-            # the seed is not zeroed again) and records E_CTX, which the main lane waits for before
-            # the lane schedule's iteration-0 flow features and the first lookup.  It writes the
-            # state a flow update leaves (flowhead.hip:flow_taps_kernel), qx only where that does.
-            gp = self._gru_path(B, h, w)
-            seed_qx = gp != "halo" or len(m.update_block.recurrent_block.kernel_size) == 1
-            plan.add_init_flow([st.flow_init[b0:b0 + B], coords, flow32, hx, qx if seed_qx else None, flow8],
-                               [B, h, w, self.flow_off, self.flow_off])
-        else:
-            plan.add_init_coords([coords], [B, h, w])
-        plan.add_record(E_CTX)
-
-        fmap = alloc("fmap", (2 * Bi, h, w, self.fmap_ch))
-        if self.fe_external:
-            lane(p_main)   # fmap is written before each replay (RaftEngineMixed._pre_launch)
-        elif fe_split:
-            # the feature encoder of image2 on a third lane, concurrent with image1's
-            # (and the context encoder): per-image instance norms, so the halves are
-            # exact, and the sequential encoder chain that gates the correlation
-            # pyramid is half as long
-            lane(p_side2)
-            plan.add_wait(E_PREP)
-            featb, _, _ = self._encoder(st, plan, "fe", m.feature_encoder, x0[Bi:], Bi, H, W, bt=pt + "fe2.")
-            self._conv(plan, sp["fe.conv"], featb, Bi, h, w, fmap[Bi:])
-            plan.add_record(E_FE2)
-            lane(p_main)
-            feat, fh_, fw_ = self._encoder(st, plan, "fe", m.feature_encoder, x0[:Bi], Bi, H, W, bt=pt)
-            assert (fh_, fw_) == (h, w), "The feature encoder should downsample H and W by 8"
-            self._conv(plan, sp["fe.conv"], feat, Bi, h, w, fmap[:Bi])
-            plan.add_wait(E_FE2)
-        else:
-            lane(p_main)
-            feat, fh_, fw_ = self._encoder(st, plan, "fe", m.feature_encoder, x0, 2 * Bi, H, W, bt=pt)
-            assert (fh_, fw_) == (h, w), "The feature encoder should downsample H and W by 8"
-            self._conv(plan, sp["fe.conv"], feat, 2 * Bi, h, w, fmap)
-        # bf16 levels of /16-wide maps: levels 0 / 1 in the blocked layout (one
-        # pyramid tile per block: whole-line writes, 2 x 2 blocks per lookup window)
-        blocked = int(self.corr_dtype == BF16 and w % 16 == 0 and (h * w) % 8 == 0 and not self.cp)
-        self.corr_blocked = bool(blocked)
-        # context parallelism: this rank's pyramid holds the query rows [r0, r1) only
-        slabs = self._cp_slabs(h) if self.cp else [(0, h)]
-        r0, r1 = slabs[self.cp_rank]
-        nq = (r1 - r0) * w
-        on_demand = self.corr_mode == "on_demand"
-        assert not (on_demand and (bidir or self.cp)), "on-demand plans: one direction, no context parallelism"
-        levels = []
-        hl, wl = h, w
-        # on demand: no volume -- the pooled target features of levels 1 .. L-1 (fp32) instead
-        pooled = [alloc(f"fpool.l{l}", (Bi, h >> l, w >> l, self.fmap_ch), F32) for l in range(1, L)] if on_demand else []
-        for l in range(0 if on_demand else L):
-            shape = (M, -(-h // 8) * (8 >> l), -(-w // 16) * (16 >> l)) if blocked and l < 2 else (B * nq, hl, wl)
-            levels.append(alloc(f"corr.l{l}", shape, self.corr_dtype))
-            hl //= 2
-            wl //= 2
-        scale = 1.0 / float(self.fmap_ch) ** 0.5
-        if on_demand:
-            plan.add_feat_pool([fmap[Bi:]] + pooled, [Bi, h, w, self.fmap_ch, L])
-        elif self.cp:
-            for b in range(B):
-                plan.add_corr([fmap[b, r0:r1], fmap[B + b]] + [v[b * nq:(b + 1) * nq] for v in levels] + [None] * (4 - L),
-                              [1, h, w, self.fmap_ch, L, nq, 0], scale)
-        else:
-            # blocked 2: the persistent pyramid kernel (corr_pyr.hip) also at batch 1 -- not in a
-            # pipelined slot, whose graph runs it next to the previous pair's loop (there the
-            # short-lived tiles interleave better: b1 stream 227 vs 200-204 FPS, round 4)
-            bl = 2 if (blocked and self.CORR_PERSIST_B1 and not getattr(self, "_slot_build", False)) else blocked
-            plan.add_corr([fmap[:Bi], fmap[Bi:]] + levels + [None] * (4 - L), [Bi, h, w, self.fmap_ch, L, h * w, bl],
-                          scale)
-            if bidir:   # 2 -> 1: the halves swapped, into the second B*h*w query rows of every level
-                plan.add_corr([fmap[Bi:], fmap[:Bi]] + [v[Bi * h * w:] for v in levels] + [None] * (4 - L),
-                              [Bi, h, w, self.fmap_ch, L, h * w, bl], scale)
-        plan.add_wait(E_CTX)
-
-        # ---------------- loop body: one refinement iteration (model.py:495-510)
-        me = m.update_block.motion_encoder
-        cl, fl = me.corr_layers, me.flow_layers
-        corr = alloc("corr", (M, self.corr_cs))
-        cf = alloc("cf", (M, cl[-1] + fl[-1]))
-        f1 = alloc("f1", (M, fl[0]))
-        c1 = alloc("c1", (M, cl[0])) if len(cl) == 2 else None
-        taps = alloc("fh2.taps", (M, 24), F32)
-        stride = st.out.shape[1] * H * W * 2  # one iteration of the full-batch output
-        # mask predictor's 3x3 conv on its own (mask lane / context parallel), else fused into FlowHead conv1
-        split_mask = lanes_on or self.cp
-        # FlowHead conv1 of the loop: alone (lanes / final-only / no mask head) or
-        # fused with the mask predictor's 3x3 conv (one lane, every iteration upsampled)
-        s1 = sp["fh1"] if (self.has_mask and all_iters and not split_mask) else sp["fh1.flow"] if self.has_mask else sp["fh1"]
-        # the taps epilogue: the 256 FlowHead features never leave the CU
-        taps_epi = self._taps_epi_w is not None and s1.cout == 256
-        fm = None if taps_epi else alloc("fm", (M, round_up(s1.cout, 8)))
-        mfeat = (alloc("mfeat", (M, round_up(sp["mask.convrelu"].cout, 8)))
-                 if self.has_mask and (split_mask or not all_iters) else None)
-        mask = alloc("mask", (M, 576)) if self.has_mask and self._convex_w is None else None
-        # ConvGRU lowering: "halo" (gru_halo.hip, one launch per stage at any size / batch),
-        # "fused" (gru_fused.hip, whole-row tiles) or "unfused" (EPI_GRU_A / EPI_GRU_B convs)
-        gru_path = self._gru_path(B, h, w)
-        if gru_path == "fused" and self.cp:
-            gru_path = "unfused"
-        self.gru_path = gru_path
-        # the motion conv inside the first fused stage's kernel (gru_fused_me)
-        gru_me = gru_path == "fused" and self._gru_me_ok(B, h, w)
-        ngru = len(m.update_block.recurrent_block.kernel_size)
-        # the halo kernel cannot update h in place (neighbouring tiles read it): raft_large's
-        # stage 1 writes h' into qx, stage 2 reads it there and writes hx; raft_small's single
-        # stage ping-pongs h between hx (read on even iterations) and qx (odd), and its FlowHead
-        # reads the buffer the stage just wrote
-        halo_pp = gru_path == "halo" and ngru == 1
-        # qx's [motion | flow] part is read only by the unfused GRU-B and the ping-pong
-        qx_x = gru_path != "halo" or halo_pp
-        # with the mask lane, the mask head reads h from its own copy `hm` (written by the last
-        # stage), so the first stage can replace h in hx while the mask lane still runs
-        # raft_small's ping-pong stage with a mask head (an injected MaskPredictor) also writes the copy:
-        # its h' alternates between qx and hx, so the mask head (final-only epilogue, context parallel,
-        # mask lane) reads hm instead of a buffer that holds h' only on every other iteration
-        hm = (alloc("hm", (M, self.hidden))
-              if gru_path != "unfused" and self.has_mask and (lanes_on or halo_pp) else None)
-        # Parity-buffered mask-lane operands (gru_fused + convex head, MASK_PARITY = True): the last
-        # GRU stage writes h into hm / hm2 and the update writes the flow into flow32 / flow32b by
-        # iteration parity, so iteration i+1 never overwrites what the lane still reads for iteration
-        # i; the lane's next read of a buffer is ordered by the E_FLOW join of the iteration after,
-        # and the per-iteration E_MASK join (a ~10 us cross-stream graph edge) goes away.  Measured
-        # slower at batch 4 (359-365 vs 372 pairs/s, profiles/r4_mask_parity_ab.txt): unjoined, the
-        # mask head overlaps the ConvGRU stages (48 -> 54-56 us each) instead of the motion encoder.
-        parity = (hm is not None and gru_path == "fused" and self._convex_w is not None
-                  and self.MASK_PARITY)
-        hm2 = alloc("hm2", (M, self.hidden)) if parity else None
-        flow32b = alloc("flow32b", (M, 2), F32) if parity else None
-        st.flow_out.append((b0, B, flow32, flow32b))
-
-        # one-lane schedule: the flow conv + the previous iteration's upsampling as one grid (merged.hip)
-        c1k = me.convflow1.layers_0.kernel
-        merged_up = (self._cf1_w is not None and tuple(c1k.shape[:2]) == (7, 7) and not self.cp
-                     and (not self.has_mask or (self._convex_w is not None and fm is not None))
-                     and self.MERGED_UP)
-
-        def flow_features():
-            if self._cf1_w is not None:
-                c = me.convflow1.layers_0
-                kh, kw_, _, co = c.kernel.shape
-                plan.add_conv_direct([flow8, self._cf1_w, self._cf1_b, f1],
-                                     [B, h, w, 2, kh, kw_, c.padding[0], c.padding[1], co, 1, 0])
-            else:
-                self._conv(plan, sp["me.convflow1"], flow8, B, h, w, f1, act=ACT_RELU)
-            self._conv(plan, sp["me.convflow2"], f1, B, h, w, cf, y_coff=cl[-1], act=ACT_RELU)
-
-        def flow_head():
-            """FlowHead conv1 (+ conv2 as per-pixel tap partials into ``taps``)."""
-            if taps_epi:
-                self._conv(plan, s1, hx, B, h, w, taps, act=ACT_RELU, epi=EPI_TAPS, tapw=self._taps_epi_w)
-                return
-            if halo_pp:   # h' of even iterations is in qx, of odd ones in hx
-                self._conv(plan, s1, qx, B, h, w, fm, x_alt=hx, act=ACT_RELU)
-            else:
-                self._conv(plan, s1, hx, B, h, w, fm, act=ACT_RELU)
-            if self._taps_w is not None:   # skinny GEMM kernel (flowhead.hip), N = 18
-                plan.add_taps_gemm([fm, self._taps_w, taps], [M, self.fh_hidden, 0])
-            else:
-                self._conv(plan, sp["fh2.taps"], fm, B, h, w, taps)
-
-        def flow_update():
-            """``coords1 += delta`` (model.py:505) from the taps; flow into hx / qx / flow8."""
-            plan.add_flow_taps([taps, self._fh2_b, coords, flow32, hx, qx if qx_x else None, flow8]
-                               + ([flow32b] if parity else []), [B, h, w, self.flow_off, self.flow_off])
-
-        def upsample(stride, mask_from_fm: bool):
-            """x8 upsampling of flow32 into the output (model.py:508): convex with
-            the mask head (its 3x3 conv from hx, or the fused FlowHead conv1's
-            second half in ``fm``), else bilinear."""
-            if not self.has_mask:
-                plan.add_upsample_bilinear([flow32, out, st.out_slot], [B, h, w, stride, out_off])
-                return
-            if mask_from_fm:
-                feat_, coff = fm, self.fh_hidden
-            else:
-                self._conv(plan, sp["mask.convrelu"], hm if hm is not None else hx, B, h, w, mfeat, act=ACT_RELU,
-                           x_alt=hm2)
-                feat_, coff = mfeat, 0
-            if self._convex_w is not None:
-                plan.add_convex_head([feat_, self._convex_w, self._convex_b, flow32, out, st.out_slot]
-                                     + ([flow32b] if parity else []),
-                                     [B, h, w, coff, stride, 0, out_off], m.mask_predictor.multiplier)
-            else:   # generic mask head (an injected MaskPredictor): 1x1 conv + convex upsampling
-                st.slot_ok = False
-                self._conv(plan, sp["mask"], feat_, B, h, w, mask, x_coff=coff, alpha=m.mask_predictor.multiplier)
-                plan.add_upsample_convex([mask, flow32, out], [B, h, w, stride])
-
-        def lookup(with_update: bool):
-            upd = [taps, self._fh2_b, flow32, hx, qx if qx_x else None, flow8] if with_update else []
-            if with_update and parity:
-                upd.append(flow32b)   # t[12]: the odd iterations' flow
-            extra = [self.flow_off, self.flow_off] if with_update else []
-            if on_demand:
-                plan.add_lookup_od([coords, corr, fmap[:Bi], fmap[Bi:]] + pooled + [None] * (4 - L) + upd,
-                                   [L, B, h, w, self.radius, self.fmap_ch] + extra)
-                return
-            plan.add_lookup([coords, corr] + levels + [None] * (4 - L) + upd,
-                            [L, B, h, w, self.radius, h * w, blocked] + extra)
-
-        # the one-lane merged grid also runs convcorr1 (1x1, K 324 -> 352; merged.hip)
-        c1_merged = (merged_up and self.has_mask and len(cl) == 2 and self._cc1_w is not None
-                     and self._cc1_kpad == 352)
-
-        def motion_and_gru(wait_flow: bool, wait_mask: bool, flow2: bool = False):
-            """``flow2``: convflow2 (the flow branch's second conv) is added here, as one grid
-            with the last correlation conv when a grouped launch serves its tile config
-            (conv_grouped_kernel; CONV_GROUP = False keeps them separate launches)."""
-            if len(cl) == 2:
-                if flow2 and c1_merged:
-                    pass                      # ran in the flow conv's merged grid
-                elif self._cc1_w is not None:   # LDS-resident-weight 1x1 kernel (conv1x1.hip)
-                    plan.add_conv1x1([corr, self._cc1_w, self._cc1_b, c1],
-                                     [M, self.corr_cs, self._cc1_kpad, cl[0], ACT_RELU, 0])
-                else:
-                    self._conv(plan, sp["me.convcorr1"], corr, B, h, w, c1, act=ACT_RELU)
-                last = (sp["me.convcorr2"], c1, B, h, w, cf, dict(act=ACT_RELU))
-            else:
-                last = (sp["me.convcorr1"], corr, B, h, w, cf, dict(act=ACT_RELU))
-            fl2 = (sp["me.convflow2"], f1, B, h, w, cf, dict(y_coff=cl[-1], act=ACT_RELU))
-            if not (flow2 and self.CONV_GROUP and self._conv_group(plan, last, fl2)):
-                if flow2:
-                    self._conv(plan, *fl2[:6], **fl2[6])
-                self._conv(plan, *last[:6], **last[6])
-            if wait_flow:
-                plan.add_wait(E_FLOW)
-            if not gru_me:
-                self._conv(plan, sp["me.conv"], cf, B, h, w, hx, y_coff=self.mot_off, act=ACT_RELU,
-                           y2=qx if qx_x else None, y2_coff=self.mot_off)
-            if gru_path == "halo":
-                _, stages = self._halo_geom()
-                for gi, (mode, axis) in enumerate(stages):
-                    wa_, wb_ = self._halo_w[gi]
-                    last = gi == ngru - 1
-                    if halo_pp:
-                        t = [hx, hx, wa_, wb_, gbias[gi], h32, qx, hm, qx, qx, hx]
-                    else:
-                        t = [hx if gi == 0 else qx, hx, wa_, wb_, gbias[gi], h32, qx if gi == 0 else hx,
-                             hm if last else None]
-                    if wait_mask and last:
-                        plan.add_wait(E_MASK)  # the previous iteration's mask head has read hm (and flow32)
-                    base = [B, h, w, mode, axis]
-                    tile = self._halo_tile(gi, mode, axis, B, h, w, (t, base))
-                    plan.add_gru_halo(t, base + list(tile))
-                return
-            for gi in range(ngru):
-                if gru_path == "fused":
-                    last = gi == ngru - 1
-                    if wait_mask and not parity and (last if hm is not None else gi == 0):
-                        plan.add_wait(E_MASK)  # the previous iteration's mask head has read hm / h (and flow32)
-                    ks = m.update_block.recurrent_block.kernel_size[gi]
-                    if gi == 0 and gru_me:   # stage 1 computes its own motion features (nothing reads qx's copy)
-                        mc = sp["me.conv"]
-                        plan.add_gru_fused_me([hx, sp["gru0.a"].w, sp["gru0.b"].w, gbias[0], h32, hx,
-                                               hm if last else None, None, cf, mc.w, mc.b], [B, h, w, mc.cout])
-                        continue
-                    plan.add_gru_fused([hx, sp[f"gru{gi}.a"].w, sp[f"gru{gi}.b"].w, gbias[gi], h32, hx,
-                                        hm if last else None] + ([None, hm2] if last and parity else []),
-                                       [B, h, w, int(ks[0] > 1)])
-                    continue
-                # r*h from the bf16 h of the conv's own input hx (no fp32 state read)
-                self._conv(plan, sp[f"gru{gi}.a"], hx, B, h, w, qx, zbuf=zb, hidden=self.hidden,
-                           epi=EPI_GRU_A, bmap=gbias[gi], bmap_coff=0)
-                if gi == 0 and wait_mask:
-                    plan.add_wait(E_MASK)  # the previous iteration's mask head has read h (and flow32)
-                self._conv(plan, sp[f"gru{gi}.b"], qx, B, h, w, hx, h32=h32, zbuf=zb, hidden=self.hidden,
-                           epi=EPI_GRU_B, bmap=gbias[gi], bmap_coff=2 * self.hidden)
-
-        if self.cp:
-            # segment 1: this rank's lookups; the engine all-gathers them into `corr`
-            # (_gather_corr); segment 3: the rest of the iteration, replicated
-            hw = h * w
-            local = alloc("corr.local", (B, max(b_ - a_ for a_, b_ in slabs) * w, self.corr_cs))
-            plan.set_segment(1)
-            for b in range(B):
-                plan.add_lookup([coords[b * hw + r0 * w:b * hw + r1 * w], local[b]]
-                                + [v[b * nq:(b + 1) * nq] for v in levels] + [None] * (4 - L),
-                                [L, 1, h, w, self.radius, nq, 0])
-            plan.set_segment(3)
-            flow_features()
-            motion_and_gru(wait_flow=False, wait_mask=False)
-            flow_head()
-            flow_update()
-            if all_iters:
-                upsample(stride, mask_from_fm=False)
-            plan.set_segment(2)
-            if not all_iters:
-                upsample(0, mask_from_fm=False)
-            st.cp = dict(slabs=slabs, local=local, corr=corr, w=w)
-        elif lanes_on:
-            # iteration 0's flow features (zero flow) run once in the prologue
-            plan.set_segment(0)
-            lane(main)
-            flow_features()
-            plan.set_segment(1)
-            lane(main)
-            lookup(with_update=True)      # + iteration i-1's flow update
-            plan.add_record(E_FH)
-            lane(side2)
-            plan.set_defer(1)             # skipped in iteration 0
-            plan.add_wait(E_FH)
-            flow_features()
-            plan.add_record(E_FLOW)
-            upsample(stride, mask_from_fm=False)   # iteration i-1 (h intact: GRU-B waits E_MASK)
-            plan.add_record(E_MASK)
-            plan.set_defer(0)
-            lane(main)
-            motion_and_gru(wait_flow=True, wait_mask=True)
-            flow_head()
-            plan.set_segment(2)           # epilogue: the last iteration's update, mask head and upsampling
-            lane(main)
-            flow_update()
-            plan.set_defer(1)
-            upsample(stride, mask_from_fm=False)
-            plan.set_defer(0)
-        elif all_iters:
-            plan.set_segment(1)
-            lane(main)
-            lookup(with_update=True)
-            if merged_up:
-                # the 7x7 flow conv and iteration i-1's x8 upsampling in ONE grid (merged.hip):
-                # both read the flow the lookup just updated, and at batch 1 neither fills the GPU
-                c = me.convflow1.layers_0
-                kh, kw_, _, co = c.kernel.shape
-                ints = [B, h, w, 2, kh, kw_, c.padding[0], c.padding[1], co, 1, 0]
-                if self.has_mask:
-                    t_ = [flow8, self._cf1_w, self._cf1_b, f1, flow32, out, st.out_slot, fm, self._convex_w,
-                          self._convex_b]
-                    i_ = ints + [2, stride, out_off, self.fh_hidden]
-                    if c1_merged:   # + convcorr1 (LDS-weight 1x1 kernel) in the same grid
-                        t_ += [corr, self._cc1_w, self._cc1_b, c1]
-                        i_ += [M, self.corr_cs, self._cc1_kpad, cl[0], ACT_RELU, 0]
-                    plan.add_flowin_dual(t_, i_, m.mask_predictor.multiplier)
-                else:
-                    plan.add_flowin_dual([flow8, self._cf1_w, self._cf1_b, f1, flow32, out, st.out_slot],
-                                         ints + [1, stride, out_off, 0], 1.0)
-            else:
-                flow_features()
-                plan.set_defer(1)
-                upsample(stride, mask_from_fm=fm is not None and self.has_mask)   # iteration i-1
-                plan.set_defer(0)
-            motion_and_gru(wait_flow=False, wait_mask=False, flow2=merged_up)
-            flow_head()
-            plan.set_segment(2)
-            flow_update()
-            plan.set_defer(1)
-            upsample(stride, mask_from_fm=fm is not None and self.has_mask)
-            plan.set_defer(0)
-        elif self._cf1_w is not None and tuple(c1k.shape[:2]) == (7, 7) and B < self.AUTO_STREAMS_MIN_BATCH:
-            # final-only below batch 4, the one-lane order of the all-iterations loop: the flow update
-            # fused into the next lookup, the 7x7 flow conv in the merged grid (its bilinear half
-            # writes the single output slot every iteration; the epilogue's upsampling overwrites
-            # it), convflow2 grouped with convcorr2.  Batch 1: 239.5 -> 244.6 pairs/s; batch 4
-            # loses (414.8 -> 402.7), keeps the order below (profiles/r4_host_gate.txt)
-            plan.set_segment(1)
-            lane(main)
-            lookup(with_update=True)
-            c = me.convflow1.layers_0
-            kh, kw_, _, co = c.kernel.shape
-            plan.add_flowin_dual([flow8, self._cf1_w, self._cf1_b, f1, flow32, out, st.out_slot],
-                                 [B, h, w, 2, kh, kw_, c.padding[0], c.padding[1], co, 1, 0, 1, 0, out_off, 0], 1.0)
-            motion_and_gru(wait_flow=False, wait_mask=False, flow2=True)
-            flow_head()
-            plan.set_segment(2)           # epilogue: the last update, then the final flow upsampled once
-            flow_update()
-            upsample(0, mask_from_fm=False)
-        else:
-            plan.set_segment(1)
-            lane(main)
-            flow_features()
-            lookup(with_update=False)
-            motion_and_gru(wait_flow=False, wait_mask=False)
-            flow_head()
-            flow_update()
-            plan.set_segment(2)           # epilogue: upsample the final flow once (out has one iteration)
-            upsample(0, mask_from_fm=False)
-        lane(main)
+                     src: Optional[Tuple[int, int, int, int]], warp: bool = False, *, slot: bool = False) -> _PlanState:
+        """Record the plan of ``forward(bidirectional=True)`` (runtime/lowering.py:build_bidir)."""
+        return lowering.build_bidir(self, B, H, W, n_iters, all_iters, src, warp, slot=slot)
 
     # --------------------------------------------------------------- forward
     @torch.no_grad()
@@ -1938,16 +1347,8 @@ class RaftEngine:
 
     # ------------------------------------- software-pipelined graphs (throughput)
     def _slot_state(self, key, slot: int) -> _PlanState:
-        def build():
-            saved, self.split = self.split, 1
-            self._slot_build = True
-            try:
-                return self._build_key(key)
-            finally:
-                self.split = saved
-                self._slot_build = False
-
-        return self._plan_state(key + ("pslot", slot), build)
+        """The plan of one :meth:`pipelined` slot: one part, recorded as a slot's plan."""
+        return self._plan_state(key + ("pslot", slot), lambda: self._build_key(key, parts=1, slot=True))
 
     @torch.no_grad()
     def pipelined(self, image1: torch.Tensor, image2: torch.Tensor, num_flow_updates: int = 12,

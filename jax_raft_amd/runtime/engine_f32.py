@@ -82,7 +82,7 @@ class RaftEngineF32(RaftEngine):
                 self._specs[name] = nat.make_spec_f32(k, b.to(self.device), stride, pad, cin4=cin4, device=self.device)
         self._snap = self._snapshot()
 
-    def uses_lanes(self, B: int, all_iters: bool = True) -> bool:
+    def uses_lanes(self, B: int, all_iters: bool = True, **_) -> bool:
         return False
 
     def _conv(self, plan, spec, x, N, H, W, y, **kw):
@@ -162,7 +162,7 @@ class RaftEngineF32(RaftEngine):
         return x, H, W
 
     def _build(self, B: int, H: int, W: int, n_iters: int, all_iters: bool = True, src=None,
-               warm: bool = False) -> _PlanState:
+               warm: bool = False, **_) -> _PlanState:   # (parts / slot: one part, no slot-specific lowering)
         assert src is None, "fp32 engine: uint8 frames are prepared by RaftEngine._host_u8"
         if warm and self.cp:
             raise NotImplementedError("warm start (flow_init) is not lowered under context parallelism")
@@ -345,9 +345,9 @@ class RaftEngineMixed(RaftEngine):
         self._f32._hold_model_weakly()
 
     def _build(self, B: int, H: int, W: int, n_iters: int, all_iters: bool = True, src=None,
-               warm: bool = False) -> _PlanState:
+               warm: bool = False, **kw) -> _PlanState:
         assert src is None, "mixed engine: uint8 frames are prepared by RaftEngine._host_u8"
-        st = super()._build(B, H, W, n_iters, all_iters, src, warm)
+        st = super()._build(B, H, W, n_iters, all_iters, src, warm, **kw)
         f = self._f32
         if f._stale():
             f._pack()
