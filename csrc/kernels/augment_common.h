@@ -1,9 +1,9 @@
-// Device helpers shared by the dense, the sparse and the mixed augmentation gathers (augment.hip,
-// augment_sparse.hip, augment_mixed.hip): the record words the layouts have in common, the texel
-// transform, the bilinear blend, the source position of a resized coordinate, one output pixel of
-// both images, the flow of one output pixel from dense ground truth (the four-tap blend) and from
-// sparse ground truth (the scan for the winner), and the stores of a thread's run of 4 pixels.
-// Every file switches contraction off; the pragma below covers the functions defined here.
+// The per-pixel functions of the augmentation gather (augment.hip), the same for its three layouts:
+// the record words, the texel transform, the bilinear blend, the source position of a resized
+// coordinate, one output pixel of both images, the flow of one output pixel from dense ground truth
+// (the four-tap blend) and from sparse ground truth (the scan for the winner), and the stores of a
+// thread's run of 4 pixels.
+// augment.hip switches contraction off; the pragma below covers the functions defined here.
 #pragma once
 #include "common.h"
 
@@ -14,6 +14,8 @@ namespace augment_dev {
 // words 0..15 of a record's ints and 0..31 of its floats (train/augment.py), dense and sparse alike
 constexpr int I_HR = 0, I_WR = 1, I_Y0 = 2, I_X0 = 3, I_HFLIP = 4, I_VFLIP = 5, I_NRECT = 6, I_RECT = 8;
 constexpr int F_SX = 0, F_SY = 1, F_ISX = 2, F_ISY = 3, F_COL1 = 4, F_COL2 = 16;
+// words 16..18 of the ints of a sparse or mixed record: the sample's own size; 1 for dense ground truth (mixed)
+constexpr int I_HS = 16, I_WS = 17, I_DENSE = 18;
 
 struct Colour {
   float b, k, s, m[9], mean[3], cm;   // cm: the contrast pivot min(255, b * luma(mean))

@@ -329,36 +329,30 @@ int jr_warp_frames(const void* src0, const void* src1, const void* own0, const v
                    const float* flow1, const void* slot, long off0, long off1, const void* occ, void* warped,
                    long long* photo, int B, int H, int W, int H0, int W0, int top, int left, int dirs,
                    hipStream_t stream);
-// Training-data augmentation (augment.hip; train/augment.py:augment_pairs, bitwise).  img1 / img2 uint8
-// [B][Hs][Ws][3], flow fp32 [B][Hs][Ws][2], params int32 [B][48] (the sampler's records), sums int32
-// [2][B][3].  jr_augment_sums clears sums (a memset in the stream) and adds up every frame's channels
-// (Hs * Ws * 255.5 must fit an int32); jr_augment reads them and writes out1 / out2 fp32 [B][h][w][3] in
-// [-1, 1], out_flow fp32 [B][h][w][2] and valid fp32 [B][h][w], all 16-byte aligned.  Source taps are
-// clamped into the frame whatever a record says.
-int jr_augment_sums(const void* img1, const void* img2, int B, int Hs, int Ws, int* sums, hipStream_t stream);
-int jr_augment(const void* img1, const void* img2, const float* flow, const int* params, const int* sums,
-               float* out1, float* out2, float* out_flow, float* valid, int B, int Hs, int Ws, int h, int w,
-               hipStream_t stream);
-// The sparse-ground-truth augmentation (augment_sparse.hip; train/augment.py:augment_pairs_sparse,
-// bitwise).  Every sample sits in the top-left corner of a [Hb][Wb] buffer: img1 / img2 uint8
-// [B][Hb][Wb][3], flow fp32 [B][Hb][Wb][2], valid_in uint8 [B][Hb][Wb], params int32 [B][52] (the dense
-// record plus the sample's own size, which the kernels clamp into the buffer), sums int32 [2][B][3] over
-// each sample's own region.  Outputs as jr_augment's.  Nothing outside a sample's region is read.
-int jr_augment_sparse_sums(const void* img1, const void* img2, const int* params, int B, int Hb, int Wb, int* sums,
-                           hipStream_t stream);
-int jr_augment_sparse(const void* img1, const void* img2, const float* flow, const void* valid_in, const int* params,
-                      const int* sums, float* out1, float* out2, float* out_flow, float* valid, int B, int Hb, int Wb,
-                      int h, int w, hipStream_t stream);
-// Dense and sparse samples in one batch (augment_mixed.hip; train/augment.py:augment_pairs_mixed, bitwise).
-// Packed slots: img1 / img2 uint8 [B][S][3], flow fp32 [B][S][2], valid_in uint8 [B][S], sample n in the first
-// Hs * Ws pixels of slot n with row pitch Ws.  params int32 [B][52]: the sparse record, word 18 = 1 for a
-// dense sample (four-tap flow blend, valid_in not read) and 0 for a sparse one; the kernels clamp Hs * Ws
-// into the slot.  S * 255.5 must fit an int32.  sums and the outputs as jr_augment_sparse's.
-int jr_augment_mixed_sums(const void* img1, const void* img2, const int* params, int B, long S, int* sums,
-                          hipStream_t stream);
-int jr_augment_mixed(const void* img1, const void* img2, const float* flow, const void* valid_in, const int* params,
-                     const int* sums, float* out1, float* out2, float* out_flow, float* valid, int B, long S, int h, int w,
-                     hipStream_t stream);
+// Training-data augmentation (augment.hip; the golden ops of train/augment.py, bitwise).  One pair of launches
+// for three layouts of a batch; g0, g1 are the frame geometry, a frame being g0 * g1 pixels:
+//   JR_AUGMENT_DENSE   (g0, g1) = (Hs, Ws): img1 / img2 uint8 [B][Hs][Ws][3], flow fp32 [B][Hs][Ws][2], params
+//                      int32 [B][48] (the sampler's records); no valid_in (pass null), and the sums launch
+//                      takes no params (augment_pairs);
+//   JR_AUGMENT_SPARSE  (g0, g1) = (Hb, Wb): every sample in the top-left corner of a [Hb][Wb] buffer, valid_in
+//                      uint8 [B][Hb][Wb], params int32 [B][52] (the dense record plus the sample's own size,
+//                      which the kernels clamp into the buffer) (augment_pairs_sparse);
+//   JR_AUGMENT_MIXED   (g0, g1) = (1, S), any other g0 is refused: packed slots, img1 / img2 uint8 [B][S][3], flow
+//                      fp32 [B][S][2], valid_in uint8 [B][S], sample n in the first Hs * Ws pixels of slot n with
+//                      row pitch Ws; params int32 [B][52]: the sparse record, word 18 = 1 for a dense sample
+//                      (four-tap flow blend, valid_in not read) and 0 for a sparse one; the kernels clamp
+//                      Hs * Ws into the slot (augment_pairs_mixed).
+// jr_augment_sums clears sums, int32 [2][B][3] (a memset in the stream), and adds up the channels of every
+// sample's own pixels (g0 * g1 * 255.5 must fit an int32); jr_augment_gather reads them and writes out1 / out2
+// fp32 [B][h][w][3] in [-1, 1], out_flow fp32 [B][h][w][2] and valid fp32 [B][h][w], all 16-byte aligned.  Source
+// taps are clamped into the sample whatever a record says; nothing outside a sample's pixels is read.  An
+// unknown layout is hipErrorInvalidValue.
+enum { JR_AUGMENT_DENSE = 0, JR_AUGMENT_SPARSE = 1, JR_AUGMENT_MIXED = 2 };
+int jr_augment_sums(int layout, const void* img1, const void* img2, const int* params, int B, int g0, int g1, int* sums,
+                    hipStream_t stream);
+int jr_augment_gather(int layout, const void* img1, const void* img2, const float* flow, const void* valid_in,
+                      const int* params, const int* sums, float* out1, float* out2, float* out_flow, float* valid, int B,
+                      int g0, int g1, int h, int w, hipStream_t stream);
 // Flow validation metrics (metrics.hip; eval/metrics.py:flow_metrics: counts bitwise, fp64 sums up to
 // their order).  pred fp32 [B][Hp][Wp][2], gt fp32 [B][Hg][Wg][2], valid (optional) uint8 [B][Hg][Wg],
 // sizes int32 [B][2] = (Hs, Ws) on the device (clamped into both maps by the kernels): sample n is the

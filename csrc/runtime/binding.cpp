@@ -1941,7 +1941,21 @@ static Launch make_warp_frames(const TList& t, const IList& i, std::vector<at::T
 }
 
 // -------------------------------------------------------- training-data augmentation
-// (kernels augment.hip).  The frames as uploaded: img1 / img2 uint8 [B][Hs][Ws][3]; sums int32 [2][B][3].
+// (kernels augment.hip).  One row per layout of a batch (kernels.h: JR_AUGMENT_*); a builder per launch takes a row.
+struct AugmentLayout {
+  int id;
+  const char *sums_op, *op;   // the op names: every message begins with the one that was called
+  int64_t words;              // int32 words of a record
+  bool sums_records, valid;   // the sums op takes the records; a valid input exists
+  int geom;                   // geometry ints after B: 2 = (Hs, Ws) | (Hb, Wb); 1 = (S), packed slots being frames [B][1][S]
+  const char* dims;           // ... as the messages name them
+};
+static const AugmentLayout AUGMENT_LAYOUTS[3] = {
+    {JR_AUGMENT_DENSE, "augment_sums", "augment", 48, false, false, 2, "[B][Hs][Ws]"},
+    {JR_AUGMENT_SPARSE, "augment_sparse_sums", "augment_sparse", 52, true, true, 2, "[B][Hb][Wb]"},
+    {JR_AUGMENT_MIXED, "augment_mixed_sums", "augment_mixed", 52, true, true, 1, "[B][S]"},
+};
+// The frames as uploaded: img1 / img2 uint8 [B][Hs][Ws][3]; sums int32 [2][B][3].
 static void check_augment_frames(const at::Tensor& a, const at::Tensor& b, int64_t B, int64_t Hs, int64_t Ws, const char* op) {
   TORCH_CHECK(B >= 1 && B <= 32767 && Hs >= 1 && Ws >= 1 && Hs * Ws * 255 + Hs * Ws / 2 <= INT32_MAX, op,
               ": sizes (a frame's channel sum must fit an int32)");
@@ -1959,7 +1973,7 @@ static bool augment_overlap(const at::Tensor& a, const at::Tensor& b) {
 }
 // the four outputs of a gather: fp32 [B][h][w][3 | 3 | 2 | 1], 16-byte aligned, aliasing no input and no other output
 static void check_augment_outputs(const std::string& op, std::array<const at::Tensor*, 4> outs,
-                                  std::initializer_list<const at::Tensor*> ins, int64_t B, int64_t h, int64_t w) {
+                                  const std::vector<const at::Tensor*>& ins, int64_t B, int64_t h, int64_t w) {
   const int64_t ch[4] = {3, 3, 2, 1};
   const char* what[4] = {": image1 out", ": image2 out", ": flow out", ": valid out"};
   for (int k = 0; k < 4; ++k) {
@@ -1971,129 +1985,60 @@ static void check_augment_outputs(const std::string& op, std::array<const at::Te
     for (int j = 0; j < k; ++j) TORCH_CHECK(!augment_overlap(*outs[k], *outs[j]), name, " aliases another output");
   }
 }
-// t = [img1, img2, sums], i = [B, Hs, Ws]
-static Launch make_augment_sums(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
-  at::Tensor a = opt(t, 0), b = opt(t, 1), sums = opt(t, 2);
-  const int64_t B = i[0], Hs = i[1], Ws = i[2];
-  check_augment_frames(a, b, B, Hs, Ws, "augment_sums");
-  check_augment_sums(sums, B, "augment_sums");
-  TORCH_CHECK(!augment_overlap(sums, a) && !augment_overlap(sums, b), "augment_sums: sums aliases an image");
-  keep.push_back(a); keep.push_back(b); keep.push_back(sums);
-  const void *ap = a.data_ptr(), *bp = b.data_ptr();
-  int* sp = sums.data_ptr<int>();
-  return [=](hipStream_t s, int) { return jr_augment_sums(ap, bp, (int)B, (int)Hs, (int)Ws, sp, s); };
-}
-// t = [img1, img2, flow (fp32 [B][Hs][Ws][2]), params (int32 [B][48]), sums, out1, out2 (fp32 [B][h][w][3]),
-// out_flow (fp32 [B][h][w][2]), valid (fp32 [B][h][w])], i = [B, Hs, Ws, h, w]
-static Launch make_augment(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
-  at::Tensor a = opt(t, 0), b = opt(t, 1), flow = opt(t, 2), params = opt(t, 3), sums = opt(t, 4);
-  at::Tensor o1 = opt(t, 5), o2 = opt(t, 6), of = opt(t, 7), ov = opt(t, 8);
-  const int64_t B = i[0], Hs = i[1], Ws = i[2], h = i[3], w = i[4];
-  check_augment_frames(a, b, B, Hs, Ws, "augment");
-  check_augment_sums(sums, B, "augment");
-  TORCH_CHECK(h >= 1 && w >= 1 && h <= 65535 * 4 && h * w <= 0x3fffffff, "augment: crop size");
-  check_f32(flow, "augment: flow");
-  TORCH_CHECK(flow.numel() == B * Hs * Ws * 2 && reinterpret_cast<uintptr_t>(flow.data_ptr()) % 16 == 0,
-              "augment: flow [B][Hs][Ws][2], 16-byte aligned");
-  TORCH_CHECK(params.defined() && params.is_cuda() && params.scalar_type() == at::kInt && params.is_contiguous() &&
-                  params.numel() == 48 * B, "augment: params must be a contiguous device int32 [B][48]");
-  check_augment_outputs("augment", {&o1, &o2, &of, &ov}, {&a, &b, &flow, &params, &sums}, B, h, w);
-  for (auto& v : {a, b, flow, params, sums, o1, o2, of, ov}) keep.push_back(v);
-  const void *ap = a.data_ptr(), *bp = b.data_ptr();
-  const float* fp = flow.data_ptr<float>();
-  const int *pp = params.data_ptr<int>(), *sp = sums.data_ptr<int>();
-  float *p1 = o1.data_ptr<float>(), *p2 = o2.data_ptr<float>(), *pf = of.data_ptr<float>(), *pv = ov.data_ptr<float>();
-  return [=](hipStream_t s, int) {
-    return jr_augment(ap, bp, fp, pp, sp, p1, p2, pf, pv, (int)B, (int)Hs, (int)Ws, (int)h, (int)w, s);
-  };
-}
-
-// ---- sparse ground truth (kernels augment_sparse.hip): samples of several sizes in [Hb][Wb] buffers
-static void check_augment_records(const at::Tensor& params, int64_t B, int64_t words, const std::string& op) {
+static void check_augment_records(const at::Tensor& params, int64_t B, int64_t words, const char* op) {
   TORCH_CHECK(params.defined() && params.is_cuda() && params.scalar_type() == at::kInt && params.is_contiguous() &&
                   params.numel() == words * B, op, ": params must be a contiguous device int32 [B][", words, "]");
 }
-// t = [img1, img2, params (int32 [B][52]), sums], i = [B, Hb, Wb]
-static Launch make_augment_sparse_sums(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
-  at::Tensor a = opt(t, 0), b = opt(t, 1), params = opt(t, 2), sums = opt(t, 3);
-  const int64_t B = i[0], Hb = i[1], Wb = i[2];
-  check_augment_frames(a, b, B, Hb, Wb, "augment_sparse_sums");
-  check_augment_records(params, B, 52, "augment_sparse_sums");
-  check_augment_sums(sums, B, "augment_sparse_sums");
+// t = [img1, img2, params (int32 [B][words]; a layout whose sums op takes the records), sums], i = [B, geometry]
+static Launch make_augment_sums(const AugmentLayout& L, const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  at::Tensor a = opt(t, 0), b = opt(t, 1), params = L.sums_records ? opt(t, 2) : at::Tensor();
+  at::Tensor sums = opt(t, 2 + L.sums_records);
+  const int64_t B = i[0], g0 = L.geom == 2 ? i[1] : 1, g1 = i[L.geom];
+  check_augment_frames(a, b, B, g0, g1, L.sums_op);
+  if (L.sums_records) check_augment_records(params, B, L.words, L.sums_op);
+  check_augment_sums(sums, B, L.sums_op);
   for (const at::Tensor* in : {&a, &b, &params})
-    TORCH_CHECK(!augment_overlap(sums, *in), "augment_sparse_sums: sums aliases an input");
-  for (auto& v : {a, b, params, sums}) keep.push_back(v);
+    TORCH_CHECK(!in->defined() || !augment_overlap(sums, *in), L.sums_op, ": sums aliases an input");
+  for (auto& v : {a, b, params, sums})
+    if (v.defined()) keep.push_back(v);
   const void *ap = a.data_ptr(), *bp = b.data_ptr();
-  const int* pp = params.data_ptr<int>();
+  const int* pp = (const int*)ptr(params);
   int* sp = sums.data_ptr<int>();
-  return [=](hipStream_t s, int) { return jr_augment_sparse_sums(ap, bp, pp, (int)B, (int)Hb, (int)Wb, sp, s); };
+  const int layout = L.id;
+  return [=](hipStream_t s, int) { return jr_augment_sums(layout, ap, bp, pp, (int)B, (int)g0, (int)g1, sp, s); };
 }
-// t = [img1, img2, flow (fp32 [B][Hb][Wb][2]), valid (uint8 [B][Hb][Wb]), params (int32 [B][52]), sums, out1, out2
-// (fp32 [B][h][w][3]), out_flow (fp32 [B][h][w][2]), out_valid (fp32 [B][h][w])], i = [B, Hb, Wb, h, w]
-static Launch make_augment_sparse(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
-  at::Tensor a = opt(t, 0), b = opt(t, 1), flow = opt(t, 2), vin = opt(t, 3), params = opt(t, 4), sums = opt(t, 5);
-  at::Tensor o1 = opt(t, 6), o2 = opt(t, 7), of = opt(t, 8), ov = opt(t, 9);
-  const int64_t B = i[0], Hb = i[1], Wb = i[2], h = i[3], w = i[4];
-  check_augment_frames(a, b, B, Hb, Wb, "augment_sparse");
-  check_augment_sums(sums, B, "augment_sparse");
-  TORCH_CHECK(h >= 1 && w >= 1 && h <= 65535 * 4 && h * w <= 0x3fffffff, "augment_sparse: crop size");
-  check_f32(flow, "augment_sparse: flow");
-  TORCH_CHECK(flow.numel() == B * Hb * Wb * 2 && reinterpret_cast<uintptr_t>(flow.data_ptr()) % 16 == 0,
-              "augment_sparse: flow [B][Hb][Wb][2], 16-byte aligned");
-  TORCH_CHECK(vin.defined() && vin.is_cuda() && vin.scalar_type() == at::kByte && vin.is_contiguous() &&
-                  vin.numel() == B * Hb * Wb, "augment_sparse: valid must be a contiguous device uint8 [B][Hb][Wb]");
-  check_augment_records(params, B, 52, "augment_sparse");
-  check_augment_outputs("augment_sparse", {&o1, &o2, &of, &ov}, {&a, &b, &flow, &vin, &params, &sums}, B, h, w);
-  for (auto& v : {a, b, flow, vin, params, sums, o1, o2, of, ov}) keep.push_back(v);
-  const void *ap = a.data_ptr(), *bp = b.data_ptr(), *vp = vin.data_ptr();
+// t = [img1, img2, flow (fp32 dims[2]), valid (uint8 dims; a layout that has one), params (int32 [B][words]), sums, out1,
+// out2 (fp32 [B][h][w][3]), out_flow (fp32 [B][h][w][2]), out_valid (fp32 [B][h][w])], i = [B, geometry, h, w]
+static Launch make_augment_gather(const AugmentLayout& L, const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  const int v0 = 3 + L.valid;   // the tensors after valid
+  at::Tensor a = opt(t, 0), b = opt(t, 1), flow = opt(t, 2), vin = L.valid ? opt(t, 3) : at::Tensor();
+  at::Tensor params = opt(t, v0), sums = opt(t, v0 + 1);
+  at::Tensor o1 = opt(t, v0 + 2), o2 = opt(t, v0 + 3), of = opt(t, v0 + 4), ov = opt(t, v0 + 5);
+  const int64_t B = i[0], g0 = L.geom == 2 ? i[1] : 1, g1 = i[L.geom], h = i[L.geom + 1], w = i[L.geom + 2];
+  const std::string op = L.op;
+  check_augment_frames(a, b, B, g0, g1, L.op);
+  check_augment_sums(sums, B, L.op);
+  TORCH_CHECK(h >= 1 && w >= 1 && h <= 65535 * 4 && h * w <= 0x3fffffff, op, ": crop size");
+  check_f32(flow, (op + ": flow").c_str());
+  TORCH_CHECK(flow.numel() == B * g0 * g1 * 2 && reinterpret_cast<uintptr_t>(flow.data_ptr()) % 16 == 0, op, ": flow ",
+              L.dims, "[2], 16-byte aligned");
+  std::vector<const at::Tensor*> ins = {&a, &b, &flow, &params, &sums};
+  if (L.valid) {
+    TORCH_CHECK(vin.defined() && vin.is_cuda() && vin.scalar_type() == at::kByte && vin.is_contiguous() &&
+                    vin.numel() == B * g0 * g1, op, ": valid must be a contiguous device uint8 ", L.dims);
+    ins.push_back(&vin);
+  }
+  check_augment_records(params, B, L.words, L.op);
+  check_augment_outputs(op, {&o1, &o2, &of, &ov}, ins, B, h, w);
+  for (const at::Tensor* v : ins) keep.push_back(*v);
+  for (auto& v : {o1, o2, of, ov}) keep.push_back(v);
+  const void *ap = a.data_ptr(), *bp = b.data_ptr(), *vp = ptr(vin);
   const float* fp = flow.data_ptr<float>();
   const int *pp = params.data_ptr<int>(), *sp = sums.data_ptr<int>();
   float *p1 = o1.data_ptr<float>(), *p2 = o2.data_ptr<float>(), *pf = of.data_ptr<float>(), *pv = ov.data_ptr<float>();
+  const int layout = L.id;
   return [=](hipStream_t s, int) {
-    return jr_augment_sparse(ap, bp, fp, vp, pp, sp, p1, p2, pf, pv, (int)B, (int)Hb, (int)Wb, (int)h, (int)w, s);
-  };
-}
-
-// ---- dense and sparse samples in one batch (kernels augment_mixed.hip): packed slots of S pixels, i.e.
-// frames [B][1][S] to the checks above
-// t = [img1, img2 (uint8 [B][S][3]), params (int32 [B][52]), sums], i = [B, S]
-static Launch make_augment_mixed_sums(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
-  at::Tensor a = opt(t, 0), b = opt(t, 1), params = opt(t, 2), sums = opt(t, 3);
-  const int64_t B = i[0], S = i[1];
-  check_augment_frames(a, b, B, 1, S, "augment_mixed_sums");
-  check_augment_records(params, B, 52, "augment_mixed_sums");
-  check_augment_sums(sums, B, "augment_mixed_sums");
-  for (const at::Tensor* in : {&a, &b, &params})
-    TORCH_CHECK(!augment_overlap(sums, *in), "augment_mixed_sums: sums aliases an input");
-  for (auto& v : {a, b, params, sums}) keep.push_back(v);
-  const void *ap = a.data_ptr(), *bp = b.data_ptr();
-  const int* pp = params.data_ptr<int>();
-  int* sp = sums.data_ptr<int>();
-  return [=](hipStream_t s, int) { return jr_augment_mixed_sums(ap, bp, pp, (int)B, (long)S, sp, s); };
-}
-// t = [img1, img2, flow (fp32 [B][S][2]), valid (uint8 [B][S]), params (int32 [B][52]), sums, out1, out2
-// (fp32 [B][h][w][3]), out_flow (fp32 [B][h][w][2]), out_valid (fp32 [B][h][w])], i = [B, S, h, w]
-static Launch make_augment_mixed(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
-  at::Tensor a = opt(t, 0), b = opt(t, 1), flow = opt(t, 2), vin = opt(t, 3), params = opt(t, 4), sums = opt(t, 5);
-  at::Tensor o1 = opt(t, 6), o2 = opt(t, 7), of = opt(t, 8), ov = opt(t, 9);
-  const int64_t B = i[0], S = i[1], h = i[2], w = i[3];
-  check_augment_frames(a, b, B, 1, S, "augment_mixed");
-  check_augment_sums(sums, B, "augment_mixed");
-  TORCH_CHECK(h >= 1 && w >= 1 && h <= 65535 * 4 && h * w <= 0x3fffffff, "augment_mixed: crop size");
-  check_f32(flow, "augment_mixed: flow");
-  TORCH_CHECK(flow.numel() == B * S * 2 && reinterpret_cast<uintptr_t>(flow.data_ptr()) % 16 == 0,
-              "augment_mixed: flow [B][S][2], 16-byte aligned");
-  TORCH_CHECK(vin.defined() && vin.is_cuda() && vin.scalar_type() == at::kByte && vin.is_contiguous() &&
-                  vin.numel() == B * S, "augment_mixed: valid must be a contiguous device uint8 [B][S]");
-  check_augment_records(params, B, 52, "augment_mixed");
-  check_augment_outputs("augment_mixed", {&o1, &o2, &of, &ov}, {&a, &b, &flow, &vin, &params, &sums}, B, h, w);
-  for (auto& v : {a, b, flow, vin, params, sums, o1, o2, of, ov}) keep.push_back(v);
-  const void *ap = a.data_ptr(), *bp = b.data_ptr(), *vp = vin.data_ptr();
-  const float* fp = flow.data_ptr<float>();
-  const int *pp = params.data_ptr<int>(), *sp = sums.data_ptr<int>();
-  float *p1 = o1.data_ptr<float>(), *p2 = o2.data_ptr<float>(), *pf = of.data_ptr<float>(), *pv = ov.data_ptr<float>();
-  return [=](hipStream_t s, int) {
-    return jr_augment_mixed(ap, bp, fp, vp, pp, sp, p1, p2, pf, pv, (int)B, (long)S, (int)h, (int)w, s);
+    return jr_augment_gather(layout, ap, bp, fp, vp, pp, sp, p1, p2, pf, pv, (int)B, (int)g0, (int)g1, (int)h, (int)w, s);
   };
 }
 
@@ -2470,6 +2415,12 @@ static OpRow row_tia(const char* name, const char* fname, int lo, int hi, Launch
 static Launch make_conv_fwd(const TList& t, const IList& i, double alpha, Keep& keep) { return make_conv(t, i, alpha, keep); }
 static Launch make_init_flow_bf16(const TList& t, const IList& i, Keep& keep) { return make_init_flow(t, i, false, keep); }
 static Launch make_init_flow_f32(const TList& t, const IList& i, Keep& keep) { return make_init_flow(t, i, true, keep); }
+template <int L> static Launch make_augment_sums_of(const TList& t, const IList& i, Keep& keep) {
+  return make_augment_sums(AUGMENT_LAYOUTS[L], t, i, keep);
+}
+template <int L> static Launch make_augment_gather_of(const TList& t, const IList& i, Keep& keep) {
+  return make_augment_gather(AUGMENT_LAYOUTS[L], t, i, keep);
+}
 
 static const std::vector<OpRow>& op_table() {
   static const std::vector<OpRow> rows = {
@@ -2517,12 +2468,12 @@ static const std::vector<OpRow>& op_table() {
       row_ti("pack", 2, 2, make_pack),
       row_ti("wgrad", 16, 16, make_wgrad),
       row_ti("bn_table", 2, 2, make_bn_table),
-      row_ti("augment_sums", 3, 3, make_augment_sums),
-      row_ti("augment", 5, 5, make_augment),
-      row_ti("augment_sparse_sums", 3, 3, make_augment_sparse_sums),
-      row_ti("augment_sparse", 5, 5, make_augment_sparse),
-      row_ti("augment_mixed_sums", 2, 2, make_augment_mixed_sums),
-      row_ti("augment_mixed", 4, 4, make_augment_mixed),
+      row_ti("augment_sums", 3, 3, make_augment_sums_of<JR_AUGMENT_DENSE>),
+      row_ti("augment", 5, 5, make_augment_gather_of<JR_AUGMENT_DENSE>),
+      row_ti("augment_sparse_sums", 3, 3, make_augment_sums_of<JR_AUGMENT_SPARSE>),
+      row_ti("augment_sparse", 5, 5, make_augment_gather_of<JR_AUGMENT_SPARSE>),
+      row_ti("augment_mixed_sums", 2, 2, make_augment_sums_of<JR_AUGMENT_MIXED>),
+      row_ti("augment_mixed", 4, 4, make_augment_gather_of<JR_AUGMENT_MIXED>),
       row_ti("flow_metrics", 6, 6, make_flow_metrics),
       row_ti("unsup_loss", 4, 4, make_unsup_loss),
       row_ti("unsup_loss_bwd", 4, 4, make_unsup_loss_bwd),

@@ -53,8 +53,6 @@ KERNEL_SOURCES = [
     CSRC / "kernels" / "fbcheck.hip",
     CSRC / "kernels" / "framewarp.hip",
     CSRC / "kernels" / "augment.hip",
-    CSRC / "kernels" / "augment_sparse.hip",
-    CSRC / "kernels" / "augment_mixed.hip",
     CSRC / "kernels" / "metrics.hip",
     CSRC / "kernels" / "unsup.hip",
     CSRC / "kernels" / "census.hip",

@@ -675,14 +675,43 @@ def warp_frames(src: torch.Tensor, flow: torch.Tensor, occ: Optional[torch.Tenso
     return warped[0], (None if photo is None else photo[0])
 
 
+def _augment_sums(kernel: str, img1_u8, img2_u8, rec, out):
+    """Launch 1 of layout ``kernel`` (``augment``, ``augment_sparse`` or ``augment_mixed``); ``rec``: the
+    packed records on the device where the layout's sums read them."""
+    B, *geom = img1_u8.shape[:-1]
+    if out is None:
+        out = torch.empty((2, B, 3), dtype=torch.int32, device=img1_u8.device)
+    getattr(ops(), kernel + "_sums")([img1_u8, img2_u8] + ([] if rec is None else [rec]) + [out], [B, *geom])
+    return out
+
+
+def _augment_pairs(op: str, img1_u8, img2_u8, flow, valid_u8, params, crop):
+    """The GPU path of front-end ``op`` (``augment_pairs``, ``_sparse`` or ``_mixed``): the batch check it
+    shares with its golden op, the records validated on the host, uploaded pinned and ``non_blocking``,
+    the sums launch, four fresh outputs, the gather launch.  No host synchronisation.  ``valid_u8`` is
+    None for the dense layout, which has no valid plane and whose sums launch reads no records."""
+    from ..train import augment as A
+
+    B, *geom = A.check_batch(op, img1_u8, img2_u8, flow, valid_u8, params)
+    h, w = int(crop[0]), int(crop[1])
+    params.validate(tuple(geom) if len(geom) == 2 else geom[0], (h, w))
+    dev = img1_u8.device
+    kernel = op.replace("_pairs", "")
+    rec = params.packed(pin=True).to(dev, non_blocking=True)
+    sums = _augment_sums(kernel, img1_u8, img2_u8, None if valid_u8 is None else rec, None)
+    out1 = torch.empty((B, h, w, 3), dtype=torch.float32, device=dev)
+    out2 = torch.empty_like(out1)
+    oflow = torch.empty((B, h, w, 2), dtype=torch.float32, device=dev)
+    valid = torch.empty((B, h, w), dtype=torch.float32, device=dev)
+    planes = [img1_u8, img2_u8, flow] + ([] if valid_u8 is None else [valid_u8])
+    getattr(ops(), kernel)(planes + [rec, sums, out1, out2, oflow, valid], [B, *geom, h, w])
+    return out1, out2, oflow, valid
+
+
 def augment_sums(img1_u8: torch.Tensor, img2_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Exact per-channel integer sums of two batches of (B, Hs, Ws, 3) uint8 GPU frames ->
     int32 (2, B, 3) (launch 1 of :func:`augment_pairs`; the kernel clears ``out`` itself)."""
-    B, Hs, Ws, _ = img1_u8.shape
-    if out is None:
-        out = torch.empty((2, B, 3), dtype=torch.int32, device=img1_u8.device)
-    ops().augment_sums([img1_u8, img2_u8, out], [B, Hs, Ws])
-    return out
+    return _augment_sums("augment", img1_u8, img2_u8, None, out)
 
 
 def augment_pairs(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tensor, params,
@@ -693,87 +722,41 @@ def augment_pairs(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tens
     (bitwise equal; two launches and the upload of the records, no host synchronisation) on
     GPU tensors.  ``params``: the batch's :class:`~jax_raft_amd.train.augment.AugmentParams`,
     validated here on the host before anything is uploaded or launched."""
-    from ..train import augment as A
-
     if not img1_u8.is_cuda:
+        from ..train import augment as A
+
         return A.augment_pairs(img1_u8, img2_u8, flow, params, crop)
-    if (img1_u8.ndim != 4 or img1_u8.shape[-1] != 3 or img1_u8.shape != img2_u8.shape
-            or img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8):
-        raise ValueError("augment_pairs: images must be (B, Hs, Ws, 3) uint8 of one size")
-    B, Hs, Ws, _ = img1_u8.shape
-    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, Hs, Ws, 2):
-        raise ValueError(f"augment_pairs: flow must be ({B}, {Hs}, {Ws}, 2) fp32, got {tuple(flow.shape)} {flow.dtype}")
-    if len(params) != B:
-        raise ValueError(f"augment_pairs: {len(params)} records for a batch of {B}")
-    h, w = int(crop[0]), int(crop[1])
-    params.validate((Hs, Ws), (h, w))
-    dev = img1_u8.device
-    rec = params.packed(pin=True).to(dev, non_blocking=True)
-    sums = augment_sums(img1_u8, img2_u8)
-    out1 = torch.empty((B, h, w, 3), dtype=torch.float32, device=dev)
-    out2 = torch.empty_like(out1)
-    oflow = torch.empty((B, h, w, 2), dtype=torch.float32, device=dev)
-    valid = torch.empty((B, h, w), dtype=torch.float32, device=dev)
-    ops().augment([img1_u8, img2_u8, flow, rec, sums, out1, out2, oflow, valid], [B, Hs, Ws, h, w])
-    return out1, out2, oflow, valid
+    return _augment_pairs("augment_pairs", img1_u8, img2_u8, flow, None, params, crop)
 
 
 def augment_sums_sparse(img1_u8: torch.Tensor, img2_u8: torch.Tensor, rec: torch.Tensor,
                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Exact per-channel integer sums of each sample's own region of two batches of (B, Hb, Wb, 3)
     uint8 GPU buffers -> int32 (2, B, 3); ``rec``: the packed sparse records on the device."""
-    B, Hb, Wb, _ = img1_u8.shape
-    if out is None:
-        out = torch.empty((2, B, 3), dtype=torch.int32, device=img1_u8.device)
-    ops().augment_sparse_sums([img1_u8, img2_u8, rec, out], [B, Hb, Wb])
-    return out
+    return _augment_sums("augment_sparse", img1_u8, img2_u8, rec, out)
 
 
 def augment_pairs_sparse(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tensor, valid_u8: torch.Tensor,
                          params, crop: Tuple[int, int]):
     """RAFT's sparse augmentation (KITTI / HD1K) of a batch of samples of several sizes, each in
     the top-left corner of its (Hb, Wb) buffer -> ``(image1, image2, flow, valid)`` at the crop
-    size: ``train/augment.py:augment_pairs_sparse`` itself on CPU tensors, the HIP kernels of
-    ``augment_sparse.hip`` (bitwise equal; two launches and the upload of the records, no host
+    size: ``train/augment.py:augment_pairs_sparse`` itself on CPU tensors, the sparse layout of the
+    HIP kernels of ``augment.hip`` (bitwise equal; two launches and the upload of the records, no host
     synchronisation) on GPU tensors.  ``params``: the batch's
     :class:`~jax_raft_amd.train.augment.SparseAugmentParams`, validated here on the host before
     anything is uploaded or launched."""
-    from ..train import augment as A
-
     if not img1_u8.is_cuda:
+        from ..train import augment as A
+
         return A.augment_pairs_sparse(img1_u8, img2_u8, flow, valid_u8, params, crop)
-    if (img1_u8.ndim != 4 or img1_u8.shape[-1] != 3 or img1_u8.shape != img2_u8.shape
-            or img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8):
-        raise ValueError("augment_pairs_sparse: images must be (B, Hb, Wb, 3) uint8 of one size")
-    B, Hb, Wb, _ = img1_u8.shape
-    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, Hb, Wb, 2):
-        raise ValueError(f"augment_pairs_sparse: flow must be ({B}, {Hb}, {Wb}, 2) fp32, got {tuple(flow.shape)} {flow.dtype}")
-    if valid_u8.dtype != torch.uint8 or tuple(valid_u8.shape) != (B, Hb, Wb):
-        raise ValueError(f"augment_pairs_sparse: valid must be ({B}, {Hb}, {Wb}) uint8, got {tuple(valid_u8.shape)} {valid_u8.dtype}")
-    if not isinstance(params, A.SparseAugmentParams) or len(params) != B:
-        raise ValueError(f"augment_pairs_sparse: SparseAugmentParams for a batch of {B} wanted")
-    h, w = int(crop[0]), int(crop[1])
-    params.validate((Hb, Wb), (h, w))
-    dev = img1_u8.device
-    rec = params.packed(pin=True).to(dev, non_blocking=True)
-    sums = augment_sums_sparse(img1_u8, img2_u8, rec)
-    out1 = torch.empty((B, h, w, 3), dtype=torch.float32, device=dev)
-    out2 = torch.empty_like(out1)
-    oflow = torch.empty((B, h, w, 2), dtype=torch.float32, device=dev)
-    valid = torch.empty((B, h, w), dtype=torch.float32, device=dev)
-    ops().augment_sparse([img1_u8, img2_u8, flow, valid_u8, rec, sums, out1, out2, oflow, valid], [B, Hb, Wb, h, w])
-    return out1, out2, oflow, valid
+    return _augment_pairs("augment_pairs_sparse", img1_u8, img2_u8, flow, valid_u8, params, crop)
 
 
 def augment_sums_mixed(img1_u8: torch.Tensor, img2_u8: torch.Tensor, rec: torch.Tensor,
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Exact per-channel integer sums of each sample's packed pixels in two batches of (B, S, 3) uint8
     GPU slots -> int32 (2, B, 3); ``rec``: the packed mixed records on the device."""
-    B, S, _ = img1_u8.shape
-    if out is None:
-        out = torch.empty((2, B, 3), dtype=torch.int32, device=img1_u8.device)
-    ops().augment_mixed_sums([img1_u8, img2_u8, rec, out], [B, S])
-    return out
+    return _augment_sums("augment_mixed", img1_u8, img2_u8, rec, out)
 
 
 def augment_pairs_mixed(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tensor, valid_u8: torch.Tensor,
@@ -781,35 +764,15 @@ def augment_pairs_mixed(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torc
     """The augmentation of a batch of dense and sparse samples (RAFT's Sintel stage) in packed slots --
     (B, S, 3) uint8 x 2, (B, S, 2) fp32, (B, S) uint8, sample n in the first Hs * Ws pixels of slot n --
     -> ``(image1, image2, flow, valid)`` at the crop size: ``train/augment.py:augment_pairs_mixed``
-    itself on CPU tensors, the HIP kernels of ``augment_mixed.hip`` (bitwise equal; two launches and the
-    upload of the records, no host synchronisation) on GPU tensors.  ``params``: the batch's
-    :class:`~jax_raft_amd.train.augment.MixedAugmentParams`, validated here on the host before
+    itself on CPU tensors, the mixed layout of the HIP kernels of ``augment.hip`` (bitwise equal; two
+    launches and the upload of the records, no host synchronisation) on GPU tensors.  ``params``: the
+    batch's :class:`~jax_raft_amd.train.augment.MixedAugmentParams`, validated here on the host before
     anything is uploaded or launched."""
-    from ..train import augment as A
-
     if not img1_u8.is_cuda:
+        from ..train import augment as A
+
         return A.augment_pairs_mixed(img1_u8, img2_u8, flow, valid_u8, params, crop)
-    if (img1_u8.ndim != 3 or img1_u8.shape[-1] != 3 or img1_u8.shape != img2_u8.shape
-            or img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8):
-        raise ValueError("augment_pairs_mixed: images must be (B, S, 3) uint8 of one size")
-    B, S, _ = img1_u8.shape
-    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, S, 2):
-        raise ValueError(f"augment_pairs_mixed: flow must be ({B}, {S}, 2) fp32, got {tuple(flow.shape)} {flow.dtype}")
-    if valid_u8.dtype != torch.uint8 or tuple(valid_u8.shape) != (B, S):
-        raise ValueError(f"augment_pairs_mixed: valid must be ({B}, {S}) uint8, got {tuple(valid_u8.shape)} {valid_u8.dtype}")
-    if not isinstance(params, A.MixedAugmentParams) or len(params) != B:
-        raise ValueError(f"augment_pairs_mixed: MixedAugmentParams for a batch of {B} wanted")
-    h, w = int(crop[0]), int(crop[1])
-    params.validate(S, (h, w))
-    dev = img1_u8.device
-    rec = params.packed(pin=True).to(dev, non_blocking=True)
-    sums = augment_sums_mixed(img1_u8, img2_u8, rec)
-    out1 = torch.empty((B, h, w, 3), dtype=torch.float32, device=dev)
-    out2 = torch.empty_like(out1)
-    oflow = torch.empty((B, h, w, 2), dtype=torch.float32, device=dev)
-    valid = torch.empty((B, h, w), dtype=torch.float32, device=dev)
-    ops().augment_mixed([img1_u8, img2_u8, flow, valid_u8, rec, sums, out1, out2, oflow, valid], [B, S, h, w])
-    return out1, out2, oflow, valid
+    return _augment_pairs("augment_pairs_mixed", img1_u8, img2_u8, flow, valid_u8, params, crop)
 
 
 METRICS_RUN, METRICS_BLOCK = 4, 256      # pixels per thread and threads per block of metrics.hip

@@ -40,7 +40,7 @@ plain crop plus normalisation: the ``augment=False`` path is this op with such r
 
 Sparse ground truth (KITTI, HD1K) has an op of its own, :func:`augment_pairs_sparse`, with records
 that also carry each sample's size (:class:`SparseAugmentParams`, :func:`sample_sparse`): the
-images as above, the flow moved point by point (its docstring; ``csrc/kernels/augment_sparse.hip``).
+images as above, the flow moved point by point (its docstring; ``augment.hip``'s sparse layout).
 """
 from __future__ import annotations
 
@@ -342,15 +342,8 @@ def augment_pairs(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tens
                   crop: Tuple[int, int]):
     """The golden op (module docstring): (B, Hs, Ws, 3) uint8 x 2, (B, Hs, Ws, 2) fp32 flow ->
     image1, image2 (B, h, w, 3) fp32 in [-1, 1], flow (B, h, w, 2) fp32, valid (B, h, w) fp32."""
-    B, Hs, Ws, _ = img1_u8.shape
+    B, Hs, Ws = check_batch("augment_pairs", img1_u8, img2_u8, flow, None, params)
     h, w = crop
-    if (img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8 or img1_u8.shape != img2_u8.shape
-            or img1_u8.shape[-1] != 3):
-        raise ValueError("augment_pairs: images must be (B, Hs, Ws, 3) uint8 of one size")
-    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, Hs, Ws, 2):
-        raise ValueError("augment_pairs: flow must be (B, Hs, Ws, 2) fp32")
-    if len(params) != B:
-        raise ValueError(f"augment_pairs: {len(params)} records for a batch of {B}")
     params.validate((Hs, Ws), (h, w))
     dev = img1_u8.device
     pi, pf, icol, fcol = _records_on(params, dev)
@@ -370,7 +363,7 @@ def augment_pairs(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tens
 # ------------------------------------------------------- sparse ground truth
 # RAFT's ``SparseFlowAugmentor`` (KITTI, HD1K).  The samples of a batch have sizes of their own
 # and sit in the top-left corners of (B, Hb, Wb, ...) buffers.
-# record layout (one sample: 20 int32 words + 32 fp32 words; csrc/kernels/augment_sparse.hip reads
+# record layout (one sample: 20 int32 words + 32 fp32 words; csrc/kernels/augment.hip reads
 # the same): words 0..15 of the ints and all floats are the dense record's, then the sample's size
 N_INTS_SPARSE = 20
 I_HS, I_WS = 16, 17
@@ -388,7 +381,7 @@ _SPARSE_HFLIP = {"kitti": 0.0, "sintel": 0.5}
 
 def scan_window(T, ratio, size: int):
     """The source indices ``lo .. hi`` the kernel scans for landers on target ``T`` (an int or an
-    array), the formula of ``augment_sparse.hip:scan_window`` in fp32: ``floor((T - 0.5) * ratio)
+    array), the formula of ``augment_common.h:scan_window`` in fp32: ``floor((T - 0.5) * ratio)
     - 1 .. ceil((T + 0.5) * ratio) + 1`` clamped to ``[0, size - 1]``.  ``fp32(s) * inv`` is
     monotone in s and ``rint(.) == T`` needs it within 0.5 of T up to rounding, far inside the
     margin of 1."""
@@ -508,17 +501,8 @@ def augment_pairs_sparse(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: tor
     gather of the winners); the kernel is a gather that inverts the map, so the two are independent.
     ``return_landers``: also the number of landers per output pixel, (B, h, w) int64, and the number
     of valid points dropped at ``X == Wr`` per sample."""
-    if (img1_u8.ndim != 4 or img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8
-            or img1_u8.shape != img2_u8.shape or img1_u8.shape[-1] != 3):
-        raise ValueError("augment_pairs_sparse: images must be (B, Hb, Wb, 3) uint8 of one size")
-    B, Hb, Wb, _ = img1_u8.shape
+    B, Hb, Wb = check_batch("augment_pairs_sparse", img1_u8, img2_u8, flow, valid_u8, params)
     h, w = crop
-    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, Hb, Wb, 2):
-        raise ValueError("augment_pairs_sparse: flow must be (B, Hb, Wb, 2) fp32")
-    if valid_u8.dtype != torch.uint8 or tuple(valid_u8.shape) != (B, Hb, Wb):
-        raise ValueError("augment_pairs_sparse: valid must be (B, Hb, Wb) uint8")
-    if not isinstance(params, SparseAugmentParams) or len(params) != B:
-        raise ValueError(f"augment_pairs_sparse: SparseAugmentParams for a batch of {B} wanted")
     params.validate((Hb, Wb), (h, w))
     dev = img1_u8.device
     outs, landers, dropped = [], [], []
@@ -565,7 +549,7 @@ def augment_pairs_sparse(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: tor
 # RAFT's Sintel stage draws dense lists (Sintel, FlyingThings) and sparse ones (KITTI, HD1K) into the
 # same batches.  The samples sit in PACKED SLOTS: buffers (B, S, ...) with S the largest Hs * Ws, sample
 # n in the first Hs * Ws pixels of slot n with row pitch Ws.  The record is the sparse one with one of
-# its spare words in use (csrc/kernels/augment_mixed.hip reads the same).
+# its spare words in use (csrc/kernels/augment.hip reads the same).
 I_DENSE = 18           # 1: dense ground truth (the four-tap blend), 0: sparse (the point-by-point move)
 
 
@@ -647,6 +631,30 @@ def sample_mixed(batch: int, sizes: Sequence[Tuple[int, int]], dense_flags: Sequ
     return MixedAugmentParams.cat(out)
 
 
+# What the three golden ops and their GPU front-ends (ops/native.py) check first, per layout: the frame
+# dims as the messages name them, and the record class (a class with sizes of its own: a valid plane too)
+_LAYOUTS = {"augment_pairs": ("Hs, Ws", AugmentParams), "augment_pairs_sparse": ("Hb, Wb", SparseAugmentParams),
+            "augment_pairs_mixed": ("S", MixedAugmentParams)}
+
+
+def check_batch(op: str, img1_u8, img2_u8, flow, valid_u8, params) -> Tuple[int, ...]:
+    """``ValueError`` unless this is a batch of op ``op``'s layout: images uint8 of one shape
+    ``lead + (3,)``, flow fp32 ``lead + (2,)``, valid uint8 ``lead`` where the layout has one, and
+    ``lead[0]`` records of the layout's class -> ``lead``: (B, Hs, Ws), (B, Hb, Wb) or (B, S)."""
+    dims, cls = _LAYOUTS[op]
+    if (img1_u8.ndim != dims.count(",") + 3 or img1_u8.shape[-1] != 3 or img1_u8.shape != img2_u8.shape
+            or img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8):
+        raise ValueError(f"{op}: images must be (B, {dims}, 3) uint8 of one size")
+    lead = tuple(img1_u8.shape[:-1])
+    if flow.dtype != torch.float32 or tuple(flow.shape) != lead + (2,):
+        raise ValueError(f"{op}: flow must be {lead + (2,)} fp32, got {tuple(flow.shape)} {flow.dtype}")
+    if cls is not AugmentParams and (valid_u8.dtype != torch.uint8 or tuple(valid_u8.shape) != lead):
+        raise ValueError(f"{op}: valid must be {lead} uint8, got {tuple(valid_u8.shape)} {valid_u8.dtype}")
+    if not isinstance(params, cls) or len(params) != lead[0]:
+        raise ValueError(f"{op}: {cls.__name__} for a batch of {lead[0]} wanted")
+    return lead
+
+
 @torch.no_grad()
 def augment_pairs_mixed(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torch.Tensor, valid_u8: torch.Tensor,
                         params: MixedAugmentParams, crop: Tuple[int, int]):
@@ -656,16 +664,7 @@ def augment_pairs_mixed(img1_u8: torch.Tensor, img2_u8: torch.Tensor, flow: torc
     :func:`augment_pairs` if the record is dense (valid then follows the dense rule, and the slot's
     valid bytes are not read) or through :func:`augment_pairs_sparse` if it is sparse; the outputs
     are stacked.  Nothing past ``Hs * Ws`` in a slot is read."""
-    if (img1_u8.ndim != 3 or img1_u8.dtype != torch.uint8 or img2_u8.dtype != torch.uint8
-            or img1_u8.shape != img2_u8.shape or img1_u8.shape[-1] != 3):
-        raise ValueError("augment_pairs_mixed: images must be (B, S, 3) uint8 of one size")
-    B, S, _ = img1_u8.shape
-    if flow.dtype != torch.float32 or tuple(flow.shape) != (B, S, 2):
-        raise ValueError("augment_pairs_mixed: flow must be (B, S, 2) fp32")
-    if valid_u8.dtype != torch.uint8 or tuple(valid_u8.shape) != (B, S):
-        raise ValueError("augment_pairs_mixed: valid must be (B, S) uint8")
-    if not isinstance(params, MixedAugmentParams) or len(params) != B:
-        raise ValueError(f"augment_pairs_mixed: MixedAugmentParams for a batch of {B} wanted")
+    B, S = check_batch("augment_pairs_mixed", img1_u8, img2_u8, flow, valid_u8, params)
     crop = (int(crop[0]), int(crop[1]))
     params.validate(S, crop)
     outs = []

@@ -112,6 +112,30 @@ def test_sums_cover_each_sample_s_packed_pixels():
     assert got.dtype == torch.int32 and torch.equal(got.cpu().long(), want)
 
 
+def test_the_three_sums_agree_across_a_block_boundary():
+    """A sums block covers 4096 pixels: 70 x 61 = 4270 is two blocks with a ragged second one, and the second block
+    of 3 x 5 returns early.  Dense (each sample a batch of one), sparse ((70, 61) buffers, padding 255) and mixed
+    (slots of 4270 pixels, tails 255) all give the int64 sums of the host."""
+    sizes = [(70, 61), (3, 5)]
+    Hb, Wb = sizes[0]
+    g = torch.Generator().manual_seed(0)
+    frames = [[torch.randint(0, 256, (Hs, Ws, 3), generator=g, dtype=torch.uint8) for Hs, Ws in sizes] for _ in range(2)]
+    want = torch.stack([torch.stack([f.to(torch.int64).sum((0, 1)) for f in img]) for img in frames])     # (2, B, 3)
+    dense = torch.cat([nat.augment_sums(frames[0][n][None].cuda(), frames[1][n][None].cuda()) for n in range(2)], 1)
+    padded = torch.full((2, 2, Hb, Wb, 3), 255, dtype=torch.uint8)
+    packed = torch.full((2, 2, Hb * Wb, 3), 255, dtype=torch.uint8)
+    for k in range(2):
+        for n, (Hs, Ws) in enumerate(sizes):
+            padded[k, n, :Hs, :Ws] = frames[k][n]
+            packed[k, n, :Hs * Ws] = frames[k][n].reshape(Hs * Ws, 3)
+    sparse = nat.augment_sums_sparse(padded[0].cuda(), padded[1].cuda(), SparseAugmentParams.identity(sizes).packed().cuda())
+    mixed = nat.augment_sums_mixed(packed[0].cuda(), packed[1].cuda(),
+                                   MixedAugmentParams.identity(sizes, [True, False]).packed().cuda())
+    for name, got in (("dense", dense), ("sparse", sparse), ("mixed", mixed)):
+        assert got.dtype == torch.int32 and torch.equal(got.cpu().to(torch.int64), want), name
+    assert torch.equal(dense, sparse) and torch.equal(sparse, mixed)
+
+
 def test_host_checks_raise_before_anything_is_launched():
     B, S, h, w = 1, 16 * 24, 8, 12
     dev = "cuda"

@@ -18,14 +18,14 @@ PNG decoding (Sintel) is not covered: the generated dataset is PPM.
 
 ``--sparse``: the same for sparse ground truth at the KITTI sizes (sources 375 x 1242 and
 370 x 1226 mixed in one batch, crop 288 x 960, batch 6): the two launches of
-``augment_sparse.hip`` on sampled ``kitti`` records, the training loop on a generated KITTI tree
+``augment.hip``'s sparse layout on sampled ``kitti`` records, the training loop on a generated KITTI tree
 (PNG frames, flow written by ``write_flow_png`` with the five filter types cycling over the rows)
 against ``SyntheticFlow`` at the crop size, and the host time of one flow-PNG decode with the
 C++ un-filter and with the numpy fallback.
 
 ``--mixed``: RAFT's Sintel-stage mixture on a generated tree with all five parts at their real frame
 sizes (Sintel 436 x 1024, FlyingThings3D 540 x 960, KITTI, HD1K 1080 x 2560; crop 368 x 768, batch 6):
-the two launches of ``augment_mixed.hip`` on sampled ``sintel`` records, the bytes and stream time of the
+the two launches of ``augment.hip``'s mixed layout on sampled ``sintel`` records, the bytes and stream time of the
 prefix uploads and the decode time of a batch with and without an HD1K sample, and the training loop
 with RAFT's weights (``mix``) and with HD1K weighted up so that most batches hold one (``mix+``) against
 ``SyntheticFlow`` at the crop size.
