@@ -397,6 +397,23 @@ int jr_census_loss_bwd(const float* pred, const float* gray, const float* coef, 
 int jr_range_splat(const float* flow_fw, const float* flow_bw, int* acc, int B, int H, int W, hipStream_t stream);
 int jr_range_visible(const float* flow_fw, const float* flow_bw, const int* acc, float* vis, int B, int H, int W,
                      int T, hipStream_t stream);
+// Self-supervision for label-free training (selfsup.hip; train/selfsup.py, crop_resize bitwise).
+// jr_crop_resize: x, out fp32 [B][H][W][C] (C = 1, 2, 3; distinct buffers), the centre crop [c, H - c) x
+// [c, W - c) resampled bilinearly to H x W; prm fp32 [6] = (rx, ry, scale[0..3]) on the device; c >= 1,
+// 2 c < min(H, W), B and H at most 65535.  jr_selfsup_loss / _bwd: pred fp32 [N][Btot][H][W][2] (8-byte
+// aligned), of which the batches [B0, B0 + B) are read; target fp32 [B][H][W][2] (8-byte aligned); weight
+// (optional) fp32 [B][H][W]; prm fp32 [1] = eps; 1 <= N <= 32, Btot * H * W < 2^31.  jr_selfsup_loss writes
+// part fp32 [jr_selfsup_loss_blocks(B * H * W)][N][4] (16-byte aligned): the sum of the terms, and for
+// iteration N - 1 that sum again, the sum of the weights and the count of weights above 0 (0 in the other
+// rows).  jr_selfsup_loss_bwd writes grad fp32 [N][B][H][W][2] (8-byte aligned) with scale fp32 [N].  Both launch
+// their 16-byte instantiation when the window, the target (and grad) are 16-byte aligned, the weight 8-byte aligned
+// and B * H * W, Btot * H * W and B0 * H * W even; the 8-byte instantiation otherwise.
+int jr_crop_resize(const float* x, const float* prm, float* out, int B, int H, int W, int C, int c, hipStream_t stream);
+int jr_selfsup_loss_blocks(long P);
+int jr_selfsup_loss(const float* pred, const float* target, const float* weight, const float* prm, float* part, int N,
+                    int B, int H, int W, int Btot, int B0, hipStream_t stream);
+int jr_selfsup_loss_bwd(const float* pred, const float* target, const float* weight, const float* prm, const float* scale,
+                        float* grad, int N, int B, int H, int W, int Btot, int B0, hipStream_t stream);
 // Conv of a 2-channel input (the flow branch's 7x7 / 3x3): x bf16 NHWC
 // [N][H][W][x_cstride] (channels 0, 1 used), stride 1, output H x W; w bf16
 // MFMA A fragments [cout/16][NKC][64 lanes][8] (jax_raft_amd/ops/native.py:

@@ -2383,6 +2383,84 @@ static Launch make_range_visible(const TList& t, const IList& i, std::vector<at:
   return [=](hipStream_t s, int) { return jr_range_visible(fp, bp, ap, vp, b, h, w, T, s); };
 }
 
+// ------------------------------------------------------------ self-supervision
+// (kernels selfsup.hip).  crop_resize: t = [x (fp32 [B][H][W][C], C = 1..3), prm (fp32 [6] = rx, ry, scale[0..3]),
+// out (fp32 like x)], i = [B, H, W, C, c].  selfsup_loss: t = [pred (fp32 [N][Btot][H][W][2]), target (fp32
+// [B][H][W][2]), weight? (fp32 [B][H][W]), prm (fp32 [1] = eps), part (fp32 [blocks][N][4])]; selfsup_loss_bwd:
+// t = [pred, target, weight?, prm, scale (fp32 [N]), grad (fp32 [N][B][H][W][2])]; i = [N, B, H, W, Btot, B0]
+// for both: the batches [B0, B0 + B) of pred are read in place.
+static Launch make_crop_resize(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  const std::string op = "crop_resize";
+  at::Tensor x = opt(t, 0), prm = opt(t, 1), out = opt(t, 2);
+  const int64_t B = i[0], H = i[1], W = i[2], C = i[3], c = i[4];
+  TORCH_CHECK(B >= 1 && B <= 65535 && H >= 1 && H <= 65535 && W >= 1 && W <= INT32_MAX, op, ": sizes (B and H at most 65535)");
+  TORCH_CHECK(C >= 1 && C <= 3, op, ": 1..3 channels, got ", C);
+  TORCH_CHECK(B * H * W * C <= INT32_MAX, op, ": B * H * W * C must be below 2^31");
+  TORCH_CHECK(c >= 1 && 2 * c < std::min(H, W), op, ": the crop margin must be at least 1 and leave a crop, got ", c);
+  check_f32(x, "crop_resize: x");
+  check_f32(prm, "crop_resize: prm");
+  check_f32(out, "crop_resize: out");
+  TORCH_CHECK(x.numel() == B * H * W * C && out.numel() == x.numel(), op, ": x and out must hold [B][H][W][C] = ",
+              B * H * W * C, " elements");
+  TORCH_CHECK(prm.numel() == 6, op, ": prm must hold (rx, ry, scale[0..3])");
+  TORCH_CHECK(x.device() == out.device() && prm.device() == out.device(), op, ": operands on several devices");
+  census_no_alias(op, ": out", out, {x, prm});
+  keep.insert(keep.end(), {x, prm, out});
+  const float *xp = x.data_ptr<float>(), *pp = prm.data_ptr<float>();
+  float* op_ = out.data_ptr<float>();
+  const int b = (int)B, h = (int)H, w = (int)W, ch = (int)C, cc = (int)c;
+  return [=](hipStream_t s, int) { return jr_crop_resize(xp, pp, op_, b, h, w, ch, cc, s); };
+}
+static Launch make_selfsup(const TList& t, const IList& i, std::vector<at::Tensor>& keep, bool bwd) {
+  const std::string op = bwd ? "selfsup_loss_bwd" : "selfsup_loss";
+  at::Tensor pred = opt(t, 0), target = opt(t, 1), weight = opt(t, 2), prm = opt(t, 3);
+  at::Tensor scale = bwd ? opt(t, 4) : at::Tensor(), out = opt(t, bwd ? 5 : 4);
+  const int64_t N = i[0], B = i[1], H = i[2], W = i[3], Btot = i[4], B0 = i[5];
+  TORCH_CHECK(N >= 1 && N <= 32, op, ": 1..32 predictions, got ", N);
+  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && Btot >= 1 && Btot <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX &&
+                  Btot * H <= INT32_MAX && Btot * H * W <= INT32_MAX, op, ": sizes (Btot * H * W must be below 2^31)");
+  TORCH_CHECK(B0 >= 0 && B0 <= Btot - B, op, ": the batch window [", B0, ", ", B0 + B, ") must lie inside [0, ", Btot, ")");
+  const int64_t P = B * H * W;
+  const std::pair<const at::Tensor*, const char*> f32s[] = {{&pred, ": pred"}, {&target, ": target"}, {&prm, ": prm"},
+                                                             {&out, bwd ? ": grad" : ": part"}};
+  for (const auto& v : f32s) check_f32(*v.first, (op + v.second).c_str());
+  TORCH_CHECK(pred.numel() == N * Btot * H * W * 2, op, ": pred must hold [N][Btot][H][W][2] = ", N * Btot * H * W * 2,
+              " elements");
+  TORCH_CHECK(target.numel() == P * 2, op, ": target must hold [B][H][W][2] = ", P * 2, " elements");
+  TORCH_CHECK(prm.numel() == 1, op, ": prm must hold (eps)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(pred.data_ptr()) % 8 == 0 && reinterpret_cast<uintptr_t>(target.data_ptr()) % 8 == 0,
+              op, ": pred and target must be 8-byte aligned");
+  std::vector<at::Tensor> inputs = {pred, target, prm};
+  if (weight.defined()) {
+    check_f32(weight, (op + ": weight").c_str());
+    TORCH_CHECK(weight.numel() == P, op, ": weight must hold [B][H][W] = ", P, " elements");
+    inputs.push_back(weight);
+  }
+  if (bwd) {
+    check_f32(scale, (op + ": scale").c_str());
+    TORCH_CHECK(scale.numel() == N, op, ": scale must hold [N] = ", N, " elements");
+    inputs.push_back(scale);
+    TORCH_CHECK(out.numel() == N * P * 2, op, ": grad must hold [N][B][H][W][2] = ", N * P * 2, " elements");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0, op, ": grad must be 8-byte aligned");
+  } else {
+    const int64_t need = (int64_t)jr_selfsup_loss_blocks(P) * N * 4;
+    TORCH_CHECK(out.numel() == need, op, ": part must hold [blocks][N][4] = ", need, " elements");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0, op, ": part must be 16-byte aligned");
+  }
+  for (const at::Tensor& v : inputs) TORCH_CHECK(v.device() == out.device(), op, ": operands on several devices");
+  census_no_alias(op, bwd ? ": grad" : ": part", out, inputs);
+  keep.insert(keep.end(), inputs.begin(), inputs.end());
+  keep.push_back(out);
+  const float *pp = pred.data_ptr<float>(), *tp = target.data_ptr<float>(), *wp = (const float*)ptr(weight);
+  const float *rp = prm.data_ptr<float>(), *sp = (const float*)ptr(scale);
+  float* op_ = out.data_ptr<float>();
+  const int n = (int)N, b = (int)B, h = (int)H, w = (int)W, bt = (int)Btot, b0 = (int)B0;
+  if (bwd) return [=](hipStream_t s, int) { return jr_selfsup_loss_bwd(pp, tp, wp, rp, sp, op_, n, b, h, w, bt, b0, s); };
+  return [=](hipStream_t s, int) { return jr_selfsup_loss(pp, tp, wp, rp, op_, n, b, h, w, bt, b0, s); };
+}
+static Launch make_selfsup_loss(const TList& t, const IList& i, std::vector<at::Tensor>& keep) { return make_selfsup(t, i, keep, false); }
+static Launch make_selfsup_loss_bwd(const TList& t, const IList& i, std::vector<at::Tensor>& keep) { return make_selfsup(t, i, keep, true); }
+
 // ----------------------------------------------------------------- op table
 // One row per launch op: its name, signature class, the int-list lengths it accepts and its
 // maker.  Both front-ends are generated from the row (register_ops): the eager op
@@ -2482,6 +2560,9 @@ static const std::vector<OpRow>& op_table() {
       row_ti("census_loss_bwd", 5, 5, make_census_loss_bwd),
       row_ti("range_splat", 3, 3, make_range_splat),
       row_ti("range_visible", 4, 4, make_range_visible),
+      row_ti("crop_resize", 5, 5, make_crop_resize),
+      row_ti("selfsup_loss", 6, 6, make_selfsup_loss),
+      row_ti("selfsup_loss_bwd", 6, 6, make_selfsup_loss_bwd),
       // fp32 parity mode
       row_tia("conv_f32", "alpha", 22, 22, make_conv_f32),
       row_ti("stats_f32", 3, 3, make_stats_f32),

@@ -57,6 +57,7 @@ KERNEL_SOURCES = [
     CSRC / "kernels" / "unsup.hip",
     CSRC / "kernels" / "census.hip",
     CSRC / "kernels" / "occlusion.hip",
+    CSRC / "kernels" / "selfsup.hip",
 ]
 HOST_SOURCES = [CSRC / "runtime" / "binding.cpp", CSRC / "runtime" / "png.cpp"]
 # every header of csrc/ is a dependency of every object (a missed header left stale objects in

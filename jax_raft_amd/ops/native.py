@@ -1094,6 +1094,135 @@ def visibility_masks(flow_fw: torch.Tensor, flow_bw: torch.Tensor, kind: str, th
     return torch.stack([~O.lands_inside(fw) | ~occ_fw, ~O.lands_inside(bw) | ~occ_bw]).float()
 
 
+SELFSUP_BLOCK, SELFSUP_GRID_X = 256, 1024    # threads per block (2 pixels each) and blocks per round (selfsup.hip)
+_selfsup_prm = {}
+
+
+def _cached_floats(values, device) -> torch.Tensor:
+    """A few floats as an fp32 device tensor, uploaded once per device and set of values (as ``unsup_params``)."""
+    key = (str(device),) + tuple(float(v) for v in values)
+    if key not in _selfsup_prm:
+        if len(_selfsup_prm) >= 64:
+            _selfsup_prm.clear()
+        _selfsup_prm[key] = torch.tensor(key[1:], dtype=torch.float32, device=device)
+    return _selfsup_prm[key]
+
+
+def crop_resize(x: torch.Tensor, c: int, scale=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The centre crop ``[c, H-c) x [c, W-c)`` of x (B, H, W, C) resampled bilinearly back to H x W, channel k
+    times ``scale[k]``: ``train/selfsup.py:crop_resize`` itself on CPU tensors (C <= 4, any float dtype), the HIP
+    kernel on GPU tensors (``csrc/kernels/selfsup.hip``; fp32, C <= 3, contiguous; bitwise equal, one launch,
+    no host synchronisation).  ``out``: a contiguous fp32 tensor like x to write into.  Wrong shapes, dtypes,
+    devices or crops raise ``ValueError`` before anything is launched."""
+    from ..train import selfsup as S
+
+    B, H, W, C = S.check_crop(x, c, scale)
+    if out is not None and (not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != x.dtype
+                            or out.device != x.device or not out.is_contiguous()):
+        raise ValueError(f"crop_resize: out must be a contiguous {tuple(x.shape)} {x.dtype} tensor on {x.device}")
+    if not x.is_cuda:
+        v = S.crop_resize(x, c, scale)
+        return v if out is None else out.copy_(v)
+    if x.dtype != torch.float32 or C > 3:
+        raise ValueError(f"crop_resize: fp32 with at most 3 channels on the GPU, got {x.dtype} with C = {C}")
+    if not x.is_contiguous():
+        raise ValueError("crop_resize: x must be contiguous on the GPU")
+    if B > 65535 or H > 65535 or B * H * W * C >= 2 ** 31:
+        raise ValueError(f"crop_resize: B and H at most 65535 and fewer than 2^31 elements, got {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.data_ptr() < x.data_ptr() + x.numel() * 4 and x.data_ptr() < out.data_ptr() + x.numel() * 4:
+        raise ValueError("crop_resize: out must not overlap x")
+    sc = [1.0] * 4 if scale is None else [float(s) for s in scale] + [1.0] * (4 - C)
+    prm = _cached_floats(S.crop_ratios(H, W, c) + tuple(sc), x.device)
+    ops().crop_resize([x.detach(), prm, out], [B, H, W, C, int(c)])
+    return out
+
+
+def selfsup_loss_blocks(P: int) -> int:
+    """Rows of block partials that ``selfsup_loss`` writes for P pixels."""
+    return min(SELFSUP_GRID_X, ((P + 1) // 2 + SELFSUP_BLOCK - 1) // SELFSUP_BLOCK)
+
+
+def selfsup_params(eps: float, device) -> torch.Tensor:
+    """``(eps,)`` as the fp32 device tensor the loss kernels read, uploaded once per device and value."""
+    return _cached_floats((eps,), device)
+
+
+def _selfsup_args(op, preds, target, weight, eps, prm, batch0):
+    """Host checks of the loss ops -> None on CPU tensors, else (tensors, ints) of the launch.  ``preds`` is the
+    whole (N, Btot, H, W, 2) stack, of which the batches [batch0, batch0 + B) are used, B = target.shape[0]."""
+    from ..train import selfsup as S
+
+    if not isinstance(preds, torch.Tensor) or preds.ndim != 5 or not isinstance(target, torch.Tensor) or target.ndim != 4:
+        raise ValueError(f"{op}: flow_preds must be (N, Btot, H, W, 2) and target (B, H, W, 2)")
+    Btot, B = preds.shape[1], target.shape[0]
+    if isinstance(batch0, bool) or not isinstance(batch0, int) or batch0 < 0 or B < 1 or batch0 + B > Btot:
+        raise ValueError(f"{op}: the batch window [{batch0}, {batch0} + {B}) must lie inside the stack's {Btot} batches")
+    win = preds[:, batch0:batch0 + B]
+    N, B, H, W = S._check(win, target, weight)
+    if not preds.is_cuda:
+        return None
+    for name, t in (("flow_preds", preds), ("target", target), ("weight", weight)):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"{op}: {name} must be fp32 on the GPU, got {t.dtype}")
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{op}: {name} must be contiguous on the GPU")
+    if preds.data_ptr() % 8 or target.data_ptr() % 8:
+        raise ValueError(f"{op}: flow_preds and target must be 8-byte aligned")
+    if N > 32 or Btot * H * W >= 2 ** 31:
+        raise ValueError(f"{op}: 1..32 predictions of fewer than 2^31 pixels, got N = {N}, Btot H W = {Btot * H * W}")
+    if prm is None:
+        prm = selfsup_params(eps, preds.device)
+    return [preds.detach(), target, weight, prm], [N, B, H, W, Btot, batch0]
+
+
+def selfsup_loss_partials(flow_preds: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None,
+                          eps: float = 0.001, prm: Optional[torch.Tensor] = None, batch0: int = 0) -> torch.Tensor:
+    """The partial sums of the self-supervision loss, fp32 (blocks, N, 4): per iteration the sum of the terms and,
+    for the last iteration, that sum again, the sum of the weights and the count of weights above 0 --
+    ``train/selfsup.py:selfsup_sums`` itself on CPU tensors (one row of partials), the HIP kernel on GPU tensors
+    (``csrc/kernels/selfsup.hip``; one launch, bitwise repeatable).  ``flow_preds`` is a whole contiguous stack
+    (N, Btot, H, W, 2), read in place at the batches ``[batch0, batch0 + B)``, B = ``target.shape[0]``."""
+    args = _selfsup_args("selfsup_loss", flow_preds, target, weight, eps, prm, batch0)
+    if args is None:
+        from ..train.selfsup import selfsup_sums
+
+        with torch.no_grad():
+            return selfsup_sums(flow_preds[:, batch0:batch0 + target.shape[0]], target, weight, eps)[None]
+    t, i = args
+    N, B, H, W = i[:4]
+    part = torch.empty((selfsup_loss_blocks(B * H * W), N, 4), dtype=torch.float32, device=flow_preds.device)
+    ops().selfsup_loss(t + [part], i)
+    return part
+
+
+def selfsup_loss_grad(flow_preds: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor], scale: torch.Tensor,
+                      eps: float = 0.001, prm: Optional[torch.Tensor] = None, batch0: int = 0) -> torch.Tensor:
+    """The gradient of ``sum_i scale[i] (sum of terms)_i`` in the window's predictions, (N, B, H, W, 2) contiguous:
+    autograd through ``train/selfsup.py:selfsup_sums`` on CPU tensors, the one-pass kernel on GPU tensors.
+    scale: (N,)."""
+    args = _selfsup_args("selfsup_loss_bwd", flow_preds, target, weight, eps, prm, batch0)
+    N = flow_preds.shape[0]
+    if not isinstance(scale, torch.Tensor) or tuple(scale.shape) != (N,) or scale.device != flow_preds.device:
+        raise ValueError(f"selfsup_loss_bwd: scale must be {(N,)} on {flow_preds.device}, got "
+                         f"{tuple(scale.shape) if isinstance(scale, torch.Tensor) else scale}")
+    if args is None:
+        from ..train.selfsup import selfsup_sums
+
+        with torch.enable_grad():
+            f = flow_preds[:, batch0:batch0 + target.shape[0]].detach().requires_grad_(True)
+            s = selfsup_sums(f, target, weight, eps)
+            return torch.autograd.grad((s[:, 0] * scale.to(s.dtype)).sum(), f)[0]
+    t, i = args
+    if scale.dtype != torch.float32:
+        raise ValueError(f"selfsup_loss_bwd: scale must be fp32 on the GPU, got {scale.dtype}")
+    N, B, H, W = i[:4]
+    grad = torch.empty((N, B, H, W, 2), dtype=torch.float32, device=flow_preds.device)
+    ops().selfsup_loss_bwd(t + [scale.contiguous(), grad], i)
+    return grad
+
+
 def conv2d(spec: ConvSpec, x: torch.Tensor, act: int = ACT_NONE, out_dtype=torch.bfloat16, alpha: float = 1.0,
            res: Optional[torch.Tensor] = None, res_post: int = 0, cfg: Optional[int] = None) -> torch.Tensor:
     """Eager NHWC conv of a contiguous bf16 tensor [N, H, W, C] (C == cin8)."""

@@ -32,7 +32,11 @@ Without ground truth: ``--loss unsup`` trains on the photometric + edge-aware sm
 UnFlow / SMURF; ``--gamma`` weights the iterations as ever), with augmentation records that keep
 brightness constancy.  ``--unsup-occlusion fb | range`` runs both directions in the step (2 x batch pairs
 through the model) and leaves the occluded pixels out of the photometric term (train/occlusion.py;
-``--unsup-occ-thr``: the range map's threshold, ``--unsup-occ-after``: the first step with masks).  ``--dataset frames`` lists the consecutive frames of every directory under ``--data``
+``--unsup-occ-thr``: the range map's threshold, ``--unsup-occ-after``: the first step with masks).
+``--unsup-selfsup-weight W`` (> 0; with ``--unsup-occlusion``) adds self-supervision (train/selfsup.py): from step
+``--unsup-selfsup-after`` on the model also runs on the centre crop (``--unsup-selfsup-crop``: the margin in pixels) of
+both directions, 4 x batch pairs in one call, and the cropped student is pulled towards the full frame's flow
+(``--unsup-selfsup-eps``: the Charbonnier eps).  ``--dataset frames`` lists the consecutive frames of every directory under ``--data``
 (no flow files; ``--loss unsup`` only).  On a labelled set the step also reports ``epe`` / ``1px`` / ``3px`` /
 ``5px``, which take no part in the gradient.
 
@@ -125,8 +129,31 @@ class TrainConfig:
     unsup_occlusion: str = "none"
     unsup_occ_thr: float = 0.5
     unsup_occ_after: int = 0
+    # Self-supervision (train/selfsup.py): from step unsup_selfsup_after on the model also runs on the centre crop
+    # (margin unsup_selfsup_crop, resampled to the frame) of both directions -- 4 * batch pairs in ONE model call --
+    # and the cropped "student" is pulled towards the full frame's detached flow where the teacher is valid and the
+    # student cannot verify its own flow; the term enters the loss with unsup_selfsup_weight (0: off, as ever).
+    unsup_selfsup_weight: float = 0.0
+    unsup_selfsup_crop: int = 64
+    unsup_selfsup_after: int = 0
+    unsup_selfsup_eps: float = 0.001
 
     def __post_init__(self):
+        selfsup = (self.unsup_selfsup_weight, self.unsup_selfsup_crop, self.unsup_selfsup_after, self.unsup_selfsup_eps)
+        if self.loss != "unsup" and selfsup != (0.0, 64, 0, 0.001):
+            raise ValueError("unsup_selfsup_weight, unsup_selfsup_crop, unsup_selfsup_after and unsup_selfsup_eps take "
+                             "loss='unsup'")
+        if self.unsup_selfsup_weight < 0:
+            raise ValueError(f"unsup_selfsup_weight must not be negative, got {self.unsup_selfsup_weight}")
+        if isinstance(self.unsup_selfsup_crop, bool) or not isinstance(self.unsup_selfsup_crop, int) or self.unsup_selfsup_crop < 1:
+            raise ValueError(f"unsup_selfsup_crop must be an int of at least 1, got {self.unsup_selfsup_crop!r}")
+        if not self.unsup_selfsup_eps > 0:                 # eps = 0 would give 0 / 0 where the student is on the target
+            raise ValueError(f"unsup_selfsup_eps must be above 0, got {self.unsup_selfsup_eps}")
+        if self.unsup_selfsup_after < 0:
+            raise ValueError(f"unsup_selfsup_after must not be negative, got {self.unsup_selfsup_after}")
+        if self.unsup_selfsup_weight > 0 and self.unsup_occlusion == "none":
+            raise ValueError("unsup_selfsup_weight > 0 takes unsup_occlusion 'fb' or 'range': the teacher's and the "
+                             "student's masks need both directions")
         if self.unsup_occlusion not in ("none", "fb", "range"):
             raise ValueError(f"unknown unsup_occlusion {self.unsup_occlusion!r} (none, fb or range)")
         if self.loss != "unsup" and (self.unsup_occlusion, self.unsup_occ_thr, self.unsup_occ_after) != ("none", 0.5, 0):
@@ -223,6 +250,13 @@ class Trainer:
         dp.broadcast_module(self.model)
         if cfg.sync_bn and self.world > 1:
             dp.convert_sync_batchnorm(self.model)
+        if cfg.unsup_selfsup_weight > 0:
+            # the crop has to keep one cell of the coarsest correlation level (8 * 2^(levels - 1) pixels) per axis
+            need = 8 * 2 ** (self.model.corr_block.num_levels - 1)
+            left = min(cfg.size) - 2 * cfg.unsup_selfsup_crop
+            if left < need:
+                raise ValueError(f"unsup_selfsup_crop = {cfg.unsup_selfsup_crop} leaves {left} pixels of the "
+                                 f"{tuple(cfg.size)} frame, {cfg.arch} needs at least {need}")
         self.flat_comm = dp.FlatGradComm() if self.world > 1 else None
         self.sync = dp.GradAllReducer(self.model, bucket_mb=cfg.bucket_mb, flat_comm=self.flat_comm)
         self._graph_ok = cfg.graph_step and self.device.type == "cuda" and self.world == 1
@@ -314,7 +348,9 @@ class Trainer:
         cfg = self.cfg
         self.opt.zero_grad(set_to_none=True)
         train_bn = not cfg.freeze_bn
-        if cfg.loss == "unsup" and cfg.unsup_occlusion != "none":
+        if cfg.loss == "unsup" and cfg.unsup_selfsup_weight > 0 and self.step >= cfg.unsup_selfsup_after:
+            loss, metrics = self._selfsup_loss(img1, img2, flow, valid)
+        elif cfg.loss == "unsup" and cfg.unsup_occlusion != "none":
             loss, metrics = self._occlusion_loss(img1, img2, flow, valid)
         elif cfg.loss == "unsup":
             preds = self.model(img1, img2, train=train_bn, num_flow_updates=cfg.iters, autograd=True)
@@ -370,12 +406,19 @@ class Trainer:
         (detached; ``ops/native.py:visibility_masks``) applied to every iteration's photometric term.  Before
         step ``unsup_occ_after`` there is no mask, but both directions run all the same, so that the batch
         shape and the cached plans do not change mid-run."""
+        B = img1.shape[0]
+        a, b = torch.cat([img1, img2]), torch.cat([img2, img1])
+        preds = self.model(a, b, train=not self.cfg.freeze_bn, num_flow_updates=self.cfg.iters, autograd=True)
+        loss, metrics, _ = self._masked_loss(preds, a, b, flow, valid)
+        return loss, metrics
+
+    def _masked_loss(self, preds, a, b, flow, valid):
+        """The loss and metrics of ``_occlusion_loss`` from the predictions (N, 2B, H, W, 2) of the stacked pairs
+        (a, b) -> ``(loss, metrics, mask)``; mask: the visibility masks (2B, H, W), None before ``unsup_occ_after``."""
         from ..ops import native as nat
 
         cfg = self.cfg
-        B = img1.shape[0]
-        a, b = torch.cat([img1, img2]), torch.cat([img2, img1])
-        preds = self.model(a, b, train=not cfg.freeze_bn, num_flow_updates=cfg.iters, autograd=True)
+        B = a.shape[0] // 2
         mask = None
         if self.step >= cfg.unsup_occ_after:
             last = preds[-1].detach()
@@ -390,7 +433,45 @@ class Trainer:
             with torch.no_grad():
                 _, sup = sequence_loss(preds[:, :B].detach(), flow, valid, cfg.gamma, cfg.max_flow)
             metrics = {**metrics, **sup}
-        return loss, metrics
+        return loss, metrics, mask
+
+    def _selfsup_loss(self, img1, img2, flow, valid):
+        """``_occlusion_loss`` plus self-supervision (train/selfsup.py): ONE model call over 4B pairs -- the 2B full
+        frames of both directions (``preds[:, :2B]``: the teacher, and the half that the existing loss, masks and
+        metrics run on unchanged) and their centre crops resampled to the frame (``preds[:, 2B:]``: the student) --
+        so the step keeps one forward and one backward.  The teacher's final flow, detached and brought into the
+        student's frame by ``crop_resize``, is the target of every student iteration, weighted by ``T' (1 - S)``:
+        T' the resampled plane "the teacher's pixel is visible and lands inside", S the same plane from the
+        student's own final flows -- the pixels the student cannot verify by itself.  (The crop of the swapped
+        stack is the swapped crop, bit for bit, so the frames are resampled by one launch, not two.)"""
+        from ..ops import native as nat
+        from .occlusion import lands_inside
+        from .selfsup import flow_scale, selfsup_loss
+
+        cfg = self.cfg
+        B = img1.shape[0]
+        c = cfg.unsup_selfsup_crop
+        a, b = torch.cat([img1, img2]), torch.cat([img2, img1])
+        sa = nat.crop_resize(a.float().contiguous(), c).to(a.dtype)
+        sb = torch.cat([sa[B:], sa[:B]])
+        preds = self.model(torch.cat([a, sa]), torch.cat([b, sb]), train=not cfg.freeze_bn, num_flow_updates=cfg.iters,
+                           autograd=True)
+        loss, metrics, mask = self._masked_loss(preds[:, :2 * B], a, b, flow, valid)
+        H, W = preds.shape[2:4]
+        with torch.no_grad():
+            full = preds[-1, :2 * B].detach().float().contiguous()
+            T = lands_inside(full).float()
+            if mask is not None:
+                T = mask * T
+            target = nat.crop_resize(full, c, flow_scale(H, W, c))
+            Tc = nat.crop_resize(T.view(2 * B, H, W, 1).contiguous(), c).view(2 * B, H, W)
+            student = preds[-1, 2 * B:].detach().float().contiguous()
+            S = lands_inside(student).float()
+            if mask is not None:
+                S = nat.visibility_masks(student[:B], student[B:], cfg.unsup_occlusion, cfg.unsup_occ_thr).view(2 * B, H, W) * S
+            weight = Tc * (1.0 - S)
+        term, mets = selfsup_loss(preds[:, 2 * B:], target, weight, cfg.gamma, cfg.unsup_selfsup_eps)
+        return loss + cfg.unsup_selfsup_weight * term, {**metrics, **mets}
 
     def _comm(self):
         """The fused native backward's flat-arena all-reduce, registered for

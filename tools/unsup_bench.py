@@ -27,7 +27,15 @@ they move and the atomics they issue; (c) the training step in three arms, block
 process: ``unsup_occlusion="none"`` at batch 6 (the step as it was), ``"none"`` at batch 12 (what the second
 direction costs: as many images through the model) and the chosen kind at batch 6 (12 images + the masks).
 
-  python tools/unsup_bench.py [--photo census | --occlusion range] [--out profiles/unsup_loss_overhead.txt]
+``--selfsup`` measures self-supervision instead (train/selfsup.py, csrc/kernels/selfsup.hip; default output
+``profiles/selfsup_overhead.txt``), at the chairs shape of a batch-6 step, (N, 2B, H, W) = (12, 12, 368, 496): (a) the
+three ``crop_resize`` launches of a step (the image stack, the flow, the teacher's plane) and the two loss launches
+on the student half of a 4B stack, read in place, with the bytes they must move; (b) ``selfsup_loss`` forward +
+backward against the golden op on the same GPU tensors, arms alternated, each run twice; (c) the training step in
+three arms alternated in one process: ``"range"`` at batch 6 without self-supervision, ``"range"`` at batch 12 (what
+4B pairs through the model cost) and self-supervision on at batch 6.
+
+  python tools/unsup_bench.py [--photo census | --occlusion range | --selfsup] [--out profiles/unsup_loss_overhead.txt]
 """
 import argparse
 import os
@@ -252,8 +260,171 @@ def occlusion_main(args, dev):
     print(text)
 
 
+def selfsup_inputs(dev, B2=2 * BATCH, c=64):
+    """A 4B stack of predictions whose student half lies around the teacher's flow in the student's frame, the
+    target, and a weight with the share of selected pixels a step has (a band near the border)."""
+    from jax_raft_amd.train.selfsup import flow_scale
+
+    _, _, flow, _ = SyntheticFlow((H, W), seed=0, device=dev).batch(list(range(B2)))
+    g = torch.Generator(device=dev).manual_seed(0)
+    target = nat.crop_resize(flow.contiguous(), c, flow_scale(H, W, c))
+    stack = torch.empty(N, 2 * B2, H, W, 2, device=dev)
+    stack[:, :B2] = flow[None]
+    stack[:, B2:] = target[None] + torch.randn(N, B2, H, W, 2, generator=g, device=dev) * torch.linspace(3.0, 0.3, N, device=dev).view(N, 1, 1, 1, 1)
+    T = nat.crop_resize(torch.ones(B2, H, W, 1, device=dev), c).view(B2, H, W)
+    S = torch.ones(B2, H, W, device=dev)
+    S[:, :24], S[:, -24:], S[:, :, :32], S[:, :, -32:] = 0.0, 0.0, 0.0, 0.0
+    return stack, target, (T * (1.0 - S)).contiguous(), flow.contiguous(), c
+
+
+def selfsup_launches(dev, reps):
+    from jax_raft_amd.train.selfsup import crop_ratios, flow_scale
+
+    stack, target, weight, flow, c = selfsup_inputs(dev)
+    B2 = target.shape[0]
+    P = B2 * H * W
+    mb = lambda *ts: sum(t.numel() * t.element_size() for t in ts) / 1e6
+    crop_mb = lambda x: 2 * x.numel() * 4 * ((H - 2 * c) * (W - 2 * c) / (H * W) + 1.0) / 2 / 1e6   # the crop read, the frame written
+    imgs = torch.rand(B2, H, W, 3, device=dev)
+    plane = torch.ones(B2, H, W, 1, device=dev)
+    rx, ry = crop_ratios(H, W, c)
+    prm1 = torch.tensor([rx, ry, 1, 1, 1, 1], dtype=torch.float32, device=dev)
+    prm2 = torch.tensor([rx, ry, *flow_scale(H, W, c), 1, 1], dtype=torch.float32, device=dev)
+    out3, out2, out1 = torch.empty_like(imgs), torch.empty_like(flow), torch.empty_like(plane)
+    eps = nat.selfsup_params(0.001, dev)
+    part = torch.empty(nat.selfsup_loss_blocks(P), N, 4, device=dev)
+    grad = torch.empty(N, B2, H, W, 2, device=dev)
+    scale = torch.full((N,), 1.0 / P, device=dev)
+    ints = [N, B2, H, W, 2 * B2, B2]
+    half = stack[:, B2:]
+    rows = [("crop_resize C=3", lambda: nat.ops().crop_resize([imgs, prm1, out3], [B2, H, W, 3, c]), crop_mb(imgs),
+             "the crop of the image stack read, the frames written"),
+            ("crop_resize C=2", lambda: nat.ops().crop_resize([flow, prm2, out2], [B2, H, W, 2, c]), crop_mb(flow),
+             "the crop of the teacher's flow read, the target written"),
+            ("crop_resize C=1", lambda: nat.ops().crop_resize([plane, prm1, out1], [B2, H, W, 1, c]), crop_mb(plane),
+             "the crop of the teacher's plane read, the weight's factor written"),
+            ("selfsup_loss", lambda: nat.ops().selfsup_loss([stack, target, weight, eps, part], ints), mb(half, target, weight, part),
+             "the student half of the predictions, target, weight, partials"),
+            ("selfsup_loss_bwd", lambda: nat.ops().selfsup_loss_bwd([stack, target, weight, eps, scale, grad], ints),
+             mb(half, target, weight, grad), "the student half, target, weight, gradient")]
+    return [(name, events(fn, dev, reps), mbytes, what) for name, fn, mbytes, what in rows], float((weight > 0).float().mean())
+
+
+def selfsup_pair(dev, reps):
+    from jax_raft_amd.train import selfsup_loss, selfsup_loss_reference
+
+    stack, target, weight, _, _ = selfsup_inputs(dev)
+    B2 = target.shape[0]
+    f = stack.requires_grad_(True)
+
+    def run(loss_fn):
+        def step():
+            f.grad = None
+            loss_fn(f[:, B2:], target, weight, 0.8, 0.001)[0].backward()
+        return step
+
+    arms = {"native": run(selfsup_loss), "torch": run(selfsup_loss_reference)}
+    times = {k: [] for k in arms}
+    peak = {}
+    for _ in range(2):
+        for name, step in arms.items():
+            f.grad = None
+            torch.cuda.reset_peak_memory_stats(dev)
+            base = torch.cuda.memory_allocated(dev)
+            times[name].append(events(step, dev, reps, warm=2) / 1000)     # ms
+            peak[name] = (torch.cuda.max_memory_allocated(dev) - base) / 1e6
+    return times, peak
+
+
+def selfsup_training(args, dev):
+    total = args.warmup + args.block * args.rounds
+    kw = dict(arch=args.arch, steps=total, iters=args.iters, size=(384, 512), log_every=10 ** 9, loss="unsup", unsup_occlusion="range")
+    arms = {"range b6": Trainer(TrainConfig(batch=BATCH, **kw)),
+            "range b12": Trainer(TrainConfig(batch=2 * BATCH, **kw)),
+            "selfsup b6": Trainer(TrainConfig(batch=BATCH, unsup_selfsup_weight=0.3, unsup_selfsup_crop=64, **kw))}
+    for name, tr in arms.items():
+        t0 = time.perf_counter()
+        for _ in range(args.warmup):
+            tr.train_step(tr.batch_for(tr.step))
+        tr.flush()
+        torch.cuda.synchronize(dev)
+        print(f"warm-up of {name}: {time.perf_counter() - t0:.1f} s", flush=True)
+    step_ms = {k: [] for k in arms}
+    share = []
+    for _ in range(args.rounds):
+        for name, tr in arms.items():
+            t0 = time.perf_counter()
+            for _ in range(args.block):
+                m = tr.train_step(tr.batch_for(tr.step))
+            tr.flush()
+            torch.cuda.synchronize(dev)
+            step_ms[name].append(1000 * (time.perf_counter() - t0) / args.block)
+            assert torch.isfinite(m["loss"]).item(), name
+            if "selfsup_w" in m:
+                share.append(float(m["selfsup_w"]))
+    return step_ms, {k: tr.skipped for k, tr in arms.items()}, share
+
+
+def selfsup_main(args, dev):
+    mean = lambda v: sum(v) / len(v)
+    B2 = 2 * BATCH
+    lines = [f"self-supervision of the label-free training step, {torch.cuda.get_device_name(dev)}",
+             f"student predictions (N, 2B, H, W) = ({N}, {B2}, {H}, {W}), fp32, the second half of a (N, 4B, H, W, 2) stack; crop margin 64", ""]
+    rows, on = selfsup_launches(dev, args.reps)
+    lines += [f"(a) GPU time per launch, device events over {args.reps} repetitions (weight > 0 on {100 * on:.1f} % of the pixels):"]
+    for name, us, mbytes, what in rows:
+        lines.append(f"    {name:17s} {us:8.1f} us   {mbytes:6.1f} MB at least ({what})  -> {mbytes / us * 1e3:6.0f} GB/s of them")
+    launch_ms = sum(us for _, us, _, _ in rows) / 1000
+    lines += [f"    the five launches of a step: {launch_ms:.3f} ms (the swapped image stack is the swapped crop: one launch for both)",
+              "    (the taps of crop_resize are re-reads that the caches serve; they are not in the byte counts)", ""]
+    print("\n".join(lines), flush=True)
+    times, peak = selfsup_pair(dev, args.pair_reps)
+    spread = max(abs(v[0] - v[1]) for v in times.values())
+    gain = mean(times["torch"]) - mean(times["native"])
+    lines += [f"(b) selfsup_loss forward + backward through the slice of the 4B stack, {args.pair_reps} repetitions per run, arms alternated "
+              "native / torch x 2:"]
+    for k, v in times.items():
+        lines.append(f"    {k:7s} {mean(v):8.3f} ms   [runs: {v[0]:.3f}, {v[1]:.3f}]   peak extra memory {peak[k]:8.0f} MB")
+    lines += [f"    torch - native: {gain:+.3f} ms ({mean(times['torch']) / mean(times['native']):.1f} x); larger difference "
+              f"between the two runs of one arm: {spread:.3f} ms",
+              "    -> " + ("native is faster by more than that spread" if gain > spread else
+                           "NOT faster by more than that spread: the condition does not hold"),
+              "    (both arms include autograd's padding of the window's gradient into the 4B stack)", ""]
+    print("\n".join(lines[-len(times) - 5:]), flush=True)
+    if not args.skip_training:
+        step_ms, skipped, share = selfsup_training(args, dev)
+        a, b, c = list(step_ms)
+        lines += [f"(c) training step, {args.arch}, 384x512, {args.iters} iterations, SyntheticFlow, loss='unsup', unsup_occlusion='range'; "
+                  f"{args.block} steps per block, blocks alternated {a} / {b} / {c} x {args.rounds} in one process after {args.warmup} "
+                  "warm-up steps each"]
+        for k, v in step_ms.items():
+            lines.append(f"    {k:10s} {mean(v):7.2f} ms/step  [per block: " + ", ".join(f"{x:.2f}" for x in v)
+                         + f"]  spread {max(v) - min(v):.2f} ms   skipped steps: {skipped[k]}")
+        worst = max(max(v) - min(v) for v in step_ms.values())
+        extra = mean(step_ms[c]) - mean(step_ms[b])
+        lines += [f"    {a} is the step as it was; {b} runs as many pairs through the model as {c} (24), without self-supervision",
+                  f"    4B pairs ({b} - {a}): {mean(step_ms[b]) - mean(step_ms[a]):+.2f} ms/step ({mean(step_ms[b]) / mean(step_ms[a]):.2f} x)",
+                  f"    self-supervision on top ({c} - {b}): {extra:+.2f} ms/step; the measured launches: {launch_ms:.2f} ms; largest spread "
+                  f"between blocks of one arm {worst:.2f} ms",
+                  "    -> " + ("the self-supervised step costs no more than the batch-12 arm plus the launches, within that spread"
+                               if extra <= launch_ms + worst else
+                               "the self-supervised step costs MORE than the batch-12 arm plus the launches and the spread: the condition "
+                               "does not hold"),
+                  "    share of pixels with weight > 0, last step of each block: " + ", ".join(f"{v:.3f}" for v in share),
+                  "    (beside the five launches the step runs a second visibility_masks call, two lands_inside compositions, the slice "
+                  "copy of the full-frame half for unsup_loss and the padding of both halves' gradients)", ""]
+    lines += ["No accuracy figure follows from this: the weights are random and there is no dataset here, so whether self-supervision "
+              "helps is not measured.", ""]
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--selfsup", action="store_true", help="measure self-supervision instead of the loss")
     ap.add_argument("--occlusion", default=None, choices=("fb", "range"), help="measure the occlusion masks instead of the loss")
     ap.add_argument("--photo", default="charbonnier", choices=("charbonnier", "census"))
     ap.add_argument("--out", default=None, help="default: profiles/unsup_loss_overhead.txt, census_loss_overhead.txt with --photo census")
@@ -267,6 +438,10 @@ def main():
     ap.add_argument("--skip-training", action="store_true", help="(a) and (b) only")
     args = ap.parse_args()
     census = args.photo == "census"
+    if args.selfsup:
+        assert torch.cuda.is_available(), "unsup_bench measures on the GPU"
+        args.out = args.out or "profiles/selfsup_overhead.txt"
+        return selfsup_main(args, torch.device("cuda", 0))
     if args.occlusion:
         assert torch.cuda.is_available(), "unsup_bench measures on the GPU"
         args.out = args.out or "profiles/occlusion_overhead.txt"
