@@ -26,8 +26,8 @@
 //      per offset, the warped part once per offset and iteration.  TX = 32: one 32-lane half of a
 //      wave reads 32 consecutive words of one LDS row, whatever the offset, so the shifted reads
 //      (ds_read_b32: banks modulo 32 per half) have no bank conflict and the rows need no padding.
-//      Output: one row part[tile][i][4] per tile and iteration (thread -> wave shuffles -> 4 LDS
-//      words): (sum of mask * term, masked pixels that are not inside, masked pixels inside but in
+//      Output: one row part[tile][i][4] per tile and iteration (loss_common.h's reduction):
+//      (sum of mask * term, masked pixels that are not inside, masked pixels inside but in
 //      the band, sum of cen over the valid masked pixels -- the last iteration only, 0 elsewhere),
 //      and the plane coef[i][q] = mask valid 0.4 (h + 0.01)^-0.6 for the backward.  Counts are at
 //      most TX * TY per row: exact.
@@ -41,18 +41,18 @@
 //      writes (add = 0) or adds (add = 1) scale[i] A(q) (dw/dwx, dw/dwy)(q) where inside(q), 0
 //      elsewhere, to grad[i][q]: each element is owned by one thread.
 //   The per-element order of products and sums depends on neither the tile nor the block.
-#include "common.h"
 #include "kernels.h"
+#include "loss_common.h"
 
 namespace {
 
+using namespace loss;
+
 constexpr int TX = 32, TY = 8;            // the pixel tile of a block; TX * TY threads
-constexpr int ITERS = 4;                  // iterations per block
 constexpr int R = 3;                      // patch radius
 constexpr int LW = TX + 2 * R, LH = TY + 2 * R;
 constexpr int LN = LW * LH;
-constexpr int BLOCK = TX * TY;
-constexpr int MAX_N = 32;
+static_assert(TX * TY == BLOCK, "one thread per pixel of the tile");
 constexpr float C_TAU = 0.81f, C_K = 0.1f, C_H = 0.01f;
 
 // The hardware's reciprocal and reciprocal square root (1 ulp; the arguments are at least 0.1 and
@@ -67,7 +67,7 @@ __device__ __forceinline__ float tau(float d) { return d * rsq(C_TAU + d * d); }
 __device__ __forceinline__ float warp_gray(float2 f, int y, int x, int H, int W, const float* __restrict__ g2, bool& inside,
                                            float& dwx, float& dwy) {
   const float px = (float)x + f.x, py = (float)y + f.y;
-  inside = px >= 0.f && px <= (float)(W - 1) && py >= 0.f && py <= (float)(H - 1);
+  inside = JR_INSIDE_FRAME(px, py, H, W);
   const float pxc = fminf(px >= 0.f ? px : 0.f, (float)(W - 1));    // NaN -> 0
   const float pyc = fminf(py >= 0.f ? py : 0.f, (float)(H - 1));
   const float x0f = floorf(pxc), y0f = floorf(pyc);
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(BLOCK) void census_loss_kernel(const float* __restr
       if (i >= N) break;
       const float2 f = *(const float2*)(pred + 2 * ((long)i * P + p));
       const float px = (float)x + f.x, py = (float)y + f.y;
-      const bool inside = px >= 0.f && px <= (float)(W - 1) && py >= 0.f && py <= (float)(H - 1);
+      const bool inside = JR_INSIDE_FRAME(px, py, H, W);
       const bool valid = inside && geom;
       const float hh = h[k] + C_H;
       const float cen = powf(hh, 0.4f);
@@ -198,25 +198,11 @@ __global__ __launch_bounds__(BLOCK) void census_loss_kernel(const float* __restr
       coef[(long)i * P + p] = (on && valid) ? 0.4f * cen / hh : 0.f;
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < Q; ++k) {
-    float v = acc[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) red[k][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < ITERS && i0 + (int)threadIdx.x < N) {
-    const int k = threadIdx.x, i = i0 + k;
-    auto total = [&](int q) { return ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3]; };
-    float4 row;
-    row.x = total(k);
-    row.y = total(ITERS + k);
-    row.z = total(2 * ITERS + k);
-    row.w = i == N - 1 ? total(3 * ITERS) : 0.f;
-    *(float4*)(part + 4 * ((long)blockIdx.x * N + i)) = row;
-  }
+  block_sums(acc, red);
+  int k, i;
+  if (owns_row(i0, N, k, i))
+    store_row(part, N, i, row_total(red[k]), row_total(red[ITERS + k]), row_total(red[2 * ITERS + k]),
+              i == N - 1 ? row_total(red[3 * ITERS]) : 0.f);
 }
 
 // scale fp32 [N]; grad fp32 [N][P][2]
@@ -283,17 +269,13 @@ __global__ __launch_bounds__(BLOCK) void census_loss_bwd_kernel(const float* __r
   }
 }
 
-inline bool sizes_ok(int B, int H, int W, int N) {
-  return B >= 1 && H >= 1 && W >= 1 && N >= 1 && N <= MAX_N && (long)B * H * W <= 0x7fffffffL;
-}
-
 }  // namespace
 
 extern "C" long jr_census_tiles(int B, int H, int W) { return (long)B * ((H + TY - 1) / TY) * ((W + TX - 1) / TX); }
 
 extern "C" int jr_census_gray(const float* img1, const float* img2, float* gray, int B, int H, int W, hipStream_t stream) {
+  if (!sizes_ok(B, H, W, 1) || !img1 || !img2 || !gray) return (int)hipErrorInvalidValue;
   const long P = (long)B * H * W;
-  if (B < 1 || H < 1 || W < 1 || P > 0x7fffffffL || !img1 || !img2 || !gray) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(census_gray_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream, img1, img2, gray, P);
   return (int)hipGetLastError();
 }
@@ -302,7 +284,7 @@ extern "C" int jr_census_loss(const float* pred, const float* gray, const float*
                               float* coef, int B, int H, int W, int N, hipStream_t stream) {
   if (!sizes_ok(B, H, W, N) || !pred || !gray || !prm || !part || !coef) return (int)hipErrorInvalidValue;
   const int tiles_x = (W + TX - 1) / TX, tiles_y = (H + TY - 1) / TY;
-  hipLaunchKernelGGL(census_loss_kernel, dim3((unsigned)jr_census_tiles(B, H, W), (unsigned)((N + ITERS - 1) / ITERS)),
+  hipLaunchKernelGGL(census_loss_kernel, dim3((unsigned)jr_census_tiles(B, H, W), iter_groups(N)),
                      dim3(BLOCK), 0, stream, pred, gray, mask, prm, part, coef, H, W, (long)B * H * W, N, tiles_x, tiles_y);
   return (int)hipGetLastError();
 }
@@ -311,7 +293,7 @@ extern "C" int jr_census_loss_bwd(const float* pred, const float* gray, const fl
                                   int B, int H, int W, int N, int add, hipStream_t stream) {
   if (!sizes_ok(B, H, W, N) || !pred || !gray || !coef || !scale || !grad) return (int)hipErrorInvalidValue;
   const int tiles_x = (W + TX - 1) / TX, tiles_y = (H + TY - 1) / TY;
-  hipLaunchKernelGGL(census_loss_bwd_kernel, dim3((unsigned)jr_census_tiles(B, H, W), (unsigned)((N + ITERS - 1) / ITERS)),
+  hipLaunchKernelGGL(census_loss_bwd_kernel, dim3((unsigned)jr_census_tiles(B, H, W), iter_groups(N)),
                      dim3(BLOCK), 0, stream, pred, gray, coef, scale, grad, H, W, (long)B * H * W, N, tiles_x, tiles_y, add);
   return (int)hipGetLastError();
 }

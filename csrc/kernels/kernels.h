@@ -361,6 +361,10 @@ int jr_augment_gather(int layout, const void* img1, const void* img2, const floa
 // [B][6] is written, acc fp64 [8] is added to.  Two launches; no atomics, no memset.
 int jr_flow_metrics(const float* pred, const float* gt, const void* valid, const int* sizes, double* part,
                     double* rows, double* acc, int B, int Hp, int Wp, int Hg, int Wg, int NB, hipStream_t stream);
+// The label-free losses below (unsup.hip, census.hip, selfsup.hip) share one scaffold, loss_common.h: the
+// limits 1 <= N <= 32 and fewer than 2^31 pixels, 4 iterations per block, the robust penalty, the "inside
+// the frame" test and the reduction (thread -> wave -> block in a fixed order, no atomics) that leaves one
+// 16-byte row part[block or tile][i][4] per iteration; the caller adds the rows up.
 // Label-free training loss (unsup.hip; train/unsup.py:unsup_loss_reference).  pred fp32 [N][B][H][W][2]
 // (8-byte aligned), img1 / img2 fp32 [B][H][W][3], mask (optional) fp32 [B][H][W], prm fp32 [4] = (eps,
 // eps_s, edge_kappa, out_penalty) on the device; 1 <= N <= 32, B * H * W < 2^31.  jr_unsup_loss writes

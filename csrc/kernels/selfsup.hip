@@ -23,24 +23,24 @@
 //     store of grad) when every iteration's window is 16-byte aligned and holds an even number of
 //     pixels; 8-byte loads and stores with a tail pixel otherwise,
 //     grid.y over groups of ITERS iterations so that target and weight are read once per group.
-//     Loss: grid-stride, thread -> wave (shuffles) -> 4 LDS words -> one row part[block][i][4]:
+//     Loss: grid-stride, reduced by loss_common.h to one row part[block][i][4]:
 //     (sum of term, the same for i = N - 1 else 0, sum of weight for i = N - 1, count of weight > 0
 //     for i = N - 1).  Backward: grad fp32 [N][B][H][W][2] (contiguous, every element written) =
 //     scale[i] * weight * d / sqrt(d^2 + eps^2) per component where weight > 0, 0 * pred elsewhere.
 #include <algorithm>
 
-#include "common.h"
 #include "kernels.h"
 
+// above loss_common.h: its rho and drho stay uncontracted here, as everything below
 #pragma clang fp contract(off)
+
+#include "loss_common.h"
 
 namespace {
 
+using namespace loss;
+
 constexpr int CR_BLOCK = 64;  // threads per block of crop_resize: 256 pixels of a row
-constexpr int BLOCK = 256;    // threads per block of the loss kernels
-constexpr int ITERS = 4;      // iterations per block
-constexpr int GRID_X = 1024;  // blocks per iteration group of the loss kernel
-constexpr int MAX_N = 32;
 
 // One axis of crop_resize: the two tap indices inside the crop and the weight of the second.
 __device__ __forceinline__ void axis(int u, float r, int nc, int& i0, int& i1, float& w) {
@@ -94,9 +94,6 @@ __global__ __launch_bounds__(CR_BLOCK) void crop_resize_kernel(const float* __re
   }
   for (int k = 0; k < C * n; ++k) o[k] = v[k];
 }
-
-__device__ __forceinline__ float rho(float d, float e2) { return sqrtf(d * d + e2); }
-__device__ __forceinline__ float drho(float d, float e2) { return d / sqrtf(d * d + e2); }
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -176,25 +173,12 @@ __global__ __launch_bounds__(BLOCK) void selfsup_loss_kernel(const float* __rest
       acc[ITERS + 1] += (on[0] ? 1.f : 0.f) + (on[1] ? 1.f : 0.f);
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < Q; ++k) {
-    float v = acc[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) red[k][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < ITERS && i0 + (int)threadIdx.x < N) {
-    const int k = threadIdx.x, i = i0 + k;
-    auto total = [&](int q) { return ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3]; };
+  block_sums(acc, red);
+  int k, i;
+  if (owns_row(i0, N, k, i)) {
     const bool last = i == N - 1;
-    f32x4 row;
-    row.x = total(k);
-    row.y = last ? row.x : 0.f;
-    row.z = last ? total(ITERS) : 0.f;
-    row.w = last ? total(ITERS + 1) : 0.f;
-    *(f32x4*)(part + 4 * ((long)blockIdx.x * N + i)) = row;
+    const float sum = row_total(red[k]);
+    store_row(part, N, i, sum, last ? sum : 0.f, last ? row_total(red[ITERS]) : 0.f, last ? row_total(red[ITERS + 1]) : 0.f);
   }
 }
 
@@ -249,8 +233,7 @@ __global__ __launch_bounds__(BLOCK) void selfsup_loss_bwd_kernel(const float* __
 }
 
 inline bool loss_sizes_ok(int B, int H, int W, int N, int Btot, int B0) {
-  return B >= 1 && H >= 1 && W >= 1 && N >= 1 && N <= MAX_N && B0 >= 0 && Btot >= 1 && B0 <= Btot - B &&
-         (long)Btot * H * W <= 0x7fffffffL;
+  return sizes_ok(Btot, H, W, N) && B >= 1 && B0 >= 0 && B0 <= Btot - B;
 }
 
 // The 16-byte form: every iteration's window starts 16-byte aligned and holds an even number of pixels (no
@@ -284,7 +267,7 @@ extern "C" int jr_selfsup_loss(const float* pred, const float* target, const flo
   if (!loss_sizes_ok(B, H, W, N, Btot, B0) || !pred || !target || !prm || !part) return (int)hipErrorInvalidValue;
   const long HW = (long)H * W, P = B * HW, it_stride = Btot * HW, off = B0 * HW;
   const float* win = pred + 2 * off;
-  const dim3 grid((unsigned)jr_selfsup_loss_blocks(P), (unsigned)((N + ITERS - 1) / ITERS));
+  const dim3 grid((unsigned)jr_selfsup_loss_blocks(P), iter_groups(N));
   if (loss_vec(pred, target, weight, nullptr, P, it_stride, off))
     hipLaunchKernelGGL(selfsup_loss_kernel<true>, grid, dim3(BLOCK), 0, stream, win, target, weight, prm, part, P, it_stride, N);
   else
@@ -298,7 +281,7 @@ extern "C" int jr_selfsup_loss_bwd(const float* pred, const float* target, const
   if (!loss_sizes_ok(B, H, W, N, Btot, B0) || !pred || !target || !prm || !scale || !grad) return (int)hipErrorInvalidValue;
   const long HW = (long)H * W, P = B * HW, it_stride = Btot * HW, off = B0 * HW;
   const float* win = pred + 2 * off;
-  const dim3 grid((unsigned)(((P + 1) / 2 + BLOCK - 1) / BLOCK), (unsigned)((N + ITERS - 1) / ITERS));
+  const dim3 grid((unsigned)(((P + 1) / 2 + BLOCK - 1) / BLOCK), iter_groups(N));
   if (loss_vec(pred, target, weight, grad, P, it_stride, off))
     hipLaunchKernelGGL(selfsup_loss_bwd_kernel<true>, grid, dim3(BLOCK), 0, stream, win, target, weight, prm, scale, grad, P,
                        it_stride, N);

@@ -6,8 +6,8 @@
 // "taps" decomposition the forward flow head uses (flowhead.hip).
 #include <algorithm>
 
-#include "common.h"
 #include "kernels.h"
+#include "loss_common.h"
 
 namespace {
 
@@ -209,17 +209,8 @@ __global__ __launch_bounds__(256) void seq_loss_kernel(const float* __restrict__
       }
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < LOSS_MAX_N + 5; ++k) {
-    float v = acc[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) red[k][wave] = v;
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < LOSS_MAX_N + 5; k += 256)
-    part[(long)blockIdx.x * (LOSS_MAX_N + 5) + k] = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
+  loss::block_sums(acc, red);   // (rows of 8 words, of which the 4 waves use 4)
+  for (int k = threadIdx.x; k < LOSS_MAX_N + 5; k += 256) part[(long)blockIdx.x * (LOSS_MAX_N + 5) + k] = loss::row_total(red[k]);
 }
 
 // grad[i][p] = scale_i * valid(p) * sign(pred_i(p) - gt(p))   (scale_i = g_out * gamma^(N-1-i) / (2P))

@@ -20,24 +20,22 @@
 // 3 * 32 + 1.  The flow of the right / lower (and, backward, left / upper) neighbour is a
 // coalesced read of rows that the neighbouring threads read as their own; the four texels of
 // image 2 are 12-byte gathers through the caches.
-//   1. unsup_loss_kernel: grid-stride over the pixels (GRID_X blocks at most); thread -> wave
-//      (shuffles) -> block (4 LDS words per quantity) -> one row part[block][i][4] per iteration:
-//      (sum of mask * pix, smoothness sum, masked pixels that are not inside, sum of pix over the
-//      inside masked pixels -- the last iteration only, 0 elsewhere).  A block counts at most
-//      2^31 / GRID_X pixels, which fp32 holds exactly.
+//   1. unsup_loss_kernel: grid-stride over the pixels (GRID_X blocks at most), reduced by
+//      loss_common.h to one row part[block][i][4] per iteration: (sum of mask * pix, smoothness sum,
+//      masked pixels that are not inside, sum of pix over the inside masked pixels -- the last
+//      iteration only, 0 elsewhere).
 //   2. unsup_loss_bwd_kernel: grad fp32 [N][B][H][W][2] as a gather: scale[i][0] * mask *
 //      sum_c rho'(d_c) / 3 * (dv_c/dpx, dv_c/dpy) inside, plus scale[i][1] times the
 //      four-neighbour stencil -a_x(y,x) rho_s'(D at x) + a_x(y,x-1) rho_s'(D at x-1) and the same
 //      in y; rho'(d) = d / sqrt(d^2 + eps^2).
-#include "common.h"
+#include <algorithm>
+
 #include "kernels.h"
+#include "loss_common.h"
 
 namespace {
 
-constexpr int BLOCK = 256;    // threads per block
-constexpr int ITERS = 4;      // iterations per block
-constexpr int GRID_X = 1024;  // blocks per iteration group of the loss kernel: GRID_X * BLOCK pixels per round
-constexpr int MAX_N = 32;
+using namespace loss;
 
 __device__ __forceinline__ float2 ld2(const float* p) { return *(const float2*)p; }
 
@@ -47,15 +45,12 @@ __device__ __forceinline__ float edge_weight(const float* __restrict__ a, const 
   return expf(-kappa * m);
 }
 
-__device__ __forceinline__ float rho(float d, float e2) { return sqrtf(d * d + e2); }
-__device__ __forceinline__ float drho(float d, float e2) { return d / sqrtf(d * d + e2); }
-
 // Steps 1 and 2 at pixel (y, x) with flow f: false where the landing point is outside the frame
 // (nothing else is written then); o[4] are the float offsets of the texels 00, 01, 10, 11 inside
 // one [H][W][3] image.
 __device__ __forceinline__ bool landing(float2 f, int y, int x, int H, int W, float& wx, float& wy, long* o) {
   const float px = (float)x + f.x, py = (float)y + f.y;
-  if (!(px >= 0.f && px <= (float)(W - 1) && py >= 0.f && py <= (float)(H - 1))) return false;
+  if (!JR_INSIDE_FRAME(px, py, H, W)) return false;
   const float x0f = floorf(px), y0f = floorf(py);
   wx = px - x0f;
   wy = py - y0f;
@@ -132,25 +127,11 @@ __global__ __launch_bounds__(BLOCK) void unsup_loss_kernel(const float* __restri
       if (i == N - 1 && on && in) acc[3 * ITERS] += pix;
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < Q; ++k) {
-    float v = acc[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) red[k][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < ITERS && i0 + (int)threadIdx.x < N) {
-    const int k = threadIdx.x, i = i0 + k;
-    auto total = [&](int q) { return ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3]; };
-    float4 row;
-    row.x = total(k);
-    row.y = total(ITERS + k);
-    row.z = total(2 * ITERS + k);
-    row.w = i == N - 1 ? total(3 * ITERS) : 0.f;
-    *(float4*)(part + 4 * ((long)blockIdx.x * N + i)) = row;
-  }
+  block_sums(acc, red);
+  int k, i;
+  if (owns_row(i0, N, k, i))
+    store_row(part, N, i, row_total(red[k]), row_total(red[ITERS + k]), row_total(red[2 * ITERS + k]),
+              i == N - 1 ? row_total(red[3 * ITERS]) : 0.f);
 }
 
 // scale fp32 [N][2] = (photometric, smoothness); grad fp32 [N][P][2]
@@ -233,9 +214,8 @@ extern "C" int jr_unsup_loss_blocks(long P) { return (int)std::min<long>(GRID_X,
 extern "C" int jr_unsup_loss(const float* pred, const float* img1, const float* img2, const float* mask,
                              const float* prm, float* part, int B, int H, int W, int N, hipStream_t stream) {
   const long P = (long)B * H * W;
-  if (B < 1 || H < 1 || W < 1 || N < 1 || N > MAX_N || P > 0x7fffffffL || !pred || !img1 || !img2 || !prm || !part)
-    return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(unsup_loss_kernel, dim3((unsigned)jr_unsup_loss_blocks(P), (unsigned)((N + ITERS - 1) / ITERS)),
+  if (!sizes_ok(B, H, W, N) || !pred || !img1 || !img2 || !prm || !part) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(unsup_loss_kernel, dim3((unsigned)jr_unsup_loss_blocks(P), iter_groups(N)),
                      dim3(BLOCK), 0, stream, pred, img1, img2, mask, prm, part, H, W, P, N);
   return (int)hipGetLastError();
 }
@@ -244,10 +224,8 @@ extern "C" int jr_unsup_loss_bwd(const float* pred, const float* img1, const flo
                                  const float* prm, const float* scale, float* grad, int B, int H, int W, int N,
                                  hipStream_t stream) {
   const long P = (long)B * H * W;
-  if (B < 1 || H < 1 || W < 1 || N < 1 || N > MAX_N || P > 0x7fffffffL || !pred || !img1 || !img2 || !prm || !scale ||
-      !grad)
-    return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(unsup_loss_bwd_kernel, dim3((unsigned)((P + BLOCK - 1) / BLOCK), (unsigned)((N + ITERS - 1) / ITERS)),
+  if (!sizes_ok(B, H, W, N) || !pred || !img1 || !img2 || !prm || !scale || !grad) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(unsup_loss_bwd_kernel, dim3((unsigned)((P + BLOCK - 1) / BLOCK), iter_groups(N)),
                      dim3(BLOCK), 0, stream, pred, img1, img2, mask, prm, scale, grad, H, W, P, N);
   return (int)hipGetLastError();
 }

@@ -55,6 +55,41 @@ static void check_f32(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
+// The operand checks of the loss, occlusion, augmentation and metrics ops; every message begins "<op>: ".
+// N predictions of B * H * W = P pixels (b names B in the message) -> P
+static int64_t check_loss_sizes(const std::string& op, int64_t N, int64_t B, int64_t H, int64_t W, const char* b = "B") {
+  TORCH_CHECK(N >= 1 && N <= 32, op, ": 1..32 predictions, got ", N);
+  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && B <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX && B * H <= INT32_MAX &&
+                  B * H * W <= INT32_MAX, op, ": sizes (", b, " * H * W must be below 2^31)");
+  return B * H * W;
+}
+// a contiguous fp32 device tensor of exactly n elements, which the message spells as `layout`, aligned to `align` bytes
+static void check_f32_n(const std::string& op, const char* name, const at::Tensor& t, int64_t n, const char* layout,
+                        int align = 4) {
+  check_f32(t, (op + ": " + name).c_str());
+  TORCH_CHECK(t.numel() == n, op, ": ", name, " must hold ", layout, " = ", n, " elements");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % align == 0, op, ": ", name, " must be ", align, "-byte aligned");
+}
+static void check_f32_opt(const std::string& op, const char* name, const at::Tensor& t, int64_t n, const char* layout,
+                          int align = 4) {
+  if (t.defined()) check_f32_n(op, name, t, n, layout, align);
+}
+static bool overlaps(const at::Tensor& a, const at::Tensor& b) {
+  const char *a0 = (const char*)a.data_ptr(), *b0 = (const char*)b.data_ptr();
+  return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
+}
+// out shares no byte with any of the (defined) other operands
+static void check_no_alias(const std::string& op, const char* what, const at::Tensor& out, const std::vector<at::Tensor>& ins) {
+  for (const at::Tensor& v : ins) TORCH_CHECK(!v.defined() || !overlaps(out, v), op, ": ", what, " aliases another operand");
+}
+static void check_one_device(const std::string& op, const at::Tensor& out, const std::vector<at::Tensor>& ins) {
+  for (const at::Tensor& v : ins) TORCH_CHECK(!v.defined() || v.device() == out.device(), op, ": operands on several devices");
+}
+static void hold(std::vector<at::Tensor>& keep, const std::vector<at::Tensor>& ts) {
+  for (const at::Tensor& v : ts)
+    if (v.defined()) keep.push_back(v);
+}
+
 // ----------------------------------------------------------------------- conv
 // t = [x, w, bias, y, y2, res, h32, zbuf, coords, flow32, y3, bmap(, tapw)]
 // i = [N, H, W, x_coff, cin8, KH, KW, SH, SW, PH, PW, cout, act, split,
@@ -1809,16 +1844,12 @@ static Launch make_fb_check(const TList& t, const IList& i, std::vector<at::Tens
               "fb_check: the window (H0, W0, top, left) must lie inside the map");
   const int64_t M = (int64_t)B * H * W;
   auto aligned = [](const at::Tensor& v) { return reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0; };
-  auto overlap = [](const at::Tensor& a, const at::Tensor& b) {
-    const char *a0 = (const char*)a.data_ptr(), *b0 = (const char*)b.data_ptr();
-    return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
-  };
   TORCH_CHECK(occ.defined() && occ.is_cuda() && occ.scalar_type() == at::kByte && occ.is_contiguous() &&
                   occ.numel() == 2 * M && aligned(occ), "fb_check: occ must be a contiguous device uint8 [2][B][H][W], 16-byte aligned");
   if (err.defined()) {
     check_f32(err, "fb_check: err");
     TORCH_CHECK(err.numel() == 2 * M && aligned(err), "fb_check: err [2][B][H][W], 16-byte aligned");
-    TORCH_CHECK(!overlap(err, occ), "fb_check: err aliases occ");
+    TORCH_CHECK(!overlaps(err, occ), "fb_check: err aliases occ");
   }
   check_f32(thr, "fb_check: thr");
   TORCH_CHECK(thr.numel() == 2, "fb_check: thr must hold [alpha, beta]");
@@ -1837,8 +1868,8 @@ static Launch make_fb_check(const TList& t, const IList& i, std::vector<at::Tens
     TORCH_CHECK(fw.numel() == 2 * M && bw.numel() == 2 * M, "fb_check: flows [B][H][W][2]");
     TORCH_CHECK(aligned(fw) && aligned(bw), "fb_check: flows 16-byte aligned");
     for (const at::Tensor* f : {&fw, &bw}) {
-      TORCH_CHECK(!overlap(occ, *f), "fb_check: occ aliases a flow");
-      TORCH_CHECK(!err.defined() || !overlap(err, *f), "fb_check: err aliases a flow");
+      TORCH_CHECK(!overlaps(occ, *f), "fb_check: occ aliases a flow");
+      TORCH_CHECK(!err.defined() || !overlaps(err, *f), "fb_check: err aliases a flow");
     }
     keep.push_back(fw); keep.push_back(bw);
   }
@@ -1872,10 +1903,6 @@ static Launch make_warp_frames(const TList& t, const IList& i, std::vector<at::T
   TORCH_CHECK(H0 >= 1 && W0 >= 1 && top >= 0 && left >= 0 && top + H0 <= H && left + W0 <= W,
               "warp_frames: the window (H0, W0, top, left) must lie inside the map");
   const int64_t M = (int64_t)B * H * W, F = (int64_t)B * H0 * W0 * 3;
-  auto overlap = [](const at::Tensor& a, const at::Tensor& b) {
-    const char *a0 = (const char*)a.data_ptr(), *b0 = (const char*)b.data_ptr();
-    return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
-  };
   auto is_frames = [&](const at::Tensor& v, int64_t n) {
     return v.defined() && v.is_cuda() && v.scalar_type() == at::kByte && v.is_contiguous() && v.numel() == n;
   };
@@ -1922,10 +1949,10 @@ static Launch make_warp_frames(const TList& t, const IList& i, std::vector<at::T
     }
   }
   for (const at::Tensor& v : inputs) {
-    TORCH_CHECK(!overlap(warped, v), "warp_frames: warped aliases an input");
-    TORCH_CHECK(!photo.defined() || !overlap(photo, v), "warp_frames: photo aliases an input");
+    TORCH_CHECK(!overlaps(warped, v), "warp_frames: warped aliases an input");
+    TORCH_CHECK(!photo.defined() || !overlaps(photo, v), "warp_frames: photo aliases an input");
   }
-  TORCH_CHECK(!photo.defined() || !overlap(photo, warped), "warp_frames: photo aliases warped");
+  TORCH_CHECK(!photo.defined() || !overlaps(photo, warped), "warp_frames: photo aliases warped");
   for (const at::Tensor& v : inputs) keep.push_back(v);
   keep.push_back(warped);
   if (photo.defined()) keep.push_back(photo);
@@ -1967,22 +1994,16 @@ static void check_augment_sums(const at::Tensor& sums, int64_t B, const char* op
   TORCH_CHECK(sums.defined() && sums.is_cuda() && sums.scalar_type() == at::kInt && sums.is_contiguous() &&
                   sums.numel() == 6 * B, op, ": sums must be a contiguous device int32 [2][B][3]");
 }
-static bool augment_overlap(const at::Tensor& a, const at::Tensor& b) {
-  const char *a0 = (const char*)a.data_ptr(), *b0 = (const char*)b.data_ptr();
-  return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
-}
 // the four outputs of a gather: fp32 [B][h][w][3 | 3 | 2 | 1], 16-byte aligned, aliasing no input and no other output
-static void check_augment_outputs(const std::string& op, std::array<const at::Tensor*, 4> outs,
-                                  const std::vector<const at::Tensor*>& ins, int64_t B, int64_t h, int64_t w) {
+static void check_augment_outputs(const std::string& op, std::array<const at::Tensor*, 4> outs, std::vector<at::Tensor> others,
+                                  int64_t B, int64_t h, int64_t w) {
   const int64_t ch[4] = {3, 3, 2, 1};
-  const char* what[4] = {": image1 out", ": image2 out", ": flow out", ": valid out"};
+  const char* what[4] = {"image1 out", "image2 out", "flow out", "valid out"};
+  const char* layout[4] = {"[B][h][w][3]", "[B][h][w][3]", "[B][h][w][2]", "[B][h][w]"};
   for (int k = 0; k < 4; ++k) {
-    const std::string name = op + what[k];
-    check_f32(*outs[k], name.c_str());
-    TORCH_CHECK(outs[k]->numel() == B * h * w * ch[k] && reinterpret_cast<uintptr_t>(outs[k]->data_ptr()) % 16 == 0,
-                name, " must be [B][h][w][", ch[k], "], 16-byte aligned");
-    for (const at::Tensor* in : ins) TORCH_CHECK(!augment_overlap(*outs[k], *in), name, " aliases an input");
-    for (int j = 0; j < k; ++j) TORCH_CHECK(!augment_overlap(*outs[k], *outs[j]), name, " aliases another output");
+    check_f32_n(op, what[k], *outs[k], B * h * w * ch[k], layout[k], 16);
+    check_no_alias(op, what[k], *outs[k], others);
+    others.push_back(*outs[k]);
   }
 }
 static void check_augment_records(const at::Tensor& params, int64_t B, int64_t words, const char* op) {
@@ -1997,10 +2018,8 @@ static Launch make_augment_sums(const AugmentLayout& L, const TList& t, const IL
   check_augment_frames(a, b, B, g0, g1, L.sums_op);
   if (L.sums_records) check_augment_records(params, B, L.words, L.sums_op);
   check_augment_sums(sums, B, L.sums_op);
-  for (const at::Tensor* in : {&a, &b, &params})
-    TORCH_CHECK(!in->defined() || !augment_overlap(sums, *in), L.sums_op, ": sums aliases an input");
-  for (auto& v : {a, b, params, sums})
-    if (v.defined()) keep.push_back(v);
+  check_no_alias(L.sums_op, "sums", sums, {a, b, params});
+  hold(keep, {a, b, params, sums});
   const void *ap = a.data_ptr(), *bp = b.data_ptr();
   const int* pp = (const int*)ptr(params);
   int* sp = sums.data_ptr<int>();
@@ -2022,16 +2041,16 @@ static Launch make_augment_gather(const AugmentLayout& L, const TList& t, const 
   check_f32(flow, (op + ": flow").c_str());
   TORCH_CHECK(flow.numel() == B * g0 * g1 * 2 && reinterpret_cast<uintptr_t>(flow.data_ptr()) % 16 == 0, op, ": flow ",
               L.dims, "[2], 16-byte aligned");
-  std::vector<const at::Tensor*> ins = {&a, &b, &flow, &params, &sums};
+  std::vector<at::Tensor> ins = {a, b, flow, params, sums};
   if (L.valid) {
     TORCH_CHECK(vin.defined() && vin.is_cuda() && vin.scalar_type() == at::kByte && vin.is_contiguous() &&
                     vin.numel() == B * g0 * g1, op, ": valid must be a contiguous device uint8 ", L.dims);
-    ins.push_back(&vin);
+    ins.push_back(vin);
   }
   check_augment_records(params, B, L.words, L.op);
   check_augment_outputs(op, {&o1, &o2, &of, &ov}, ins, B, h, w);
-  for (const at::Tensor* v : ins) keep.push_back(*v);
-  for (auto& v : {o1, o2, of, ov}) keep.push_back(v);
+  hold(keep, ins);
+  hold(keep, {o1, o2, of, ov});
   const void *ap = a.data_ptr(), *bp = b.data_ptr(), *vp = ptr(vin);
   const float* fp = flow.data_ptr<float>();
   const int *pp = params.data_ptr<int>(), *sp = sums.data_ptr<int>();
@@ -2062,20 +2081,21 @@ static Launch make_flow_metrics(const TList& t, const IList& i, std::vector<at::
   TORCH_CHECK(sizes.defined() && sizes.is_cuda() && sizes.scalar_type() == at::kInt && sizes.is_contiguous() &&
                   sizes.numel() == 2 * B, "flow_metrics: sizes must be a contiguous device int32 [B][2]");
   const int64_t need[3] = {B * NB * 2, B * 6, 8};
-  const char* what[3] = {"flow_metrics: part", "flow_metrics: rows", "flow_metrics: acc"};
+  const char* what[3] = {"part", "rows", "acc"};
   const at::Tensor* out[3] = {&part, &rows, &acc};
+  std::vector<at::Tensor> others = {pred, gt, valid, sizes};
   for (int k = 0; k < 3; ++k) {
     const at::Tensor& v = *out[k];
     TORCH_CHECK(v.defined() && v.is_cuda() && v.scalar_type() == at::kDouble && v.is_contiguous() &&
-                    (k == 0 ? v.numel() >= need[k] : v.numel() == need[k]), what[k], " must be a contiguous device fp64 of ",
+                    (k == 0 ? v.numel() >= need[k] : v.numel() == need[k]), "flow_metrics: ", what[k],
+                " must be a contiguous device fp64 of ",
                 need[k], " elements");
-    for (const at::Tensor* in : {&pred, &gt, &sizes}) TORCH_CHECK(!augment_overlap(v, *in), what[k], " aliases an input");
-    TORCH_CHECK(!valid.defined() || !augment_overlap(v, valid), what[k], " aliases valid");
-    TORCH_CHECK(k != 0 || reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0, what[k], " must be 16-byte aligned");
-    for (int j = 0; j < k; ++j) TORCH_CHECK(!augment_overlap(v, *out[j]), what[k], " aliases another output");
+    TORCH_CHECK(k != 0 || reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0, "flow_metrics: ", what[k],
+                " must be 16-byte aligned");
+    check_no_alias("flow_metrics", what[k], v, others);
+    others.push_back(v);
   }
-  for (auto& v : {pred, gt, valid, sizes, part, rows, acc})
-    if (v.defined()) keep.push_back(v);
+  hold(keep, others);
   const float *pp = pred.data_ptr<float>(), *gp = gt.data_ptr<float>();
   const void* vp = ptr(valid);
   const int* sp = sizes.data_ptr<int>();
@@ -2095,40 +2115,22 @@ static Launch make_unsup(const TList& t, const IList& i, std::vector<at::Tensor>
   at::Tensor pred = opt(t, 0), img1 = opt(t, 1), img2 = opt(t, 2), mask = opt(t, 3), prm = opt(t, 4);
   at::Tensor scale = bwd ? opt(t, 5) : at::Tensor(), out = opt(t, bwd ? 6 : 5);
   const int64_t B = i[0], H = i[1], W = i[2], N = i[3];
-  TORCH_CHECK(N >= 1 && N <= 32, op, ": 1..32 predictions, got ", N);
-  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && B <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX &&
-                  B * H <= INT32_MAX && B * H * W <= INT32_MAX, op, ": sizes (B * H * W must be below 2^31)");
-  const int64_t P = B * H * W;
-  const std::pair<const at::Tensor*, const char*> f32s[] = {{&pred, ": pred"}, {&img1, ": image1"}, {&img2, ": image2"},
-                                                             {&prm, ": prm"}, {&out, bwd ? ": grad" : ": part"}};
-  for (const auto& v : f32s) check_f32(*v.first, (op + v.second).c_str());
-  TORCH_CHECK(pred.numel() == N * P * 2, op, ": pred must hold [N][B][H][W][2] = ", N * P * 2, " elements");
-  TORCH_CHECK(img1.numel() == P * 3 && img2.numel() == P * 3, op, ": image1 and image2 must hold [B][H][W][3] = ", P * 3,
-              " elements");
-  TORCH_CHECK(prm.numel() == 4, op, ": prm must hold (eps, eps_s, edge_kappa, out_penalty)");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(pred.data_ptr()) % 8 == 0, op, ": pred must be 8-byte aligned");
-  std::vector<at::Tensor> inputs = {pred, img1, img2, prm};
-  if (mask.defined()) {
-    check_f32(mask, (op + ": mask").c_str());
-    TORCH_CHECK(mask.numel() == P, op, ": mask must hold [B][H][W] = ", P, " elements");
-    inputs.push_back(mask);
-  }
+  const int64_t P = check_loss_sizes(op, N, B, H, W);
+  check_f32_n(op, "pred", pred, N * P * 2, "[N][B][H][W][2]", 8);
+  check_f32_n(op, "image1", img1, P * 3, "[B][H][W][3]");
+  check_f32_n(op, "image2", img2, P * 3, "[B][H][W][3]");
+  check_f32_opt(op, "mask", mask, P, "[B][H][W]");
+  check_f32_n(op, "prm", prm, 4, "(eps, eps_s, edge_kappa, out_penalty)");
   if (bwd) {
-    check_f32(scale, (op + ": scale").c_str());
-    TORCH_CHECK(scale.numel() == 2 * N, op, ": scale must hold [N][2] = ", 2 * N, " elements");
-    inputs.push_back(scale);
-    TORCH_CHECK(out.numel() == N * P * 2, op, ": grad must hold [N][B][H][W][2] = ", N * P * 2, " elements");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0, op, ": grad must be 8-byte aligned");
+    check_f32_n(op, "scale", scale, 2 * N, "[N][2]");
+    check_f32_n(op, "grad", out, N * P * 2, "[N][B][H][W][2]", 8);
   } else {
-    const int64_t need = (int64_t)jr_unsup_loss_blocks(P) * N * 4;
-    TORCH_CHECK(out.numel() == need, op, ": part must hold [blocks][N][4] = ", need, " elements");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0, op, ": part must be 16-byte aligned");
+    check_f32_n(op, "part", out, (int64_t)jr_unsup_loss_blocks(P) * N * 4, "[blocks][N][4]", 16);
   }
-  for (const at::Tensor& v : inputs) {
-    const char *a0 = (const char*)out.data_ptr(), *b0 = (const char*)v.data_ptr();
-    TORCH_CHECK(!(a0 < b0 + v.nbytes() && b0 < a0 + out.nbytes()), op, bwd ? ": grad" : ": part", " aliases an input");
-    keep.push_back(v);
-  }
+  const std::vector<at::Tensor> inputs = {pred, img1, img2, mask, prm, scale};
+  check_one_device(op, out, inputs);
+  check_no_alias(op, bwd ? "grad" : "part", out, inputs);
+  hold(keep, inputs);
   keep.push_back(out);
   const float *pp = pred.data_ptr<float>(), *p1 = img1.data_ptr<float>(), *p2 = img2.data_ptr<float>();
   const float *mp = (const float*)ptr(mask), *rp = prm.data_ptr<float>(), *sp = (const float*)ptr(scale);
@@ -2145,31 +2147,16 @@ static Launch make_unsup_loss_bwd(const TList& t, const IList& i, std::vector<at
 // i = [B, H, W].  census_loss: t = [pred (fp32 [N][B][H][W][2]), gray, mask? (fp32 [B][H][W]), prm (fp32 [4]),
 // part (fp32 [tiles][N][4]), coef (fp32 [N][B][H][W])], i = [B, H, W, N].  census_loss_bwd: t = [pred, gray,
 // coef, scale (fp32 [N]), grad (fp32 like pred)], i = [B, H, W, N, add (0: write, 1: add into grad)].
-static int64_t census_sizes(const std::string& op, const IList& i, bool with_n) {
-  const int64_t B = i[0], H = i[1], W = i[2];
-  if (with_n) TORCH_CHECK(i[3] >= 1 && i[3] <= 32, op, ": 1..32 predictions, got ", i[3]);
-  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && B <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX && B * H <= INT32_MAX &&
-                  B * H * W <= INT32_MAX, op, ": sizes (B * H * W must be below 2^31)");
-  return B * H * W;
-}
-static void census_no_alias(const std::string& op, const char* what, const at::Tensor& out, const std::vector<at::Tensor>& ins) {
-  for (const at::Tensor& v : ins) {
-    const char *a0 = (const char*)out.data_ptr(), *b0 = (const char*)v.data_ptr();
-    TORCH_CHECK(!(a0 < b0 + v.nbytes() && b0 < a0 + out.nbytes()), op, what, " aliases another operand");
-  }
-}
 static Launch make_census_gray(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   const std::string op = "census_gray";
   at::Tensor img1 = opt(t, 0), img2 = opt(t, 1), gray = opt(t, 2);
-  const int64_t P = census_sizes(op, i, false);
-  check_f32(img1, "census_gray: image1");
-  check_f32(img2, "census_gray: image2");
-  check_f32(gray, "census_gray: gray");
-  TORCH_CHECK(img1.numel() == P * 3 && img2.numel() == P * 3, op, ": image1 and image2 must hold [B][H][W][3] = ", P * 3,
-              " elements");
-  TORCH_CHECK(gray.numel() == 2 * P, op, ": gray must hold [2][B][H][W] = ", 2 * P, " elements");
-  census_no_alias(op, ": gray", gray, {img1, img2});
-  keep.insert(keep.end(), {img1, img2, gray});
+  const int64_t P = check_loss_sizes(op, 1, i[0], i[1], i[2]);
+  check_f32_n(op, "image1", img1, P * 3, "[B][H][W][3]");
+  check_f32_n(op, "image2", img2, P * 3, "[B][H][W][3]");
+  check_f32_n(op, "gray", gray, 2 * P, "[2][B][H][W]");
+  check_one_device(op, gray, {img1, img2});
+  check_no_alias(op, "gray", gray, {img1, img2});
+  hold(keep, {img1, img2, gray});
   const float *p1 = img1.data_ptr<float>(), *p2 = img2.data_ptr<float>();
   float* gp = gray.data_ptr<float>();
   const int b = (int)i[0], h = (int)i[1], w = (int)i[2];
@@ -2178,29 +2165,17 @@ static Launch make_census_gray(const TList& t, const IList& i, std::vector<at::T
 static Launch make_census_loss(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   const std::string op = "census_loss";
   at::Tensor pred = opt(t, 0), gray = opt(t, 1), mask = opt(t, 2), prm = opt(t, 3), part = opt(t, 4), coef = opt(t, 5);
-  const int64_t P = census_sizes(op, i, true), N = i[3];
-  const std::pair<const at::Tensor*, const char*> f32s[] = {{&pred, ": pred"}, {&gray, ": gray"}, {&prm, ": prm"},
-                                                             {&part, ": part"}, {&coef, ": coef"}};
-  for (const auto& v : f32s) check_f32(*v.first, (op + v.second).c_str());
-  TORCH_CHECK(pred.numel() == N * P * 2, op, ": pred must hold [N][B][H][W][2] = ", N * P * 2, " elements");
-  TORCH_CHECK(gray.numel() == 2 * P, op, ": gray must hold [2][B][H][W] = ", 2 * P, " elements");
-  TORCH_CHECK(prm.numel() == 4, op, ": prm must hold (eps, eps_s, edge_kappa, out_penalty)");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(pred.data_ptr()) % 8 == 0, op, ": pred must be 8-byte aligned");
-  std::vector<at::Tensor> inputs = {pred, gray, prm};
-  if (mask.defined()) {
-    check_f32(mask, "census_loss: mask");
-    TORCH_CHECK(mask.numel() == P, op, ": mask must hold [B][H][W] = ", P, " elements");
-    inputs.push_back(mask);
-  }
-  const int64_t need = (int64_t)jr_census_tiles((int)i[0], (int)i[1], (int)i[2]) * N * 4;
-  TORCH_CHECK(part.numel() == need, op, ": part must hold [tiles][N][4] = ", need, " elements");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(part.data_ptr()) % 16 == 0, op, ": part must be 16-byte aligned");
-  TORCH_CHECK(coef.numel() == N * P, op, ": coef must hold [N][B][H][W] = ", N * P, " elements");
-  census_no_alias(op, ": part", part, inputs);
-  inputs.push_back(part);
-  census_no_alias(op, ": coef", coef, inputs);
-  inputs.push_back(coef);
-  keep.insert(keep.end(), inputs.begin(), inputs.end());
+  const int64_t N = i[3], P = check_loss_sizes(op, N, i[0], i[1], i[2]);
+  check_f32_n(op, "pred", pred, N * P * 2, "[N][B][H][W][2]", 8);
+  check_f32_n(op, "gray", gray, 2 * P, "[2][B][H][W]");
+  check_f32_opt(op, "mask", mask, P, "[B][H][W]");
+  check_f32_n(op, "prm", prm, 4, "(eps, eps_s, edge_kappa, out_penalty)");
+  check_f32_n(op, "part", part, jr_census_tiles((int)i[0], (int)i[1], (int)i[2]) * N * 4, "[tiles][N][4]", 16);
+  check_f32_n(op, "coef", coef, N * P, "[N][B][H][W]");
+  check_one_device(op, part, {pred, gray, mask, prm, coef});
+  check_no_alias(op, "part", part, {pred, gray, mask, prm});
+  check_no_alias(op, "coef", coef, {pred, gray, mask, prm, part});
+  hold(keep, {pred, gray, mask, prm, part, coef});
   const float *pp = pred.data_ptr<float>(), *gp = gray.data_ptr<float>(), *mp = (const float*)ptr(mask);
   const float* rp = prm.data_ptr<float>();
   float *op_ = part.data_ptr<float>(), *cp = coef.data_ptr<float>();
@@ -2210,20 +2185,16 @@ static Launch make_census_loss(const TList& t, const IList& i, std::vector<at::T
 static Launch make_census_loss_bwd(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
   const std::string op = "census_loss_bwd";
   at::Tensor pred = opt(t, 0), gray = opt(t, 1), coef = opt(t, 2), scale = opt(t, 3), grad = opt(t, 4);
-  const int64_t P = census_sizes(op, i, true), N = i[3], add = i[4];
+  const int64_t N = i[3], add = i[4], P = check_loss_sizes(op, N, i[0], i[1], i[2]);
   TORCH_CHECK(add == 0 || add == 1, op, ": add must be 0 or 1, got ", add);
-  const std::pair<const at::Tensor*, const char*> f32s[] = {{&pred, ": pred"}, {&gray, ": gray"}, {&coef, ": coef"},
-                                                             {&scale, ": scale"}, {&grad, ": grad"}};
-  for (const auto& v : f32s) check_f32(*v.first, (op + v.second).c_str());
-  TORCH_CHECK(pred.numel() == N * P * 2, op, ": pred must hold [N][B][H][W][2] = ", N * P * 2, " elements");
-  TORCH_CHECK(gray.numel() == 2 * P, op, ": gray must hold [2][B][H][W] = ", 2 * P, " elements");
-  TORCH_CHECK(coef.numel() == N * P, op, ": coef must hold [N][B][H][W] = ", N * P, " elements");
-  TORCH_CHECK(scale.numel() == N, op, ": scale must hold [N] = ", N, " elements");
-  TORCH_CHECK(grad.numel() == N * P * 2, op, ": grad must hold [N][B][H][W][2] = ", N * P * 2, " elements");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(pred.data_ptr()) % 8 == 0, op, ": pred must be 8-byte aligned");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(grad.data_ptr()) % 8 == 0, op, ": grad must be 8-byte aligned");
-  census_no_alias(op, ": grad", grad, {pred, gray, coef, scale});
-  keep.insert(keep.end(), {pred, gray, coef, scale, grad});
+  check_f32_n(op, "pred", pred, N * P * 2, "[N][B][H][W][2]", 8);
+  check_f32_n(op, "gray", gray, 2 * P, "[2][B][H][W]");
+  check_f32_n(op, "coef", coef, N * P, "[N][B][H][W]");
+  check_f32_n(op, "scale", scale, N, "[N]");
+  check_f32_n(op, "grad", grad, N * P * 2, "[N][B][H][W][2]", 8);
+  check_one_device(op, grad, {pred, gray, coef, scale});
+  check_no_alias(op, "grad", grad, {pred, gray, coef, scale});
+  hold(keep, {pred, gray, coef, scale, grad});
   const float *pp = pred.data_ptr<float>(), *gp = gray.data_ptr<float>(), *cp = coef.data_ptr<float>();
   const float* sp = scale.data_ptr<float>();
   float* op_ = grad.data_ptr<float>();
@@ -2333,11 +2304,6 @@ static int64_t range_sizes(const std::string& op, const IList& i) {
   TORCH_CHECK(2 * B <= 65535, op, ": at most 32767 samples, got ", B);
   return B * H * W;
 }
-static void range_flow(const std::string& op, const char* what, const at::Tensor& f, int64_t P) {
-  check_f32(f, (op + what).c_str());
-  TORCH_CHECK(f.numel() == 2 * P && reinterpret_cast<uintptr_t>(f.data_ptr()) % 8 == 0, op, what,
-              " must hold [B][H][W][2] = ", 2 * P, " elements, 8-byte aligned");
-}
 static void range_acc(const std::string& op, const at::Tensor& acc, int64_t n) {
   TORCH_CHECK(acc.defined() && acc.is_cuda() && acc.scalar_type() == at::kInt && acc.is_contiguous() && acc.numel() == n,
               op, ": acc must be a contiguous device int32 tensor of ", n, " elements");
@@ -2346,16 +2312,12 @@ static Launch make_range_splat(const TList& t, const IList& i, std::vector<at::T
   const std::string op = "range_splat";
   at::Tensor fw = opt(t, 0), bw = opt(t, 1), acc = opt(t, 2);
   const int64_t P = range_sizes(op, i);
-  range_flow(op, ": flow_fw", fw, P);
-  if (bw.defined()) {
-    range_flow(op, ": flow_bw", bw, P);
-    TORCH_CHECK(bw.device() == fw.device(), op, ": flow_bw is on another device");
-  }
+  check_f32_n(op, "flow_fw", fw, 2 * P, "[B][H][W][2]", 8);
+  check_f32_opt(op, "flow_bw", bw, 2 * P, "[B][H][W][2]", 8);
   range_acc(op, acc, (bw.defined() ? 2 : 1) * P);
-  TORCH_CHECK(acc.device() == fw.device(), op, ": acc is on another device");
-  census_no_alias(op, ": acc", acc, bw.defined() ? std::vector<at::Tensor>{fw, bw} : std::vector<at::Tensor>{fw});
-  keep.push_back(fw); keep.push_back(acc);
-  if (bw.defined()) keep.push_back(bw);
+  check_one_device(op, acc, {fw, bw});
+  check_no_alias(op, "acc", acc, {fw, bw});
+  hold(keep, {fw, bw, acc});
   const float* fp = fw.data_ptr<float>();
   const float* bp = bw.defined() ? bw.data_ptr<float>() : nullptr;
   int* ap = acc.data_ptr<int>();
@@ -2367,15 +2329,14 @@ static Launch make_range_visible(const TList& t, const IList& i, std::vector<at:
   at::Tensor fw = opt(t, 0), bw = opt(t, 1), acc = opt(t, 2), vis = opt(t, 3);
   const int64_t P = range_sizes(op, i);
   TORCH_CHECK(i[3] >= INT32_MIN && i[3] <= INT32_MAX, op, ": the threshold T must fit an int32");
-  range_flow(op, ": flow_fw", fw, P);
-  range_flow(op, ": flow_bw", bw, P);
+  check_f32_n(op, "flow_fw", fw, 2 * P, "[B][H][W][2]", 8);
+  check_f32_n(op, "flow_bw", bw, 2 * P, "[B][H][W][2]", 8);
   range_acc(op, acc, 2 * P);
-  check_f32(vis, "range_visible: vis");
-  TORCH_CHECK(vis.numel() == 2 * P, op, ": vis must hold [2][B][H][W] = ", 2 * P, " elements");
-  for (const at::Tensor* v : {&bw, &acc, &vis}) TORCH_CHECK(v->device() == fw.device(), op, ": operands on several devices");
-  census_no_alias(op, ": vis", vis, {fw, bw, acc});
-  census_no_alias(op, ": acc", acc, {fw, bw});
-  keep.insert(keep.end(), {fw, bw, acc, vis});
+  check_f32_n(op, "vis", vis, 2 * P, "[2][B][H][W]");
+  check_one_device(op, vis, {fw, bw, acc});
+  check_no_alias(op, "vis", vis, {fw, bw, acc});
+  check_no_alias(op, "acc", acc, {fw, bw});
+  hold(keep, {fw, bw, acc, vis});
   const float *fp = fw.data_ptr<float>(), *bp = bw.data_ptr<float>();
   const int* ap = acc.data_ptr<int>();
   float* vp = vis.data_ptr<float>();
@@ -2397,15 +2358,12 @@ static Launch make_crop_resize(const TList& t, const IList& i, std::vector<at::T
   TORCH_CHECK(C >= 1 && C <= 3, op, ": 1..3 channels, got ", C);
   TORCH_CHECK(B * H * W * C <= INT32_MAX, op, ": B * H * W * C must be below 2^31");
   TORCH_CHECK(c >= 1 && 2 * c < std::min(H, W), op, ": the crop margin must be at least 1 and leave a crop, got ", c);
-  check_f32(x, "crop_resize: x");
-  check_f32(prm, "crop_resize: prm");
-  check_f32(out, "crop_resize: out");
-  TORCH_CHECK(x.numel() == B * H * W * C && out.numel() == x.numel(), op, ": x and out must hold [B][H][W][C] = ",
-              B * H * W * C, " elements");
-  TORCH_CHECK(prm.numel() == 6, op, ": prm must hold (rx, ry, scale[0..3])");
-  TORCH_CHECK(x.device() == out.device() && prm.device() == out.device(), op, ": operands on several devices");
-  census_no_alias(op, ": out", out, {x, prm});
-  keep.insert(keep.end(), {x, prm, out});
+  check_f32_n(op, "x", x, B * H * W * C, "[B][H][W][C]");
+  check_f32_n(op, "prm", prm, 6, "(rx, ry, scale[0..3])");
+  check_f32_n(op, "out", out, B * H * W * C, "[B][H][W][C]");
+  check_one_device(op, out, {x, prm});
+  check_no_alias(op, "out", out, {x, prm});
+  hold(keep, {x, prm, out});
   const float *xp = x.data_ptr<float>(), *pp = prm.data_ptr<float>();
   float* op_ = out.data_ptr<float>();
   const int b = (int)B, h = (int)H, w = (int)W, ch = (int)C, cc = (int)c;
@@ -2416,40 +2374,24 @@ static Launch make_selfsup(const TList& t, const IList& i, std::vector<at::Tenso
   at::Tensor pred = opt(t, 0), target = opt(t, 1), weight = opt(t, 2), prm = opt(t, 3);
   at::Tensor scale = bwd ? opt(t, 4) : at::Tensor(), out = opt(t, bwd ? 5 : 4);
   const int64_t N = i[0], B = i[1], H = i[2], W = i[3], Btot = i[4], B0 = i[5];
-  TORCH_CHECK(N >= 1 && N <= 32, op, ": 1..32 predictions, got ", N);
-  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && Btot >= 1 && Btot <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX &&
-                  Btot * H <= INT32_MAX && Btot * H * W <= INT32_MAX, op, ": sizes (Btot * H * W must be below 2^31)");
-  TORCH_CHECK(B0 >= 0 && B0 <= Btot - B, op, ": the batch window [", B0, ", ", B0 + B, ") must lie inside [0, ", Btot, ")");
+  const int64_t Ptot = check_loss_sizes(op, N, Btot, H, W, "Btot");
+  TORCH_CHECK(B >= 1 && B0 >= 0 && B0 <= Btot - B, op, ": the batch window [", B0, ", ", B0 + B, ") must lie inside [0, ", Btot,
+              ")");
   const int64_t P = B * H * W;
-  const std::pair<const at::Tensor*, const char*> f32s[] = {{&pred, ": pred"}, {&target, ": target"}, {&prm, ": prm"},
-                                                             {&out, bwd ? ": grad" : ": part"}};
-  for (const auto& v : f32s) check_f32(*v.first, (op + v.second).c_str());
-  TORCH_CHECK(pred.numel() == N * Btot * H * W * 2, op, ": pred must hold [N][Btot][H][W][2] = ", N * Btot * H * W * 2,
-              " elements");
-  TORCH_CHECK(target.numel() == P * 2, op, ": target must hold [B][H][W][2] = ", P * 2, " elements");
-  TORCH_CHECK(prm.numel() == 1, op, ": prm must hold (eps)");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(pred.data_ptr()) % 8 == 0 && reinterpret_cast<uintptr_t>(target.data_ptr()) % 8 == 0,
-              op, ": pred and target must be 8-byte aligned");
-  std::vector<at::Tensor> inputs = {pred, target, prm};
-  if (weight.defined()) {
-    check_f32(weight, (op + ": weight").c_str());
-    TORCH_CHECK(weight.numel() == P, op, ": weight must hold [B][H][W] = ", P, " elements");
-    inputs.push_back(weight);
-  }
+  check_f32_n(op, "pred", pred, N * Ptot * 2, "[N][Btot][H][W][2]", 8);
+  check_f32_n(op, "target", target, P * 2, "[B][H][W][2]", 8);
+  check_f32_opt(op, "weight", weight, P, "[B][H][W]");
+  check_f32_n(op, "prm", prm, 1, "(eps)");
   if (bwd) {
-    check_f32(scale, (op + ": scale").c_str());
-    TORCH_CHECK(scale.numel() == N, op, ": scale must hold [N] = ", N, " elements");
-    inputs.push_back(scale);
-    TORCH_CHECK(out.numel() == N * P * 2, op, ": grad must hold [N][B][H][W][2] = ", N * P * 2, " elements");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0, op, ": grad must be 8-byte aligned");
+    check_f32_n(op, "scale", scale, N, "[N]");
+    check_f32_n(op, "grad", out, N * P * 2, "[N][B][H][W][2]", 8);
   } else {
-    const int64_t need = (int64_t)jr_selfsup_loss_blocks(P) * N * 4;
-    TORCH_CHECK(out.numel() == need, op, ": part must hold [blocks][N][4] = ", need, " elements");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0, op, ": part must be 16-byte aligned");
+    check_f32_n(op, "part", out, (int64_t)jr_selfsup_loss_blocks(P) * N * 4, "[blocks][N][4]", 16);
   }
-  for (const at::Tensor& v : inputs) TORCH_CHECK(v.device() == out.device(), op, ": operands on several devices");
-  census_no_alias(op, bwd ? ": grad" : ": part", out, inputs);
-  keep.insert(keep.end(), inputs.begin(), inputs.end());
+  const std::vector<at::Tensor> inputs = {pred, target, weight, prm, scale};
+  check_one_device(op, out, inputs);
+  check_no_alias(op, bwd ? "grad" : "part", out, inputs);
+  hold(keep, inputs);
   keep.push_back(out);
   const float *pp = pred.data_ptr<float>(), *tp = target.data_ptr<float>(), *wp = (const float*)ptr(weight);
   const float *rp = prm.data_ptr<float>(), *sp = (const float*)ptr(scale);

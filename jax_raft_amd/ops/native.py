@@ -813,8 +813,52 @@ def flow_metrics(pred: torch.Tensor, gt: torch.Tensor, valid: Optional[torch.Ten
     return rows, acc
 
 
+# The label-free losses (csrc/kernels/loss_common.h: the constants and the reduction their kernels share).
 UNSUP_BLOCK, UNSUP_GRID_X = 256, 1024    # threads per block and the loss kernel's blocks per round (unsup.hip)
-_unsup_prm = {}
+_floats = {}
+
+
+def _cached_floats(values, device) -> torch.Tensor:
+    """A few floats as an fp32 device tensor, uploaded once per device and set of values, so that a training
+    step does not copy from the host: the one cache of the kernels' small parameter tensors."""
+    key = (str(device),) + tuple(float(v) for v in values)
+    if key not in _floats:
+        if len(_floats) >= 64:
+            _floats.clear()
+        _floats[key] = torch.tensor(key[1:], dtype=torch.float32, device=device)
+    return _floats[key]
+
+
+def _gpu_operands(op, named, aligned, N, pixels, copy=False):
+    """The GPU-only checks the loss front ends share -> the tensors of ``named`` ((name, tensor or None) pairs) as
+    the kernels take them: fp32, contiguous and, where named in ``aligned``, 8-byte aligned (the kernels' 8-byte
+    loads) -- refused otherwise, or with ``copy`` made so; at most 32 predictions of fewer than 2^31 pixels."""
+    out = []
+    for name, t in named:
+        if t is not None:
+            if t.dtype != torch.float32:
+                raise ValueError(f"{op}: {name} must be fp32 on the GPU, got {t.dtype}")
+            if copy:
+                t = t.contiguous()
+                if name in aligned and t.data_ptr() % 8:
+                    t = t.clone()
+            elif not t.is_contiguous():
+                raise ValueError(f"{op}: {name} must be contiguous on the GPU")
+            elif name in aligned and t.data_ptr() % 8:
+                raise ValueError(f"{op}: {name} must be 8-byte aligned")
+        out.append(t)
+    if N > 32 or pixels >= 2 ** 31:
+        raise ValueError(f"{op}: 1..32 predictions of fewer than 2^31 pixels, got N = {N} of {pixels} pixels")
+    return out
+
+
+def _cpu_grad(sums, preds: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The CPU path of a ``*_loss_grad``: the gradient of ``(sums(f) * scale).sum()`` in f = preds, by autograd
+    through the golden op's differentiable sums."""
+    with torch.enable_grad():
+        f = preds.detach().requires_grad_(True)
+        s = sums(f)
+        return torch.autograd.grad((s * scale.to(s.dtype)).sum(), f)[0]
 
 
 def unsup_loss_blocks(P: int) -> int:
@@ -823,14 +867,8 @@ def unsup_loss_blocks(P: int) -> int:
 
 
 def unsup_params(eps: float, eps_s: float, edge_kappa: float, out_penalty: float, device) -> torch.Tensor:
-    """``(eps, eps_s, edge_kappa, out_penalty)`` as the fp32 device tensor the kernels read; uploaded
-    once per device and set of values, so that a training step does not copy from the host."""
-    key = (str(device), float(eps), float(eps_s), float(edge_kappa), float(out_penalty))
-    if key not in _unsup_prm:
-        if len(_unsup_prm) >= 64:
-            _unsup_prm.clear()
-        _unsup_prm[key] = torch.tensor(key[1:], dtype=torch.float32, device=device)
-    return _unsup_prm[key]
+    """``(eps, eps_s, edge_kappa, out_penalty)`` as the fp32 device tensor the kernels read (cached)."""
+    return _cached_floats((eps, eps_s, edge_kappa, out_penalty), device)
 
 
 def _unsup_args(op, preds, image1, image2, mask, eps, eps_s, edge_kappa, out_penalty, prm):
@@ -839,17 +877,9 @@ def _unsup_args(op, preds, image1, image2, mask, eps, eps_s, edge_kappa, out_pen
     N, B, H, W = U._check(preds, image1, image2, mask)
     if not preds.is_cuda:
         return None
-    for name, t in (("flow_preds", preds), ("image1", image1), ("image2", image2), ("mask", mask)):
-        if t is not None and t.dtype != torch.float32:
-            raise ValueError(f"{op}: {name} must be fp32 on the GPU, got {t.dtype}")
-    if N > 32 or B * H * W >= 2 ** 31:
-        raise ValueError(f"{op}: 1..32 predictions of fewer than 2^31 pixels, got N = {N}, P = {B * H * W}")
-    if prm is None:
-        prm = unsup_params(eps, eps_s, edge_kappa, out_penalty, preds.device)
-    preds = preds.contiguous()
-    if preds.data_ptr() % 8:   # the kernels' 8-byte loads
-        preds = preds.clone()
-    return [preds, image1.contiguous(), image2.contiguous(), None if mask is None else mask.contiguous(), prm], [B, H, W, N]
+    named = (("flow_preds", preds), ("image1", image1), ("image2", image2), ("mask", mask))
+    t = _gpu_operands(op, named, ("flow_preds",), N, B * H * W, copy=True)    # a front end for any layout: it copies
+    return t + [unsup_params(eps, eps_s, edge_kappa, out_penalty, preds.device) if prm is None else prm], [B, H, W, N]
 
 
 def unsup_loss_partials(flow_preds: torch.Tensor, image1: torch.Tensor, image2: torch.Tensor,
@@ -886,11 +916,8 @@ def unsup_loss_grad(flow_preds: torch.Tensor, image1: torch.Tensor, image2: torc
     if args is None:
         from ..train.unsup import unsup_sums
 
-        with torch.enable_grad():
-            f = flow_preds.detach().requires_grad_(True)
-            s = unsup_sums(f, image1, image2, mask, eps, eps_s, edge_kappa, out_penalty)
-            total = (s[:, :2] * scale.to(s.dtype)).sum()
-            return torch.autograd.grad(total, f)[0]
+        return _cpu_grad(lambda f: unsup_sums(f, image1, image2, mask, eps, eps_s, edge_kappa, out_penalty)[:, :2],
+                         flow_preds, scale)
     t, i = args
     if scale.dtype != torch.float32:
         raise ValueError(f"unsup_loss_bwd: scale must be fp32 on the GPU, got {scale.dtype}")
@@ -920,15 +947,7 @@ def _census_args(op, preds, gray, mask):
             raise ValueError(f"{op}: {name} must be {shape} on {preds.device}, got "
                              f"{tuple(t.shape) if isinstance(t, torch.Tensor) else t} on {getattr(t, 'device', None)}")
     if preds.is_cuda:
-        for name, t in (("flow_preds", preds), ("gray", gray), ("mask", mask)):
-            if t is not None and t.dtype != torch.float32:
-                raise ValueError(f"{op}: {name} must be fp32 on the GPU, got {t.dtype}")
-            if t is not None and not t.is_contiguous():
-                raise ValueError(f"{op}: {name} must be contiguous")
-        if preds.data_ptr() % 8:
-            raise ValueError(f"{op}: flow_preds must be 8-byte aligned")
-        if N > 32 or B * H * W >= 2 ** 31:
-            raise ValueError(f"{op}: 1..32 predictions of fewer than 2^31 pixels, got N = {N}, P = {B * H * W}")
+        _gpu_operands(op, (("flow_preds", preds), ("gray", gray), ("mask", mask)), ("flow_preds",), N, B * H * W)
     return N, B, H, W
 
 
@@ -944,11 +963,7 @@ def census_gray_planes(image1: torch.Tensor, image2: torch.Tensor) -> torch.Tens
 
         return torch.stack([census_gray(image1), census_gray(image2)])
     B, H, W, _ = image1.shape
-    for name, t in (("image1", image1), ("image2", image2)):
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"census_gray: {name} must be contiguous fp32 on the GPU, got {t.dtype}")
-    if B * H * W >= 2 ** 31:
-        raise ValueError(f"census_gray: fewer than 2^31 pixels, got {B * H * W}")
+    _gpu_operands("census_gray", (("image1", image1), ("image2", image2)), (), 1, B * H * W)
     gray = torch.empty((2, B, H, W), dtype=torch.float32, device=image1.device)
     ops().census_gray([image1, image2, gray], [B, H, W])
     return gray
@@ -1005,24 +1020,17 @@ def census_loss_grad(flow_preds: torch.Tensor, image1: torch.Tensor, image2: tor
     for name, t, shape in named:
         if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.device != dev:
             raise ValueError(f"census_loss_bwd: {name} must be {shape} on {dev}")
-        if dev.type == "cuda" and (t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 8):
-            raise ValueError(f"census_loss_bwd: {name} must be contiguous, 8-byte aligned fp32 on the GPU, got {t.dtype}")
     if not flow_preds.is_cuda:
         from ..train.unsup import census_sums
 
-        with torch.enable_grad():
-            f = flow_preds.detach().requires_grad_(True)
-            c = census_sums(f, image1, image2, mask, out_penalty)
-            g = torch.autograd.grad((c[:, 0] * scale.to(c.dtype)).sum(), f)[0]
+        g = _cpu_grad(lambda f: census_sums(f, image1, image2, mask, out_penalty)[:, 0], flow_preds, scale)
         return g if out is None else out.add_(g)
+    _gpu_operands("census_loss_bwd", [v[:2] for v in named], ("scale", "out", "coef"), N, B * H * W)
     if coef is None:
         coef = census_loss_partials(flow_preds, image1, image2, mask, out_penalty, prm, gray)[1]
     grad = torch.empty(flow_preds.shape, dtype=torch.float32, device=dev) if out is None else out
     ops().census_loss_bwd([flow_preds, gray, coef, scale, grad], [B, H, W, N, 0 if out is None else 1])
     return grad
-
-
-_fb_thr = {}
 
 
 def _range_flows(op: str, flow_fw, flow_bw):
@@ -1061,6 +1069,11 @@ def range_map(flow_fw: torch.Tensor, flow_bw: Optional[torch.Tensor] = None) -> 
     return acc
 
 
+def fb_thresholds(alpha: float, beta: float, device) -> torch.Tensor:
+    """``(alpha, beta)`` of the forward-backward check as the fp32 device tensor ``fb_check`` reads (cached)."""
+    return _cached_floats((alpha, beta), device)
+
+
 def visibility_masks(flow_fw: torch.Tensor, flow_bw: torch.Tensor, kind: str, thr: float = 0.5, alpha: float = 0.01,
                      beta: float = 0.5) -> torch.Tensor:
     """The visibility masks of a (B, H, W, 2) fp32 flow pair, fp32 (2, B, H, W) (0: fw, 1: bw; 1.0 = use
@@ -1085,27 +1098,11 @@ def visibility_masks(flow_fw: torch.Tensor, flow_bw: torch.Tensor, kind: str, th
         vis = torch.empty((2, B, H, W), dtype=torch.float32, device=fw.device)
         ops().range_visible([fw, bw, acc, vis], [B, H, W, O.range_threshold(thr)])
         return vis
-    key = (str(fw.device), float(alpha), float(beta))       # uploaded once, as unsup_params
-    if key not in _fb_thr:
-        if len(_fb_thr) >= 64:
-            _fb_thr.clear()
-        _fb_thr[key] = torch.tensor(key[1:], dtype=torch.float32, device=fw.device)
-    occ_fw, occ_bw = fb_check(fw, bw, thr=_fb_thr[key])
+    occ_fw, occ_bw = fb_check(fw, bw, thr=fb_thresholds(alpha, beta, fw.device))
     return torch.stack([~O.lands_inside(fw) | ~occ_fw, ~O.lands_inside(bw) | ~occ_bw]).float()
 
 
 SELFSUP_BLOCK, SELFSUP_GRID_X = 256, 1024    # threads per block (2 pixels each) and blocks per round (selfsup.hip)
-_selfsup_prm = {}
-
-
-def _cached_floats(values, device) -> torch.Tensor:
-    """A few floats as an fp32 device tensor, uploaded once per device and set of values (as ``unsup_params``)."""
-    key = (str(device),) + tuple(float(v) for v in values)
-    if key not in _selfsup_prm:
-        if len(_selfsup_prm) >= 64:
-            _selfsup_prm.clear()
-        _selfsup_prm[key] = torch.tensor(key[1:], dtype=torch.float32, device=device)
-    return _selfsup_prm[key]
 
 
 def crop_resize(x: torch.Tensor, c: int, scale=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1163,15 +1160,8 @@ def _selfsup_args(op, preds, target, weight, eps, prm, batch0):
     N, B, H, W = S._check(win, target, weight)
     if not preds.is_cuda:
         return None
-    for name, t in (("flow_preds", preds), ("target", target), ("weight", weight)):
-        if t is not None and t.dtype != torch.float32:
-            raise ValueError(f"{op}: {name} must be fp32 on the GPU, got {t.dtype}")
-        if t is not None and not t.is_contiguous():
-            raise ValueError(f"{op}: {name} must be contiguous on the GPU")
-    if preds.data_ptr() % 8 or target.data_ptr() % 8:
-        raise ValueError(f"{op}: flow_preds and target must be 8-byte aligned")
-    if N > 32 or Btot * H * W >= 2 ** 31:
-        raise ValueError(f"{op}: 1..32 predictions of fewer than 2^31 pixels, got N = {N}, Btot H W = {Btot * H * W}")
+    named = (("flow_preds", preds), ("target", target), ("weight", weight))
+    _gpu_operands(op, named, ("flow_preds", "target"), N, Btot * H * W)     # the stack is read in place: no copies
     if prm is None:
         prm = selfsup_params(eps, preds.device)
     return [preds.detach(), target, weight, prm], [N, B, H, W, Btot, batch0]
@@ -1210,10 +1200,8 @@ def selfsup_loss_grad(flow_preds: torch.Tensor, target: torch.Tensor, weight: Op
     if args is None:
         from ..train.selfsup import selfsup_sums
 
-        with torch.enable_grad():
-            f = flow_preds[:, batch0:batch0 + target.shape[0]].detach().requires_grad_(True)
-            s = selfsup_sums(f, target, weight, eps)
-            return torch.autograd.grad((s[:, 0] * scale.to(s.dtype)).sum(), f)[0]
+        return _cpu_grad(lambda f: selfsup_sums(f, target, weight, eps)[:, 0], flow_preds[:, batch0:batch0 + target.shape[0]],
+                         scale)
     t, i = args
     if scale.dtype != torch.float32:
         raise ValueError(f"selfsup_loss_bwd: scale must be fp32 on the GPU, got {scale.dtype}")

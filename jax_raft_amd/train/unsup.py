@@ -284,58 +284,40 @@ def unsup_loss_reference(flow_preds, image1, image2, mask=None, gamma: float = 0
     photo: "charbonnier" (steps 2-3) | "census" (steps 2c-3c)."""
     _check_photo(photo)
     P = flow_preds[0].numel() // 2
+    band = None
     if photo == "census":
         c = census_sums(flow_preds, image1, image2, mask, out_penalty)
         s, band = _census_columns(c, smooth_sums(flow_preds, image1, eps_s, edge_kappa))
-        loss, mets, _ = _assemble(s, _count(mask, P, s.device, s.dtype), P, gamma, smooth_weight, band)
-        return loss, {"photo": mets[0], "smooth": mets[1], "inside": mets[2]}
-    s = unsup_sums(flow_preds, image1, image2, mask, eps, eps_s, edge_kappa, out_penalty)
-    loss, mets, _ = _assemble(s, _count(mask, P, s.device, s.dtype), P, gamma, smooth_weight)
+    else:
+        s = unsup_sums(flow_preds, image1, image2, mask, eps, eps_s, edge_kappa, out_penalty)
+    loss, mets, _ = _assemble(s, _count(mask, P, s.device, s.dtype), P, gamma, smooth_weight, band)
     return loss, {"photo": mets[0], "smooth": mets[1], "inside": mets[2]}
 
 
 class _UnsupLoss(torch.autograd.Function):
+    """Smoothness from the two kernels of csrc/kernels/unsup.hip; the photometric term from the same launches
+    (``photo="charbonnier"``) or from csrc/kernels/census.hip, unsup.hip's then called with a zero photometric scale."""
+
     @staticmethod
-    def forward(ctx, preds, image1, image2, mask, gamma, eps, eps_s, edge_kappa, smooth_weight, out_penalty):
+    def forward(ctx, preds, image1, image2, mask, photo, gamma, eps, eps_s, edge_kappa, smooth_weight, out_penalty):
         from ..ops import native as nat
 
         P = preds[0].numel() // 2
         prm = nat.unsup_params(eps, eps_s, edge_kappa, out_penalty, preds.device)
-        part = nat.unsup_loss_partials(preds, image1, image2, mask, prm=prm)
-        s = part.double().sum(0)                       # block order; the counts stay exact
-        loss, mets, w = _assemble(s, _count(mask, P, preds.device, torch.float64), P, gamma, smooth_weight)
-        scale = torch.stack([w / P, w * (smooth_weight / (2.0 * P))], dim=-1)
-        ctx.save_for_backward(preds, image1, image2, mask, prm, scale)
-        mets = mets.float()
-        ctx.mark_non_differentiable(mets)
-        return loss.float(), mets
-
-    @staticmethod
-    def backward(ctx, gl, _gm):
-        from ..ops import native as nat
-
-        preds, image1, image2, mask, prm, scale = ctx.saved_tensors
-        grad = nat.unsup_loss_grad(preds, image1, image2, mask, (scale * gl.double()).float().contiguous(), prm=prm)
-        return (grad,) + (None,) * 9
-
-
-class _CensusLoss(torch.autograd.Function):
-    """The census term from csrc/kernels/census.hip, the smoothness term from the two kernels of
-    unsup.hip called with a zero photometric scale."""
-
-    @staticmethod
-    def forward(ctx, preds, image1, image2, mask, gamma, eps, eps_s, edge_kappa, smooth_weight, out_penalty):
-        from ..ops import native as nat
-
-        P = preds[0].numel() // 2
-        prm = nat.unsup_params(eps, eps_s, edge_kappa, out_penalty, preds.device)
-        gray = nat.census_gray_planes(image1, image2)
-        part, coef = nat.census_loss_partials(preds, image1, image2, mask, prm=prm, gray=gray)
-        smooth = nat.unsup_loss_partials(preds, image1, image2, mask, prm=prm).double().sum(0)[:, 1]
-        s, band = _census_columns(part.double().sum(0), smooth)      # tile order; the counts stay exact
+        census = photo == "census"
+        # sums in block (census: tile) order; the counts stay exact
+        s = nat.unsup_loss_partials(preds, image1, image2, mask, prm=prm).double().sum(0)
+        band = gray = coef = None
+        if census:
+            gray = nat.census_gray_planes(image1, image2)
+            part, coef = nat.census_loss_partials(preds, image1, image2, mask, prm=prm, gray=gray)
+            s, band = _census_columns(part.double().sum(0), s[:, 1])
         loss, mets, w = _assemble(s, _count(mask, P, preds.device, torch.float64), P, gamma, smooth_weight, band)
-        scale = torch.stack([torch.zeros_like(w), w * (smooth_weight / (2.0 * P)), w / P], dim=-1)
-        ctx.save_for_backward(preds, image1, image2, mask, prm, gray, coef, scale)
+        zero = torch.zeros_like(w)
+        # the backward's scales: unsup.hip's photometric and smoothness terms, census.hip's term
+        scale = torch.stack([zero if census else w / P, w * (smooth_weight / (2.0 * P)), w / P if census else zero], dim=-1)
+        ctx.photo = photo
+        ctx.save_for_backward(preds, image1, image2, mask, prm, scale, gray, coef)
         mets = mets.float()
         ctx.mark_non_differentiable(mets)
         return loss.float(), mets
@@ -344,11 +326,12 @@ class _CensusLoss(torch.autograd.Function):
     def backward(ctx, gl, _gm):
         from ..ops import native as nat
 
-        preds, image1, image2, mask, prm, gray, coef, scale = ctx.saved_tensors
+        preds, image1, image2, mask, prm, scale, gray, coef = ctx.saved_tensors
         scale = (scale * gl.double()).float()
         grad = nat.unsup_loss_grad(preds, image1, image2, mask, scale[:, :2].contiguous(), prm=prm)
-        nat.census_loss_grad(preds, image1, image2, mask, scale[:, 2].contiguous(), prm=prm, gray=gray, coef=coef, out=grad)
-        return (grad,) + (None,) * 9
+        if ctx.photo == "census":
+            nat.census_loss_grad(preds, image1, image2, mask, scale[:, 2].contiguous(), prm=prm, gray=gray, coef=coef, out=grad)
+        return (grad,) + (None,) * 10
 
 
 def unsup_loss(flow_preds, image1, image2, mask=None, gamma: float = 0.8, eps: float = 0.01, eps_s: float = 0.001,
@@ -364,12 +347,7 @@ def unsup_loss(flow_preds, image1, image2, mask=None, gamma: float = 0.8, eps: f
                                     out_penalty, photo)
     _check(flow_preds, image1, image2, mask)
     m = None if mask is None else mask.float().contiguous()
-    if photo == "census":
-        loss, mets = _CensusLoss.apply(flow_preds.float().contiguous(), image1.float().contiguous(),
-                                       image2.float().contiguous(), m, float(gamma), float(eps), float(eps_s),
-                                       float(edge_kappa), float(smooth_weight), float(out_penalty))
-        return loss, {"photo": mets[0], "smooth": mets[1], "inside": mets[2]}
-    loss, mets = _UnsupLoss.apply(flow_preds.float().contiguous(), image1.float().contiguous(),
-                                  image2.float().contiguous(), m, float(gamma), float(eps), float(eps_s),
-                                  float(edge_kappa), float(smooth_weight), float(out_penalty))
+    loss, mets = _UnsupLoss.apply(flow_preds.float().contiguous(), image1.float().contiguous(), image2.float().contiguous(), m,
+                                  photo, float(gamma), float(eps), float(eps_s), float(edge_kappa), float(smooth_weight),
+                                  float(out_penalty))
     return loss, {"photo": mets[0], "smooth": mets[1], "inside": mets[2]}

@@ -203,6 +203,18 @@ def test_front_end_checks_and_exports():
     assert nat.UNSUP_GRID_X * nat.UNSUP_BLOCK == R.UNSUP_GRID
 
 
+def test_parameter_tensors_share_one_cache():
+    dev = torch.device("cpu")
+    makers = ((nat.unsup_params, (0.01, 0.001, 10.0, 0.5)), (nat.selfsup_params, (0.001,)), (nat.fb_thresholds, (0.01, 0.5)))
+    first = [make(*values, dev) for make, values in makers]
+    for (make, values), t in zip(makers, first):
+        assert make(*values, dev) is t                                   # a second call uploads nothing
+        assert t.dtype == torch.float32 and t.tolist() == torch.tensor(values, dtype=torch.float32).tolist()
+        assert sum(v is t for v in nat._floats.values()) == 1           # ... and all live in the one cache
+    assert nat.unsup_params(0.01, 0.001, 10.0, 0.25, dev) is not first[0]
+    assert nat._cached_floats((0.001,), dev) is first[1]
+
+
 @pytest.mark.skipif(not nat.available(), reason="native library not built")
 def test_op_rows():
     for op in ("unsup_loss", "unsup_loss_bwd"):
