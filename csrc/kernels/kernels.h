@@ -439,6 +439,20 @@ int jr_flowin_dual(const void* x, int x_cstride, int N, int H, int W, int PH, in
 int jr_conv_direct(const void* x, int x_cstride, int N, int H, int W, int cin, int KH, int KW, int PH, int PW,
                    const void* w, const float* bias, int cout, int relu, void* y, int y_cstride, int y_coff,
                    hipStream_t stream);
+// The flow branch's two convs in one launch (flowfeat.hip): the 7x7 conv 2 -> 128 + relu of
+// jr_conv_direct (flow: compact bf16 [N*H*W][2]; w1 / b1 as there), recomputed per 8 x 16 tile on its
+// footprint, feeds the halo 3x3 conv 128 -> 64 + relu (w2: the halo weight stream of jr_conv_halo)
+// into channels y_coff .. + 64 of y [N*H*W][ycs].  Bitwise the two launches' output.
+struct FlowFeatParams {
+  const void* flow; int N, H, W;
+  const void* w1; const float* b1;
+  const void* w2; long w2_bytes; const float* b2;
+  void* y; int ycs, yoff;
+  int tiles_y, tiles_x, ntiles;
+};
+int jr_flow_features_fused(const FlowFeatParams* p, hipStream_t stream);
+// its tile (rows, cols) into out2; returns its LDS bytes
+int jr_flow_features_tile(int* out2);
 int jr_copy_channels(const void* src, int s_cstride, int s_coff, void* dst, int d_cstride, int d_coff,
                      int M, int C, hipStream_t stream);
 

@@ -937,6 +937,39 @@ static Launch make_conv_direct(const TList& t, const IList& i, std::vector<at::T
   };
 }
 
+// The flow branch's two convs in one launch (flowfeat.hip): 7x7 / pad 3, 2 -> 128, relu, then 3x3 / pad 1,
+// 128 -> 64, relu, into a 64-channel slice of y.
+// t = [flow (bf16 [N*H*W][2]), w1 (conv_direct's A fragments), b1 (fp32 [128]), w2 (the halo conv's weight
+//      stream, pack_halo_conv), b2 (fp32 [64]), y (bf16 [N*H*W][ycs])],  i = [N, H, W, y_coff]
+static Launch make_flow_features_fused(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  at::Tensor x = opt(t, 0), w1 = opt(t, 1), b1 = opt(t, 2), w2 = opt(t, 3), b2 = opt(t, 4), y = opt(t, 5);
+  check_bf16(x, "flow"); check_bf16(w1, "w1"); check_f32(b1, "b1"); check_bf16(w2, "w2"); check_f32(b2, "b2");
+  check_bf16(y, "y");
+  const int N = (int)i[0], H = (int)i[1], W = (int)i[2], y_coff = (int)i[3];
+  TORCH_CHECK(N > 0 && H > 0 && W > 0, "flow_features_fused: N, H, W");
+  const int64_t M = (int64_t)N * H * W;
+  TORCH_CHECK(M < (1LL << 31) / 256, "flow_features_fused: too many pixels");
+  TORCH_CHECK(cs(x) == 2 && x.numel() == M * 2, "flow_features_fused: compact 2-channel flow [N*H*W][2]");
+  TORCH_CHECK(w1.numel() == 128 * 4 * 32 && b1.numel() == 128, "flow_features_fused: 7x7 conv 2 -> 128 (pack_direct_weight)");
+  TORCH_CHECK(w2.numel() == 64 * 9 * 128 && b2.numel() == 64, "flow_features_fused: 3x3 conv 128 -> 64 (pack_halo_conv)");
+  TORCH_CHECK(cs(y) % 8 == 0 && y_coff % 8 == 0 && y_coff >= 0 && y_coff + 64 <= cs(y) && y.numel() >= M * cs(y),
+              "flow_features_fused: y");
+  for (const at::Tensor* v : {&w1, &w2, &y})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(v->data_ptr()) % 16 == 0, "flow_features_fused: 16-byte aligned operands");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 4 == 0, "flow_features_fused: 4-byte aligned flow");
+  int tile[2];
+  jr_flow_features_tile(tile);
+  FlowFeatParams p{};
+  p.flow = x.data_ptr(); p.N = N; p.H = H; p.W = W;
+  p.w1 = w1.data_ptr(); p.b1 = b1.data_ptr<float>();
+  p.w2 = w2.data_ptr(); p.w2_bytes = (long)w2.numel() * 2; p.b2 = b2.data_ptr<float>();
+  p.y = y.data_ptr(); p.ycs = cs(y); p.yoff = y_coff;
+  p.tiles_y = (H + tile[0] - 1) / tile[0]; p.tiles_x = (W + tile[1] - 1) / tile[1];
+  p.ntiles = N * p.tiles_y * p.tiles_x;
+  for (auto& v : {x, w1, b1, w2, b2, y}) keep.push_back(v);
+  return [p](hipStream_t s, int) { return jr_flow_features_fused(&p, s); };
+}
+
 // The 7x7 flow conv (as make_conv_direct) merged with the DEFERRED x8 upsampling of the
 // previous iteration (merged.hip).  t = [x, w, bias, y, flow32, out, out_slot?(, feat, wpk, cbias)],
 // i = [N, H, W, 2, 7, 7, PH, PW, cout, relu, y_coff, mode (1 bilinear / 2 convex head), out_iter_stride,
@@ -2478,6 +2511,7 @@ static const std::vector<OpRow>& op_table() {
       row_ti("gru_halo", 9, 9, make_gru_halo),
       row_ti("conv1x1", 6, 6, make_conv1x1),
       row_ti("conv_direct", 11, 11, make_conv_direct),
+      row_ti("flow_features_fused", 4, 4, make_flow_features_fused),
       row_tia("flowin_dual", "alpha", 15, 21, make_flowin_dual),   // 15 | 21
       // training
       row_tia("upsample_convex_bwd", "alpha", 3, 3, make_upsample_convex_bwd),

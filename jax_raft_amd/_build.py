@@ -39,6 +39,7 @@ KERNEL_SOURCES = [
     CSRC / "kernels" / "f32.hip",
     CSRC / "kernels" / "flowhead.hip",
     CSRC / "kernels" / "conv_direct.hip",
+    CSRC / "kernels" / "flowfeat.hip",
     CSRC / "kernels" / "train.hip",
     CSRC / "kernels" / "wgrad.hip",
     CSRC / "kernels" / "convex_head.hip",

@@ -4,7 +4,7 @@ They are operational settings (which library to load, where the tuned-config tab
 debugging aids, the rank layout of a rehearsal); none of them changes what a kernel computes.
 Lowering / schedule choices are not environment switches: each is fixed to the winner of its
 A/B (the profile is cited where the choice is made) and the ones tests flip to cover the
-alternative are class or module attributes -- ``RaftEngine.GRU``, ``.GRU_ME``, ``.PRO_LANES``,
+alternative are class or module attributes -- ``RaftEngine.GRU``, ``.GRU_ME``, ``.FLOW_FUSED``, ``.PRO_LANES``,
 ``.HALO_NORM``, ``.MERGED_UP``, ``.CONV_GROUP``, ``.MASK_PARITY``, ``.HOST_GATE``,
 ``.AUTO_STREAMS_MIN_BATCH``, ``.GATE_MIN_ITERS``, ``.max_plans`` (runtime/engine.py) and
 ``FUSED_ENCODERS``, ``FUSED_GRAPH``, ``FUSED_TRAIN``, ``FusedModel.SIDE_ENCODER``,

@@ -77,6 +77,11 @@ def gru_fused_tiles(N: int, H: int, W: int, vertical: int) -> int:
     return N * (W // J) if 1 <= H and J * H <= 128 and J * (H + 4) <= 136 and W % J == 0 else 0
 
 
+def flow_fused_tiles(N: int, H: int, W: int) -> int:
+    """Workgroups of the fused flow-feature kernel (csrc/kernels/flowfeat.hip): 8 x 16 pixel tiles."""
+    return N * -(-H // 8) * -(-W // 16)
+
+
 def _m32_chan(r: torch.Tensor) -> torch.Tensor:
     """Channel held by row r of a 32-row MFMA A block whose accumulator register i of lane
     half h is channel 16 h + i (row (i & 3) + 8 (i >> 2) + 4 h of the 32x32x16 tile)."""
@@ -521,6 +526,21 @@ def conv1x1(x: torch.Tensor, wpk: torch.Tensor, bias: torch.Tensor, kvalid: int,
     M = x.shape[0]
     y = torch.empty(M, cout, device=x.device, dtype=torch.bfloat16)
     ops().conv1x1([x, wpk, bias, y], [M, kvalid, kpad, cout, act, 0])
+    return y
+
+
+def flow_features_fused(flow: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, spec2: ConvSpec, N: int, H: int,
+                        W: int, y: torch.Tensor, y_coff: int = 0) -> torch.Tensor:
+    """Eager fused flow branch (csrc/kernels/flowfeat.hip): flow bf16 [N*H*W][2] through the 7x7
+    conv 2 -> 128 + relu (``w1``: :func:`pack_direct_weight`, ``b1``) and the 3x3 / pad-1 conv
+    128 -> 64 + relu ``spec2`` into channels ``y_coff .. + 64`` of y bf16 [N*H*W][cs]: what
+    ``conv_direct`` followed by the halo conv writes, bitwise.  The kernel assumes exactly these
+    shapes, the compact flow rows and the halo weight stream; checked here (and in the op)."""
+    assert flow.dtype == torch.bfloat16 and flow.shape[-1] == 2 and flow.numel() == N * H * W * 2 and flow.is_contiguous()
+    assert w1.numel() == 128 * 4 * 32 and b1.numel() == 128, "7x7 conv 2 -> 128 (pack_direct_weight)"
+    assert spec2.halo_ks == 3 and spec2.cin8 == 128 and spec2.cout == 64 and spec2.wh is not None, "3x3 conv 128 -> 64"
+    assert y.dtype == torch.bfloat16 and y.shape[-1] % 8 == 0 and y_coff % 8 == 0 and y_coff + 64 <= y.shape[-1]
+    ops().flow_features_fused([flow, w1, b1, spec2.wh, spec2.b, y], [N, H, W, y_coff])
     return y
 
 

@@ -268,6 +268,7 @@ class RaftEngine:
     # class, before the plan is built).  Operational environment variables: jax_raft_amd/knobs.py.
     GRU = "auto"          # ConvGRU stage lowering: "auto" | "halo" | "fused" | "unfused" (_gru_path)
     GRU_ME = "auto"       # motion conv inside the first fused ConvGRU stage: "auto" | "on" | "off" (_gru_me_ok)
+    FLOW_FUSED = "auto"   # lane schedule: the flow branch's two convs as one launch: "auto" | "on" | "off" (_flow_fused_ok)
     PRO_LANES = "auto"    # prologue branches on lanes at one-lane loops: "auto" | "on" | "off"
     HALO_NORM = True      # encoder instance norms fused into the halo 3x3 convs
     MERGED_UP = True      # one-lane loop: 7x7 flow conv merged with the x8 upsampling (merged.hip)
@@ -1124,6 +1125,24 @@ class RaftEngine:
                 or ks != (1, 5) or not 1 <= w <= 128):
             return False
         return self.GRU_ME == "on" or nat.gru_fused_tiles(B, h, w, 0) >= 3 * nat.NUM_CUS // 4
+
+    def _flow_fused_ok(self, B: int, h: int, w: int, lanes_on: bool) -> bool:
+        """On the lane schedule: whether the motion encoder's flow branch runs as one launch
+        (flowfeat.hip, op ``flow_features_fused``) instead of the 7x7 conv and the halo 3x3 conv
+        behind it.  The kernel is written for 7x7 / pad 3, 2 -> 128, then 3x3 / pad 1, 128 -> 64,
+        on the compact 2-channel flow.  ``FLOW_FUSED = "auto"``: where its 8 x 16 tiles fill the
+        GPU (the >= 3/4-of-the-CUs rule of _gru_me_ok); ``"on"`` forces it wherever it fits (the
+        tests, at small shapes); ``"off"`` keeps the two launches.  One-lane, final-only and
+        context-parallel plans, raft_small, the fp32 / mixed engines and training never take it."""
+        assert self.FLOW_FUSED in ("auto", "on", "off"), self.FLOW_FUSED
+        if self.FLOW_FUSED == "off" or not lanes_on or self.cp or self.precision != "bf16" or self._cf1_w is None:
+            return False
+        me = self.model.update_block.motion_encoder
+        c1, sp = me.convflow1.layers_0, self._specs["me.convflow2"]
+        if (tuple(c1.kernel.shape) != (7, 7, 2, 128) or tuple(c1.padding) != (3, 3)
+                or not (sp.halo_ks == 3 and sp.cin8 == 128 and sp.cout == 64 and sp.wh is not None)):
+            return False
+        return self.FLOW_FUSED == "on" or nat.flow_fused_tiles(B, h, w) >= 3 * nat.NUM_CUS // 4
 
     def _parts(self, B: int) -> int:
         """Independent part-forwards of a batch-``B`` plan: ``split`` where it divides the batch."""

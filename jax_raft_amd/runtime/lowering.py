@@ -62,6 +62,7 @@ class PartChoices:
     mask_wait: Optional[int]
     merged_up: bool               # one lane: 7x7 flow conv + the previous x8 upsampling as one grid (merged.hip)
     c1_merged: bool               # ... which also runs convcorr1 (1x1, K 324 -> 352)
+    flow_fused: bool              # lane schedule: the flow branch's two convs as one launch (flow_features_fused; no ``f1``)
 
 
 def _prologue_choices(eng, Bi: int, h: int, w: int, lanes, slot: bool) -> dict:
@@ -128,7 +129,7 @@ def _gru_choices(eng, B: int, h: int, w: int, lanes_on: bool) -> dict:
                 gru_me=gru_path == "fused" and eng._gru_me_ok(B, h, w), qx_x=gru_path != "halo" or halo_pp)
 
 
-def _head_choices(eng, B: int, all_iters: bool, lanes_on: bool) -> dict:
+def _head_choices(eng, B: int, h: int, w: int, all_iters: bool, lanes_on: bool) -> dict:
     """The flow head / mask head / flow-feature choices, and from them the schedule."""
     sp = eng._specs
     me = eng.model.update_block.motion_encoder
@@ -149,8 +150,14 @@ def _head_choices(eng, B: int, all_iters: bool, lanes_on: bool) -> dict:
     # loses (414.8 -> 402.7), keeps the "final" order (profiles/r4_host_gate.txt)
     schedule = ("cp" if eng.cp else "lanes" if lanes_on else "one_lane" if all_iters
                 else "final_merged" if flow7 and B < eng.AUTO_STREAMS_MIN_BATCH else "final")
+    # The mask lane's chain of four launches (7x7 flow conv, convflow2, mask conv, convex head) ended
+    # after the main lane wanted to start the last ConvGRU stage (the E_MASK join: 15-21 us of main-
+    # lane idle per iteration, profiles/megru_after.txt); the fused flow features take one launch
+    # and the f1 round trip out of it: 17.3 -> 9.2 us alone, +1.2-1.5 % at batch 4, and the join no
+    # longer waits for the chain (profiles/masklane_fused.txt)
+    flow_fused = schedule == "lanes" and eng._flow_fused_ok(B, h, w, lanes_on)
     return dict(split_mask=split_mask, s1=s1, taps_epi=taps_epi, merged_up=merged_up, c1_merged=c1_merged,
-                schedule=schedule)
+                schedule=schedule, flow_fused=flow_fused)
 
 
 def choose(eng, Bi: int, B: int, h: int, w: int, all_iters: bool, lanes, *, warm: bool = False,
@@ -161,7 +168,7 @@ def choose(eng, Bi: int, B: int, h: int, w: int, all_iters: bool, lanes, *, warm
     assert not (bidir and (warm or eng.cp)), "bidirectional plans: one part, cold, no context parallelism"
     pro = _prologue_choices(eng, Bi, h, w, lanes, slot)
     assert not (pro["on_demand"] and (bidir or eng.cp)), "on-demand plans: one direction, no context parallelism"
-    gru, head = _gru_choices(eng, B, h, w, pro["lanes_on"]), _head_choices(eng, B, all_iters, pro["lanes_on"])
+    gru, head = _gru_choices(eng, B, h, w, pro["lanes_on"]), _head_choices(eng, B, h, w, all_iters, pro["lanes_on"])
     return PartChoices(all_iters=bool(all_iters), warm=warm, bidir=bidir, **pro, **gru, **head)
 
 
@@ -318,7 +325,7 @@ class PartRecorder:
         cl, fl = self.me.corr_layers, self.me.flow_layers
         self.corr = self.alloc("corr", (M, e.corr_cs))
         self.cf = self.alloc("cf", (M, cl[-1] + fl[-1]))
-        self.f1 = self.alloc("f1", (M, fl[0]))
+        self.f1 = None if c.flow_fused else self.alloc("f1", (M, fl[0]))   # (the fused flow features keep it on the CU)
         self.c1 = self.alloc("c1", (M, cl[0])) if len(cl) == 2 else None
         self.taps = self.alloc("fh2.taps", (M, 24), F32)
         self.fm = None if c.taps_epi else self.alloc("fm", (M, round_up(e._specs[c.s1].cout, 8)))
@@ -333,6 +340,11 @@ class PartRecorder:
     # ---------------- op emitters of the loop body (model.py:495-510)
     def flow_features(self):
         e, p, B, h, w = self.eng, self.plan, self.B, self.h, self.w
+        if self.c.flow_fused:   # both convs in one launch (flowfeat.hip)
+            sp2 = e._specs["me.convflow2"]
+            p.add_flow_features_fused([self.flow8, e._cf1_w, e._cf1_b, sp2.wh, sp2.b, self.cf],
+                                      [B, h, w, self.me.corr_layers[-1]])
+            return
         if e._cf1_w is not None:
             p.add_conv_direct([self.flow8, e._cf1_w, e._cf1_b, self.f1], self._flowin_ints())
         else:
