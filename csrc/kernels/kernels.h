@@ -390,6 +390,16 @@ int jr_census_loss(const float* pred, const float* gray, const float* mask, cons
                    int B, int H, int W, int N, hipStream_t stream);
 int jr_census_loss_bwd(const float* pred, const float* gray, const float* coef, const float* scale, float* grad, int B,
                        int H, int W, int N, int add, hipStream_t stream);
+// Second-order edge-aware smoothness of the label-free loss (smooth2.hip; train/unsup.py:smooth2_sums).  Sizes,
+// pred and prm as above (words 1 and 2 are read).  jr_smooth2_loss writes part fp32 [jr_smooth2_loss_blocks(P)][N][4]
+// (16-byte aligned): per block and iteration the sum over the triples along x, the sum over the triples along y, 0, 0.
+// jr_smooth2_loss_bwd writes (add = 0) or adds (add = 1) the gradient to grad fp32 [N][B][H][W][2] (8-byte aligned)
+// with scale fp32 [N].
+int jr_smooth2_loss_blocks(long P);
+int jr_smooth2_loss(const float* pred, const float* img1, const float* prm, float* part, int B, int H, int W, int N,
+                    hipStream_t stream);
+int jr_smooth2_loss_bwd(const float* pred, const float* img1, const float* prm, const float* scale, float* grad, int B,
+                        int H, int W, int N, int add, hipStream_t stream);
 // Range-map occlusion estimate (occlusion.hip; train/occlusion.py:range_map / visibility_masks, bitwise).
 // flow_fw / flow_bw fp32 [B][H][W][2], 8-byte aligned; H * W <= JR_RANGE_MAX_PIXELS, so that no flow
 // field can overflow an int32 cell (256 per source pixel); at most 65535 maps per launch.

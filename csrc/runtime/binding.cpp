@@ -2235,6 +2235,46 @@ static Launch make_census_loss_bwd(const TList& t, const IList& i, std::vector<a
   return [=](hipStream_t s, int) { return jr_census_loss_bwd(pp, gp, cp, sp, op_, b, h, w, n, a, s); };
 }
 
+// ------------------------------------------------ second-order smoothness
+// (kernels smooth2.hip).  smooth2_loss: t = [pred (fp32 [N][B][H][W][2]), image1 (fp32 [B][H][W][3]), prm (fp32 [4]),
+// part (fp32 [blocks][N][4])], i = [B, H, W, N].  smooth2_loss_bwd: t = [pred, image1, prm, scale (fp32 [N]), grad
+// (fp32 like pred)], i = [B, H, W, N, add (0: write, 1: add into grad)].
+static Launch make_smooth2_loss(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  const std::string op = "smooth2_loss";
+  at::Tensor pred = opt(t, 0), img1 = opt(t, 1), prm = opt(t, 2), part = opt(t, 3);
+  const int64_t N = i[3], P = check_loss_sizes(op, N, i[0], i[1], i[2]);
+  check_f32_n(op, "pred", pred, N * P * 2, "[N][B][H][W][2]", 8);
+  check_f32_n(op, "image1", img1, P * 3, "[B][H][W][3]");
+  check_f32_n(op, "prm", prm, 4, "(eps, eps_s, edge_kappa, out_penalty)");
+  check_f32_n(op, "part", part, (int64_t)jr_smooth2_loss_blocks(P) * N * 4, "[blocks][N][4]", 16);
+  check_one_device(op, part, {pred, img1, prm});
+  check_no_alias(op, "part", part, {pred, img1, prm});
+  hold(keep, {pred, img1, prm, part});
+  const float *pp = pred.data_ptr<float>(), *p1 = img1.data_ptr<float>(), *rp = prm.data_ptr<float>();
+  float* op_ = part.data_ptr<float>();
+  const int b = (int)i[0], h = (int)i[1], w = (int)i[2], n = (int)N;
+  return [=](hipStream_t s, int) { return jr_smooth2_loss(pp, p1, rp, op_, b, h, w, n, s); };
+}
+static Launch make_smooth2_loss_bwd(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  const std::string op = "smooth2_loss_bwd";
+  at::Tensor pred = opt(t, 0), img1 = opt(t, 1), prm = opt(t, 2), scale = opt(t, 3), grad = opt(t, 4);
+  const int64_t N = i[3], add = i[4], P = check_loss_sizes(op, N, i[0], i[1], i[2]);
+  TORCH_CHECK(add == 0 || add == 1, op, ": add must be 0 or 1, got ", add);
+  check_f32_n(op, "pred", pred, N * P * 2, "[N][B][H][W][2]", 8);
+  check_f32_n(op, "image1", img1, P * 3, "[B][H][W][3]");
+  check_f32_n(op, "prm", prm, 4, "(eps, eps_s, edge_kappa, out_penalty)");
+  check_f32_n(op, "scale", scale, N, "[N]");
+  check_f32_n(op, "grad", grad, N * P * 2, "[N][B][H][W][2]", 8);
+  check_one_device(op, grad, {pred, img1, prm, scale});
+  check_no_alias(op, "grad", grad, {pred, img1, prm, scale});
+  hold(keep, {pred, img1, prm, scale, grad});
+  const float *pp = pred.data_ptr<float>(), *p1 = img1.data_ptr<float>(), *rp = prm.data_ptr<float>();
+  const float* sp = scale.data_ptr<float>();
+  float* op_ = grad.data_ptr<float>();
+  const int b = (int)i[0], h = (int)i[1], w = (int)i[2], n = (int)N, a = (int)add;
+  return [=](hipStream_t s, int) { return jr_smooth2_loss_bwd(pp, p1, rp, sp, op_, b, h, w, n, a, s); };
+}
+
 // ------------------------------------------------------------- sequence loss
 // t = [pred (fp32 [N][P][2]), gt (fp32 [P][2]), valid? (fp32 [P]), part (fp32 [blocks][37])], i = [P, N]
 void seq_loss_op(const TList& t, IList i, double max_flow) {
@@ -2534,6 +2574,8 @@ static const std::vector<OpRow>& op_table() {
       row_ti("census_gray", 3, 3, make_census_gray),
       row_ti("census_loss", 4, 4, make_census_loss),
       row_ti("census_loss_bwd", 5, 5, make_census_loss_bwd),
+      row_ti("smooth2_loss", 4, 4, make_smooth2_loss),
+      row_ti("smooth2_loss_bwd", 5, 5, make_smooth2_loss_bwd),
       row_ti("range_splat", 3, 3, make_range_splat),
       row_ti("range_visible", 4, 4, make_range_visible),
       row_ti("crop_resize", 5, 5, make_crop_resize),

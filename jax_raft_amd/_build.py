@@ -57,6 +57,7 @@ KERNEL_SOURCES = [
     CSRC / "kernels" / "metrics.hip",
     CSRC / "kernels" / "unsup.hip",
     CSRC / "kernels" / "census.hip",
+    CSRC / "kernels" / "smooth2.hip",
     CSRC / "kernels" / "occlusion.hip",
     CSRC / "kernels" / "selfsup.hip",
 ]

@@ -1053,6 +1053,70 @@ def census_loss_grad(flow_preds: torch.Tensor, image1: torch.Tensor, image2: tor
     return grad
 
 
+def smooth2_loss_blocks(P: int) -> int:
+    """Rows of block partials that ``smooth2_loss`` writes for P pixels."""
+    return min(UNSUP_GRID_X, (P + UNSUP_BLOCK - 1) // UNSUP_BLOCK)
+
+
+def _smooth2_args(op, preds, image1, extra, eps_s, edge_kappa, prm):
+    """Host checks shared by the second-order smoothness front ends; ``extra``: (name, tensor, shape) of the operands
+    beside the predictions and the image.  Nothing is launched before they pass -> (N, B, H, W, prm)."""
+    if preds.ndim != 5 or preds.shape[-1] != 2 or not preds.is_floating_point() or 0 in preds.shape:
+        raise ValueError(f"{op}: flow_preds must be a non-empty (N, B, H, W, 2) floating point tensor, got "
+                         f"{tuple(preds.shape)} {preds.dtype}")
+    N, B, H, W, _ = preds.shape
+    named = [("image1", image1, (B, H, W, 3))] + list(extra)
+    for name, t, shape in named:
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.device != preds.device or not t.is_floating_point():
+            raise ValueError(f"{op}: {name} must be floating point {shape} on {preds.device}, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else t} on {getattr(t, 'device', None)}")
+    if preds.is_cuda:
+        _gpu_operands(op, [("flow_preds", preds)] + [v[:2] for v in named], ("flow_preds", "out"), N, B * H * W)
+        if prm is None:
+            prm = unsup_params(0.01, eps_s, edge_kappa, 0.5, preds.device)
+        elif not (isinstance(prm, torch.Tensor) and prm.is_cuda and prm.dtype == torch.float32 and prm.numel() == 4):
+            raise ValueError(f"{op}: prm must be the fp32 device tensor of unsup_params")
+    return N, B, H, W, prm
+
+
+def smooth2_loss_partials(flow_preds: torch.Tensor, image1: torch.Tensor, eps_s: float = 0.001, edge_kappa: float = 10.0,
+                          prm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The partial sums of the second-order smoothness term, fp32 (blocks, N, 4): per iteration the sum over the
+    triples along x, the sum over the triples along y, 0, 0 -- ``train/unsup.py:smooth2_sums`` itself on CPU tensors
+    (one row of partials), the HIP kernel on GPU tensors (``csrc/kernels/smooth2.hip``; one launch, bitwise
+    repeatable).  ``prm``: :func:`unsup_params`, in place of the two floats."""
+    N, B, H, W, prm = _smooth2_args("smooth2_loss", flow_preds, image1, (), eps_s, edge_kappa, prm)
+    if not flow_preds.is_cuda:
+        from ..train.unsup import smooth2_sums
+
+        with torch.no_grad():
+            s = smooth2_sums(flow_preds, image1, eps_s, edge_kappa)
+            return torch.cat([s, torch.zeros_like(s)], dim=-1)[None]
+    part = torch.empty((smooth2_loss_blocks(B * H * W), N, 4), dtype=torch.float32, device=flow_preds.device)
+    ops().smooth2_loss([flow_preds, image1, prm, part], [B, H, W, N])
+    return part
+
+
+def smooth2_loss_grad(flow_preds: torch.Tensor, image1: torch.Tensor, scale: torch.Tensor, eps_s: float = 0.001,
+                      edge_kappa: float = 10.0, prm: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of ``sum_i scale[i] (x-axis sum + y-axis sum)_i`` in the predictions, (N, B, H, W, 2): fp32
+    autograd through ``train/unsup.py:smooth2_sums`` on CPU tensors, the gather kernel of ``csrc/kernels/smooth2.hip``
+    on GPU tensors (one launch, no atomics).  scale: (N,); ``out``: a gradient tensor to add into, in place of a new
+    one (it is returned)."""
+    N = flow_preds.shape[0] if flow_preds.ndim == 5 else 0
+    extra = (("scale", scale, (N,)),) + (() if out is None else (("out", out, tuple(flow_preds.shape)),))
+    N, B, H, W, prm = _smooth2_args("smooth2_loss_bwd", flow_preds, image1, extra, eps_s, edge_kappa, prm)
+    if not flow_preds.is_cuda:
+        from ..train.unsup import smooth2_sums
+
+        g = _cpu_grad(lambda f: smooth2_sums(f.float(), image1.float(), eps_s, edge_kappa).sum(-1), flow_preds, scale)
+        return g if out is None else out.add_(g)
+    grad = torch.empty(flow_preds.shape, dtype=torch.float32, device=flow_preds.device) if out is None else out
+    ops().smooth2_loss_bwd([flow_preds, image1, prm, scale, grad], [B, H, W, N, 0 if out is None else 1])
+    return grad
+
+
 def _range_flows(op: str, flow_fw, flow_bw):
     """Host checks of a flow pair (flow_bw may be None), before any launch -> (B, H, W)."""
     from ..train import occlusion as O

@@ -29,7 +29,8 @@ trains ``--dataset chairs`` on the label-1 pairs of FlyingChairs' split file onl
 Without ground truth: ``--loss unsup`` trains on the photometric + edge-aware smoothness loss of
 ``train/unsup.py`` (``--unsup-eps``, ``--unsup-eps-s``, ``--unsup-edge-kappa``, ``--unsup-smooth-weight``,
 ``--unsup-out-penalty``; ``--unsup-photo census`` replaces the colour difference by the soft census term of
-UnFlow / SMURF; ``--gamma`` weights the iterations as ever), with augmentation records that keep
+UnFlow / SMURF; ``--unsup-smooth-order 2`` penalises second differences of the flow instead of first ones, UFlow's
+and SMURF's choice on KITTI; ``--gamma`` weights the iterations as ever), with augmentation records that keep
 brightness constancy.  ``--unsup-occlusion fb | range`` runs both directions in the step (2 x batch pairs
 through the model) and leaves the occluded pixels out of the photometric term (train/occlusion.py;
 ``--unsup-occ-thr``: the range map's threshold, ``--unsup-occ-after``: the first step with masks).
@@ -123,6 +124,9 @@ class TrainConfig:
     unsup_smooth_weight: float = 0.05
     unsup_out_penalty: float = 0.5
     unsup_photo: str = "charbonnier"   # the photometric term: "charbonnier" | "census" (7x7 soft census, SMURF's constants)
+    # the smoothness term's order: 1 | 2 (second differences over triples, UFlow's / SMURF's choice on KITTI); both use
+    # unsup_smooth_weight, whose default is a placeholder for either
+    unsup_smooth_order: int = 1
     # Occlusion masks for the photometric term (train/occlusion.py): "none" | "fb" (forward-backward consistency) |
     # "range" (the range map; unsup_occ_thr = the share of a pixel that must map back onto it).  The model then runs
     # both directions as one batch of 2 * batch pairs; the masks apply from step unsup_occ_after on.
@@ -160,6 +164,11 @@ class TrainConfig:
             raise ValueError("unsup_occlusion, unsup_occ_thr and unsup_occ_after take loss='unsup'")
         if self.unsup_photo not in ("charbonnier", "census"):
             raise ValueError(f"unknown unsup_photo {self.unsup_photo!r} (charbonnier or census)")
+        if (isinstance(self.unsup_smooth_order, bool) or not isinstance(self.unsup_smooth_order, int)
+                or self.unsup_smooth_order not in (1, 2)):
+            raise ValueError(f"unknown unsup_smooth_order {self.unsup_smooth_order!r} (1 or 2)")
+        if self.loss != "unsup" and self.unsup_smooth_order != 1:
+            raise ValueError("unsup_smooth_order takes loss='unsup'")
         if self.loss not in ("sequence", "unsup"):
             raise ValueError(f"unknown loss {self.loss!r} (sequence or unsup)")
         if self.loss == "unsup" and self.graph_step:
@@ -209,8 +218,8 @@ class TrainConfig:
 VAL_FIELDS = ("val", "val_every", "val_iters", "val_batch", "val_max_pairs", "chairs_split")
 # likewise left out of latest.json while they are at their defaults
 UNSUP_FIELDS = ("loss", "unsup_eps", "unsup_eps_s", "unsup_edge_kappa", "unsup_smooth_weight", "unsup_out_penalty")
-# (unsup_photo and the unsup_occ* fields are recorded always: the tuple above is pinned by tests/test_unsup.py, which
-# reads its tail as the five floats)
+# (unsup_photo, unsup_smooth_order and the unsup_occ* fields are recorded always: the tuple above is pinned by
+# tests/test_unsup.py, which reads its tail as the five floats)
 
 
 def _adamw(params, cfg: TrainConfig, device, capturable: bool = False):
@@ -356,7 +365,7 @@ class Trainer:
             preds = self.model(img1, img2, train=train_bn, num_flow_updates=cfg.iters, autograd=True)
             loss, metrics = unsup_loss(preds, img1, img2, None, cfg.gamma, cfg.unsup_eps, cfg.unsup_eps_s,
                                        cfg.unsup_edge_kappa, cfg.unsup_smooth_weight, cfg.unsup_out_penalty,
-                                       **({} if cfg.unsup_photo == "charbonnier" else {"photo": cfg.unsup_photo}))
+                                       **self._unsup_switches())
             if self.labelled:      # a labelled set monitors the label-free run: metrics only, no gradient
                 with torch.no_grad():
                     _, sup = sequence_loss(preds.detach(), flow, valid, cfg.gamma, cfg.max_flow)
@@ -400,6 +409,13 @@ class Trainer:
         out = {"loss": loss.detach(), "grad_norm": gnorm.detach(), **{k: v.detach() for k, v in metrics.items()}}
         return out
 
+    def _unsup_switches(self) -> dict:
+        """``unsup_loss``'s ``photo`` and ``smooth_order``, each passed only where it is not the default: the
+        default run makes the call it always made."""
+        cfg = self.cfg
+        return {**({} if cfg.unsup_photo == "charbonnier" else {"photo": cfg.unsup_photo}),
+                **({} if cfg.unsup_smooth_order == 1 else {"smooth_order": cfg.unsup_smooth_order})}
+
     def _occlusion_loss(self, img1, img2, flow, valid):
         """The label-free loss with occlusion masks: both directions as one batch of 2B pairs (forward flows
         in ``preds[:, :B]``, backward flows in ``preds[:, B:]``), the visibility masks of the final prediction
@@ -426,7 +442,7 @@ class Trainer:
                                         cfg.unsup_occ_thr).view(2 * B, *last.shape[1:3])
         loss, metrics = unsup_loss(preds, a, b, mask, cfg.gamma, cfg.unsup_eps, cfg.unsup_eps_s,
                                    cfg.unsup_edge_kappa, cfg.unsup_smooth_weight, cfg.unsup_out_penalty,
-                                   **({} if cfg.unsup_photo == "charbonnier" else {"photo": cfg.unsup_photo}))
+                                   **self._unsup_switches())
         visible = torch.ones((), dtype=torch.float32, device=preds.device) if mask is None else mask.mean()
         metrics = {**metrics, "visible": visible}
         if self.labelled:          # metrics only, from the forward direction
@@ -656,7 +672,7 @@ def main(argv=None):
         else:
             typ = {"int": int, "float": float, "str": str}.get(str(f_.type).replace("Optional[str]", "str"), str)
             ap.add_argument(f"--{f_.name.replace('_', '-')}", type=typ if f_.default is not None else str,
-                            default=f_.default)
+                            default=f_.default, choices=(1, 2) if f_.name == "unsup_smooth_order" else None)
     cfg = config_from_args(ap.parse_args(argv))
     tr = Trainer(cfg)
     tr.fit()

@@ -23,9 +23,18 @@ For iteration i and pixel (y, x) with ``f = flow_preds[i, b, y, x]`` (P = B H W)
    likewise between rows; ``smooth_i = [sum a_x sum_k rho_s(f_k(y, x+1) - f_k(y, x)) + sum a_y
    sum_k rho_s(f_k(y+1, x) - f_k(y, x))] / (2P)`` over all pixels whatever the mask,
    ``rho_s(d) = sqrt(d^2 + eps_s^2)``.  H = 1 or W = 1 has no pairs on that axis.
+4b. ``smooth_order=2`` (UFlow's and SMURF's choice on KITTI: a first-order penalty pulls slanted surfaces
+   towards piecewise-constant flow, a second-order one leaves affine flow free) replaces step 4's sums:
+   ``a2_x(y, x) = exp(-edge_kappa mean_c |image1(y, x+2) - image1(y, x)|)`` for x < W-2, the stride-2
+   image difference across the triple, ``a2_y`` likewise between rows y and y+2;
+   ``D2x_k(y, x) = (f_k(y, x+2) - f_k(y, x+1)) - (f_k(y, x+1) - f_k(y, x))``, ``D2y_k`` likewise down a
+   column; ``smooth_i = [sum a2_x sum_k rho_s(D2x_k) + sum a2_y sum_k rho_s(D2y_k)] / (2P)`` over all
+   pixels whatever the mask, with step 4's ``rho_s``, normalisation and ``smooth_weight``.  A triple never
+   crosses a row end, a frame end or a sample boundary: W < 3 has no triples on the x axis, H < 3 none on
+   the y axis.
 5. ``loss = sum_i gamma^(N-i-1) (photo_i + smooth_weight smooth_i)``.  Metrics (detached, last
    iteration): ``photo`` the mean of pix over the inside masked pixels (NaN without any),
-   ``smooth`` = smooth_{N-1}, ``inside`` the share of the masked pixels (all pixels without a
+   ``smooth`` = smooth_{N-1} of the order in use, ``inside`` the share of the masked pixels (all pixels without a
    mask) that are inside.
 
 ``photo="census"`` replaces steps 2-3 by the soft census term of UnFlow / SMURF (SMURF's constants,
@@ -56,6 +65,7 @@ import torch
 DEFAULTS = dict(gamma=0.8, eps=0.01, eps_s=0.001, edge_kappa=10.0, smooth_weight=0.05, out_penalty=0.5)
 MAX_NATIVE_N = 32
 PHOTO = ("charbonnier", "census")
+SMOOTH_ORDERS = (1, 2)   # step 4 | step 4b
 # the soft census term: SMURF's published constants, not configuration
 CENSUS_R = 3           # 7x7 patch, 48 offsets
 CENSUS_TAU = 0.81      # tau(D) = D / sqrt(0.81 + D^2)
@@ -250,6 +260,33 @@ def smooth_sums(flow_preds, image1, eps_s: float = 0.001, edge_kappa: float = 10
     return torch.stack(rows)
 
 
+def edge_weights2(image1: torch.Tensor, edge_kappa: float):
+    """``(a2_x (B, H, W-2), a2_y (B, H-2, W))`` of step 4b; an axis shorter than 3 has none."""
+    ax = torch.exp(-edge_kappa * (image1[:, :, 2:] - image1[:, :, :-2]).abs().mean(-1))
+    ay = torch.exp(-edge_kappa * (image1[:, 2:] - image1[:, :-2]).abs().mean(-1))
+    return ax, ay
+
+
+def smooth2_sums(flow_preds, image1, eps_s: float = 0.001, edge_kappa: float = 10.0) -> torch.Tensor:
+    """Step 4b's sums (before the division by 2P), (N, 2): over the triples along x and over the triples
+    along y; differentiable in ``flow_preds``, computed in fp64 for fp64 input."""
+    cdt = torch.float64 if flow_preds.dtype == torch.float64 else torch.float32
+    ax, ay = edge_weights2(image1.to(cdt), edge_kappa)
+    rows = []
+    for i in range(flow_preds.shape[0]):
+        f = flow_preds[i].to(cdt)
+        dx = (f[:, :, 2:] - f[:, :, 1:-1]) - (f[:, :, 1:-1] - f[:, :, :-2])
+        dy = (f[:, 2:] - f[:, 1:-1]) - (f[:, 1:-1] - f[:, :-2])
+        rows.append(torch.stack([(ax.unsqueeze(-1) * torch.sqrt(dx ** 2 + eps_s * eps_s)).sum(),
+                                 (ay.unsqueeze(-1) * torch.sqrt(dy ** 2 + eps_s * eps_s)).sum()]))
+    return torch.stack(rows)
+
+
+def _check_order(smooth_order):
+    if isinstance(smooth_order, bool) or not isinstance(smooth_order, int) or smooth_order not in SMOOTH_ORDERS:
+        raise ValueError(f"unsup_loss: unknown smooth_order {smooth_order!r} (1 or 2)")
+
+
 def _census_columns(c: torch.Tensor, smooth: torch.Tensor):
     """Census sums (N, 4) and smoothness sums (N,) -> the (N, 4) layout of ``_assemble`` and the band count."""
     return torch.stack([c[:, 0], smooth, c[:, 1], c[:, 3]], dim=-1), c[-1, 2].detach()
@@ -278,46 +315,61 @@ def _count(mask, P: int, device, dtype):
 
 def unsup_loss_reference(flow_preds, image1, image2, mask=None, gamma: float = 0.8, eps: float = 0.01,
                          eps_s: float = 0.001, edge_kappa: float = 10.0, smooth_weight: float = 0.05,
-                         out_penalty: float = 0.5, photo: str = "charbonnier") -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+                         out_penalty: float = 0.5, photo: str = "charbonnier",
+                         smooth_order: int = 1) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """The golden op (module docstring).  flow_preds (N, B, H, W, 2), channel 0 = x, in pixels;
     image1 / image2 (B, H, W, 3) in [-1, 1]; mask (B, H, W), used where >= 0.5, or None;
-    photo: "charbonnier" (steps 2-3) | "census" (steps 2c-3c)."""
+    photo: "charbonnier" (steps 2-3) | "census" (steps 2c-3c); smooth_order: 1 (step 4) | 2 (step 4b)."""
     _check_photo(photo)
+    _check_order(smooth_order)
     P = flow_preds[0].numel() // 2
     band = None
+    second = None if smooth_order == 1 else smooth2_sums(flow_preds, image1, eps_s, edge_kappa).sum(-1)
     if photo == "census":
         c = census_sums(flow_preds, image1, image2, mask, out_penalty)
-        s, band = _census_columns(c, smooth_sums(flow_preds, image1, eps_s, edge_kappa))
+        s, band = _census_columns(c, smooth_sums(flow_preds, image1, eps_s, edge_kappa) if second is None else second)
     else:
         s = unsup_sums(flow_preds, image1, image2, mask, eps, eps_s, edge_kappa, out_penalty)
+        if second is not None:
+            s = torch.stack([s[:, 0], second, s[:, 2], s[:, 3]], dim=-1)
     loss, mets, _ = _assemble(s, _count(mask, P, s.device, s.dtype), P, gamma, smooth_weight, band)
     return loss, {"photo": mets[0], "smooth": mets[1], "inside": mets[2]}
 
 
 class _UnsupLoss(torch.autograd.Function):
     """Smoothness from the two kernels of csrc/kernels/unsup.hip; the photometric term from the same launches
-    (``photo="charbonnier"``) or from csrc/kernels/census.hip, unsup.hip's then called with a zero photometric scale."""
+    (``photo="charbonnier"``) or from csrc/kernels/census.hip, unsup.hip's then called with a zero photometric scale.
+    ``smooth_order=2``: the smoothness from the two kernels of csrc/kernels/smooth2.hip, unsup.hip's called with a zero
+    smoothness scale -- and not at all with ``photo="census"``, where they would carry nothing."""
 
     @staticmethod
-    def forward(ctx, preds, image1, image2, mask, photo, gamma, eps, eps_s, edge_kappa, smooth_weight, out_penalty):
+    def forward(ctx, preds, image1, image2, mask, photo, smooth_order, gamma, eps, eps_s, edge_kappa, smooth_weight,
+                out_penalty):
         from ..ops import native as nat
 
         P = preds[0].numel() // 2
         prm = nat.unsup_params(eps, eps_s, edge_kappa, out_penalty, preds.device)
-        census = photo == "census"
+        census, second = photo == "census", smooth_order == 2
         # sums in block (census: tile) order; the counts stay exact
-        s = nat.unsup_loss_partials(preds, image1, image2, mask, prm=prm).double().sum(0)
+        if not (census and second):
+            s = nat.unsup_loss_partials(preds, image1, image2, mask, prm=prm).double().sum(0)
+            smooth = s[:, 1]
+        if second:
+            smooth = nat.smooth2_loss_partials(preds, image1, prm=prm).double().sum(0)[:, :2].sum(-1)
+            if not census:
+                s = torch.stack([s[:, 0], smooth, s[:, 2], s[:, 3]], dim=-1)
         band = gray = coef = None
         if census:
             gray = nat.census_gray_planes(image1, image2)
             part, coef = nat.census_loss_partials(preds, image1, image2, mask, prm=prm, gray=gray)
-            s, band = _census_columns(part.double().sum(0), s[:, 1])
+            s, band = _census_columns(part.double().sum(0), smooth)
         loss, mets, w = _assemble(s, _count(mask, P, preds.device, torch.float64), P, gamma, smooth_weight, band)
         zero = torch.zeros_like(w)
-        # the backward's scales: unsup.hip's photometric and smoothness terms, census.hip's term
-        scale = torch.stack([zero if census else w / P, w * (smooth_weight / (2.0 * P)), w / P if census else zero], dim=-1)
-        ctx.photo = photo
-        ctx.save_for_backward(preds, image1, image2, mask, prm, scale, gray, coef)
+        ws = w * (smooth_weight / (2.0 * P))
+        # the backward's scales: unsup.hip's photometric and smoothness terms, census.hip's term, smooth2.hip's term
+        scale = torch.stack([zero if census else w / P, zero if second else ws, w / P if census else zero], dim=-1)
+        ctx.photo, ctx.smooth_order = photo, smooth_order
+        ctx.save_for_backward(preds, image1, image2, mask, prm, scale, gray, coef, ws if second else None)
         mets = mets.float()
         ctx.mark_non_differentiable(mets)
         return loss.float(), mets
@@ -326,28 +378,37 @@ class _UnsupLoss(torch.autograd.Function):
     def backward(ctx, gl, _gm):
         from ..ops import native as nat
 
-        preds, image1, image2, mask, prm, scale, gray, coef = ctx.saved_tensors
+        preds, image1, image2, mask, prm, scale, gray, coef, scale2 = ctx.saved_tensors
         scale = (scale * gl.double()).float()
-        grad = nat.unsup_loss_grad(preds, image1, image2, mask, scale[:, :2].contiguous(), prm=prm)
-        if ctx.photo == "census":
-            nat.census_loss_grad(preds, image1, image2, mask, scale[:, 2].contiguous(), prm=prm, gray=gray, coef=coef, out=grad)
-        return (grad,) + (None,) * 10
+        census, second = ctx.photo == "census", ctx.smooth_order == 2
+        grad = None
+        if not (census and second):
+            grad = nat.unsup_loss_grad(preds, image1, image2, mask, scale[:, :2].contiguous(), prm=prm)
+        if census:
+            grad = nat.census_loss_grad(preds, image1, image2, mask, scale[:, 2].contiguous(), prm=prm, gray=gray, coef=coef,
+                                        out=grad)
+        if second:
+            nat.smooth2_loss_grad(preds, image1, (scale2 * gl.double()).float(), prm=prm, out=grad)
+        return (grad,) + (None,) * 11
 
 
 def unsup_loss(flow_preds, image1, image2, mask=None, gamma: float = 0.8, eps: float = 0.01, eps_s: float = 0.001,
                edge_kappa: float = 10.0, smooth_weight: float = 0.05,
-               out_penalty: float = 0.5, photo: str = "charbonnier") -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+               out_penalty: float = 0.5, photo: str = "charbonnier",
+               smooth_order: int = 1) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """``unsup_loss_reference`` for training: GPU tensors with N <= 32 run the native kernels
     (csrc/kernels/unsup.hip: the partial sums in one pass over the predictions, the gradient in one
     more; ``photo="census"``: the tiled stencil kernels of csrc/kernels/census.hip for the
-    photometric term; no host synchronisation, bitwise repeatable); everything else runs the golden op."""
+    photometric term; ``smooth_order=2``: the two kernels of csrc/kernels/smooth2.hip for the smoothness
+    term; no host synchronisation, bitwise repeatable); everything else runs the golden op."""
     _check_photo(photo)
+    _check_order(smooth_order)
     if not (flow_preds.is_cuda and flow_preds.shape[0] <= MAX_NATIVE_N and flow_preds.dtype != torch.float64):
         return unsup_loss_reference(flow_preds, image1, image2, mask, gamma, eps, eps_s, edge_kappa, smooth_weight,
-                                    out_penalty, photo)
+                                    out_penalty, photo, smooth_order)
     _check(flow_preds, image1, image2, mask)
     m = None if mask is None else mask.float().contiguous()
     loss, mets = _UnsupLoss.apply(flow_preds.float().contiguous(), image1.float().contiguous(), image2.float().contiguous(), m,
-                                  photo, float(gamma), float(eps), float(eps_s), float(edge_kappa), float(smooth_weight),
-                                  float(out_penalty))
+                                  photo, int(smooth_order), float(gamma), float(eps), float(eps_s), float(edge_kappa),
+                                  float(smooth_weight), float(out_penalty))
     return loss, {"photo": mets[0], "smooth": mets[1], "inside": mets[2]}

@@ -35,11 +35,20 @@ backward against the golden op on the same GPU tensors, arms alternated, each ru
 three arms alternated in one process: ``"range"`` at batch 6 without self-supervision, ``"range"`` at batch 12 (what
 4B pairs through the model cost) and self-supervision on at batch 6.
 
-  python tools/unsup_bench.py [--photo census | --occlusion range | --selfsup] [--out profiles/unsup_loss_overhead.txt]
+``--smooth-order 2`` measures the second-order smoothness term (csrc/kernels/smooth2.hip; default output
+``profiles/smooth2_overhead.txt``): (a) its two launches with the bytes they must move, and each kernel's registers and
+occupancy from the compiler's resource-usage remarks; (b) ``unsup_loss(..., smooth_order=2)`` against the golden op with
+``smooth_order=2``; (c) the training step with ``unsup_smooth_order=2`` against ``unsup_smooth_order=1``, the step as it
+was.  ``--photo census`` combines with it in (b) and (c).
+
+  python tools/unsup_bench.py [--photo census | --smooth-order 2 | --occlusion range | --selfsup] [--out profiles/unsup_loss_overhead.txt]
 """
 import argparse
 import os
+import re
+import subprocess
 import sys
+import tempfile
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -110,10 +119,53 @@ def census_launches(dev, reps):
     return out
 
 
-def pair(dev, reps, photo="charbonnier"):
+def smooth2_launches(dev, reps):
+    preds, i1, _ = inputs(dev)
+    P = B * H * W
+    prm = nat.unsup_params(0.01, 0.001, 10.0, 0.5, dev)
+    part = torch.empty(nat.smooth2_loss_blocks(P), N, 4, device=dev)
+    grad = torch.zeros_like(preds)
+    scale = torch.full((N,), 1.0 / P, device=dev)
+    mb = lambda ts: sum(t.numel() * t.element_size() for t in ts) / 1e6
+    rows = [("smooth2_loss", lambda: nat.ops().smooth2_loss([preds, i1, prm, part], [B, H, W, N]), (preds, i1, part),
+             "predictions, image 1, partials"),
+            ("smooth2_loss_bwd", lambda: nat.ops().smooth2_loss_bwd([preds, i1, prm, scale, grad], [B, H, W, N, 0]),
+             (preds, i1, grad), "predictions, image 1, gradient written"),
+            ("smooth2_loss_bwd add", lambda: nat.ops().smooth2_loss_bwd([preds, i1, prm, scale, grad], [B, H, W, N, 1]),
+             (preds, i1, grad, grad), "predictions, image 1, gradient read and written")]
+    return [(name, events(fn, dev, reps), mb(ts), what) for name, fn, ts, what in rows]
+
+
+def resource_usage(src):
+    """(kernel, VGPRs, occupancy in waves per SIMD) of every kernel of a .hip file, from the compiler's
+    resource-usage remarks: a compile, no GPU needed.  None where there is no compiler."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(hipcc):
+        return None
+    with tempfile.TemporaryDirectory() as d:
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(root, src), "-o",
+                            os.path.join(d, "o.o"), "-Rpass-analysis=kernel-resource-usage"],
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        return None
+    out, name = [], None
+    for line in r.stdout.splitlines():
+        m = re.search(r"remark:\s+(Function Name|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\S+)", line)
+        if not m:
+            continue
+        if m.group(1) == "Function Name":
+            name = subprocess.run(["c++filt", m.group(2)], stdout=subprocess.PIPE, text=True).stdout.strip() or m.group(2)
+            out.append([re.search(r"(\w+(<\w+>)?)\(", name.replace("(anonymous namespace)::", "")).group(1)])
+        elif out:
+            out[-1].append(m.group(2))
+    return out
+
+
+def pair(dev, reps, photo="charbonnier", order=1):
     preds, i1, i2 = inputs(dev)
     f = preds.clone().requires_grad_(True)
-    kw = {} if photo == "charbonnier" else {"photo": photo}
+    kw = {**({} if photo == "charbonnier" else {"photo": photo}), **({} if order == 1 else {"smooth_order": order})}
 
     def run(loss_fn):
         def step():
@@ -137,7 +189,11 @@ def pair(dev, reps, photo="charbonnier"):
 def training(args, dev):
     total = args.warmup + args.block * args.rounds
     kw = dict(arch=args.arch, steps=total, batch=BATCH, iters=args.iters, size=(384, 512), log_every=10 ** 9)
-    if args.photo == "census":
+    if args.smooth_order == 2:
+        photo = {} if args.photo == "charbonnier" else {"unsup_photo": args.photo}
+        arms = {"order 2": Trainer(TrainConfig(loss="unsup", unsup_smooth_order=2, **photo, **kw)),
+                "order 1": Trainer(TrainConfig(loss="unsup", **photo, **kw))}
+    elif args.photo == "census":
         arms = {"census": Trainer(TrainConfig(loss="unsup", unsup_photo="census", **kw)),
                 "charbonnier": Trainer(TrainConfig(loss="unsup", **kw))}
     else:
@@ -427,7 +483,9 @@ def main():
     ap.add_argument("--selfsup", action="store_true", help="measure self-supervision instead of the loss")
     ap.add_argument("--occlusion", default=None, choices=("fb", "range"), help="measure the occlusion masks instead of the loss")
     ap.add_argument("--photo", default="charbonnier", choices=("charbonnier", "census"))
-    ap.add_argument("--out", default=None, help="default: profiles/unsup_loss_overhead.txt, census_loss_overhead.txt with --photo census")
+    ap.add_argument("--smooth-order", type=int, default=1, choices=(1, 2), help="2: measure the second-order smoothness term")
+    ap.add_argument("--out", default=None, help="default: profiles/unsup_loss_overhead.txt, census_loss_overhead.txt with --photo census, "
+                    "smooth2_overhead.txt with --smooth-order 2")
     ap.add_argument("--reps", type=int, default=500)
     ap.add_argument("--pair-reps", type=int, default=20)
     ap.add_argument("--block", type=int, default=20, help="steps per block")
@@ -446,19 +504,34 @@ def main():
         assert torch.cuda.is_available(), "unsup_bench measures on the GPU"
         args.out = args.out or "profiles/occlusion_overhead.txt"
         return occlusion_main(args, torch.device("cuda", 0))
-    args.out = args.out or ("profiles/census_loss_overhead.txt" if census else "profiles/unsup_loss_overhead.txt")
+    order2 = args.smooth_order == 2
+    args.out = args.out or ("profiles/smooth2_overhead.txt" if order2 else
+                            "profiles/census_loss_overhead.txt" if census else "profiles/unsup_loss_overhead.txt")
     assert torch.cuda.is_available(), "unsup_bench measures on the GPU"
     dev = torch.device("cuda", 0)
     mean = lambda v: sum(v) / len(v)
-    lines = [f"label-free loss ({'census' if census else 'photometric'} + edge-aware smoothness), {torch.cuda.get_device_name(dev)}",
+    lines = [f"label-free loss ({'census' if census else 'photometric'} + edge-aware {'second-order ' if order2 else ''}smoothness), "
+             f"{torch.cuda.get_device_name(dev)}",
              f"predictions (N, B, H, W) = ({N}, {B}, {H}, {W}), fp32; no mask", ""]
-    if census:
+    if order2:
+        lines += [f"(a) GPU time per launch, device events over {args.reps} repetitions:"]
+        for name, us, mbytes, what in smooth2_launches(dev, args.reps):
+            lines.append(f"    {name:20s} {us:8.1f} us   {mbytes:6.1f} MB at least ({what})  -> {mbytes / us * 1e3:6.0f} GB/s of them")
+        lines += ["    (neighbouring flows and image texels are re-reads that the caches serve; they are not in the byte counts;",
+                  "     the training step uses the adding form of the backward: unsup.hip's or census.hip's launch writes the gradient first)"]
+        usage = resource_usage("csrc/kernels/smooth2.hip")
+        if usage is None:
+            lines += ["    compiler resource usage: no compiler here, not recorded"]
+        for row in usage or []:
+            lines.append("    compiler resource usage (gfx950): {:32s} VGPRs {}, scratch {} bytes/lane, occupancy {} waves/SIMD".format(*row))
+        lines += [""]
+    elif census:
         lines += [f"(a) GPU time per launch, device events over {args.reps} repetitions:"]
         for name, us, mbytes, what in census_launches(dev, args.reps):
             lines.append(f"    {name:16s} {us:8.1f} us   {mbytes:6.1f} MB at least ({what})  -> {mbytes / us * 1e3:6.0f} GB/s of them")
         lines += ["    (the halo's samples and the texel gathers are re-reads that the caches serve; they are not in the byte counts;",
                   "     the census loss also runs unsup_loss and unsup_loss_bwd for the smoothness term: profiles/unsup_loss_overhead.txt)", ""]
-    kt = None if census else launches(dev, args.reps)
+    kt = None if census or order2 else launches(dev, args.reps)
     if kt:
         lines += [f"(a) GPU time per launch, device events over {args.reps} repetitions:",
                   f"    unsup_loss     {kt['fwd']:8.1f} us   {kt['fwd_mb']:6.1f} MB at least (predictions, both images, partials)"
@@ -467,7 +540,7 @@ def main():
                   f"  -> {kt['bwd_mb'] / kt['bwd'] * 1e3:6.0f} GB/s of them",
                   "    (neighbouring flows and the texel gathers are re-reads that the caches serve; they are not in the byte counts)", ""]
     print("\n".join(lines), flush=True)
-    times, peak = pair(dev, args.pair_reps, args.photo)
+    times, peak = pair(dev, args.pair_reps, args.photo, args.smooth_order)
     spread = max(abs(v[0] - v[1]) for v in times.values())
     gain = mean(times["torch"]) - mean(times["native"])
     lines += [f"(b) loss forward + backward, {args.pair_reps} repetitions per run, arms alternated native / torch x 2:"]
@@ -490,6 +563,8 @@ def main():
                          + ", ".join(f"{v:.1f}" for v in rate[k]) + f"]   skipped steps: {skipped[k]}")
         lines += [f"    {first} - {second}: {ms(u) - ms(s):+.2f} ms/step ({100 * (u - s) / s:+.1f} % pairs/s); largest spread between "
                   f"blocks of one arm {max(max(v) - min(v) for v in rate.values()):.1f} pairs/s",
+                  f"    ({second} is the step as it was: unsup_smooth_order=1 changes nothing in it; both arms also run the sequence loss's "
+                  "forward kernel for the EPE metrics)" if order2 else
                   "    (both arms also run the sequence loss's forward kernel for the EPE metrics of the labelled synthetic set)" if census
                   else "    (the unsup step also runs the sequence loss's forward kernel for the EPE metrics of the labelled synthetic set)", ""]
     lines += ["Not measured: accuracy.  There is no checkpoint and no real data here, and the loss's default weights are placeholders.", ""]
