@@ -411,6 +411,20 @@ int jr_smooth2_loss_bwd(const float* pred, const float* img1, const float* prm, 
 int jr_range_splat(const float* flow_fw, const float* flow_bw, int* acc, int B, int H, int W, hipStream_t stream);
 int jr_range_visible(const float* flow_fw, const float* flow_bw, const int* acc, float* vis, int B, int H, int W,
                      int T, hipStream_t stream);
+// Frame interpolation by forward splatting (interp.hip; models/reference.py:interpolate_frames, bitwise, acc
+// included).  frame0 / frame1 uint8 [B][H0][W0][3] (frame 1 and frame 2 of the pair), flow0 (1 -> 2) / flow1
+// (2 -> 1) fp32 [B][H][W][2] read inside the frame's rectangle (H0, W0, top, left) only -- tensors, or (slot, as
+// in jr_fb_check) float offsets off0 / off1 from a base address read at run time; 8-byte aligned.  occ
+// (optional) uint8 [2][B][H][W]; par int32 [2] = (tq, Dmin) of the time, on the device.  jr_interp_splat ADDS
+// (w k, w k R, w k G, w k B) per tap into acc int64 [2][B][H0][W0][4] (16-byte aligned) with integer atomics,
+// so the caller clears it first; jr_interp_resolve blends the two directions into out uint8 [B][H0][W0][3]
+// and holes uint8 [B][H0][W0].  H0 * W0 <= JR_INTERP_MAX_PIXELS keeps every sum inside an int64.
+#define JR_INTERP_MAX_PIXELS (1L << 30)
+int jr_interp_splat(const void* frame0, const void* frame1, const float* flow0, const float* flow1, const void* slot,
+                    long off0, long off1, const void* occ, long long* acc, const int* par, int B, int H, int W, int H0,
+                    int W0, int top, int left, hipStream_t stream);
+int jr_interp_resolve(const void* frame0, const void* frame1, const long long* acc, const int* par, void* out,
+                      void* holes, int B, int H0, int W0, hipStream_t stream);
 // Self-supervision for label-free training (selfsup.hip; train/selfsup.py, crop_resize bitwise).
 // jr_crop_resize: x, out fp32 [B][H][W][C] (C = 1, 2, 3; distinct buffers), the centre crop [c, H - c) x
 // [c, W - c) resampled bilinearly to H x W; prm fp32 [6] = (rx, ry, scale[0..3]) on the device; c >= 1,

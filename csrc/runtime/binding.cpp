@@ -2000,6 +2000,92 @@ static Launch make_warp_frames(const TList& t, const IList& i, std::vector<at::T
   };
 }
 
+// ------------------------------------------- frame interpolation by forward splatting
+// (kernels interp.hip; models/reference.py:interpolate_frames).  Both ops read (tq, Dmin) of their time from
+// row k of par (int32 [K][2], on the device), so another t or min_cover records and captures nothing.
+// interp_splat: t = [frame1, frame2 (uint8 [B][H0][W0][3]), flow_fw?, flow_bw? (fp32 [B][H][W][2]), occ? (uint8
+// [2][B][H][W]), acc (int64 [2][B][H0][W0][4], ADDED to: cleared by the caller), par, out_slot?],
+// i = [B, H, W, H0, W0, top, left, k(, off_fw, off_bw)]; with out_slot the flows are read at float offsets from
+// the address it holds (see make_fb_check).  interp_resolve: t = [frame1, frame2, acc, par, frame_t (uint8
+// [B][H0][W0][3]), holes (uint8 [B][H0][W0])], i = [B, H0, W0, k].
+static bool interp_is_u8(const at::Tensor& v, int64_t n) {
+  return v.defined() && v.is_cuda() && v.scalar_type() == at::kByte && v.is_contiguous() && v.numel() == n;
+}
+// the checks both ops share: sizes, the two frames, acc and row k of par -> the row's address
+static const int* interp_common(const std::string& op, int64_t B, int64_t H0, int64_t W0, int64_t k, const at::Tensor& f1,
+                                const at::Tensor& f2, const at::Tensor& acc, const at::Tensor& par) {
+  TORCH_CHECK(B >= 1 && 2 * B <= 65535, op, ": dirs * B must be at most 65535, got B = ", B);
+  TORCH_CHECK(H0 >= 1 && W0 >= 1 && H0 <= JR_INTERP_MAX_PIXELS && W0 <= JR_INTERP_MAX_PIXELS && H0 * W0 <= JR_INTERP_MAX_PIXELS,
+              op, ": sizes (H0 * W0 must be at most 2^30: an int64 cell holds below 2^20 per source)");
+  const int64_t P = B * H0 * W0;
+  TORCH_CHECK(interp_is_u8(f1, 3 * P) && interp_is_u8(f2, 3 * P), op, ": frames must be contiguous device uint8 [B][H0][W0][3]");
+  TORCH_CHECK(acc.defined() && acc.is_cuda() && acc.scalar_type() == at::kLong && acc.is_contiguous() && acc.numel() == 8 * P,
+              op, ": acc must be a contiguous device int64 [2][B][H0][W0][4]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(acc.data_ptr()) % 16 == 0, op, ": acc must be 16-byte aligned");
+  TORCH_CHECK(par.defined() && par.is_cuda() && par.scalar_type() == at::kInt && par.is_contiguous() && par.numel() >= 2 &&
+                  par.numel() % 2 == 0, op, ": par must be a contiguous device int32 [K][2]");
+  TORCH_CHECK(k >= 0 && k < par.numel() / 2, op, ": the time index k = ", k, " must lie in [0, ", par.numel() / 2, ")");
+  check_one_device(op, acc, {f1, f2, par});
+  check_no_alias(op, "acc", acc, {f1, f2, par});
+  return par.data_ptr<int>() + 2 * k;
+}
+static Launch make_interp_splat(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  const std::string op = "interp_splat";
+  at::Tensor f1 = opt(t, 0), f2 = opt(t, 1), flow[2] = {opt(t, 2), opt(t, 3)}, occ = opt(t, 4), acc = opt(t, 5);
+  at::Tensor par = opt(t, 6), slot = opt(t, 7);
+  const int64_t B = i[0], H = i[1], W = i[2], H0 = i[3], W0 = i[4], top = i[5], left = i[6];
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= 0x3fffffff && W <= 0x3fffffff && H * W <= 0x3fffffff, op, ": sizes");
+  TORCH_CHECK(H0 >= 1 && W0 >= 1 && top >= 0 && left >= 0 && top + H0 <= H && left + W0 <= W, op,
+              ": the window (H0, W0, top, left) must lie inside the map");
+  const int* pp = interp_common(op, B, H0, W0, i[7], f1, f2, acc, par);
+  const int64_t M = B * H * W;
+  if (occ.defined()) {
+    TORCH_CHECK(interp_is_u8(occ, 2 * M), op, ": occ must be a contiguous device uint8 [2][B][H][W]");
+    check_no_alias(op, "acc", acc, {occ});
+  }
+  int64_t off[2] = {0, 0};
+  if (slot.defined()) {
+    TORCH_CHECK(slot.is_cuda() && slot.scalar_type() == at::kLong && slot.numel() == 1, op, ": out_slot must be one device int64");
+    TORCH_CHECK(!flow[0].defined() && !flow[1].defined() && i.size() == 10, op,
+                ": out_slot takes [.., off_fw, off_bw] and no flow tensors");
+    off[0] = i[8]; off[1] = i[9];
+    TORCH_CHECK(off[0] >= 0 && off[1] >= 0 && off[0] % 2 == 0 && off[1] % 2 == 0, op, ": flow offsets (8-byte aligned)");
+    check_no_alias(op, "acc", acc, {slot});
+  } else {
+    TORCH_CHECK(i.size() == 8, op, ": expected [B, H, W, H0, W0, top, left, k] with flow tensors");
+    for (int d = 0; d < 2; ++d) check_f32_n(op, d ? "flow_bw" : "flow_fw", flow[d], 2 * M, "[B][H][W][2]", 8);
+    check_one_device(op, acc, {flow[0], flow[1]});
+    check_no_alias(op, "acc", acc, {flow[0], flow[1]});
+  }
+  check_one_device(op, acc, {occ, slot});
+  hold(keep, {f1, f2, flow[0], flow[1], occ, acc, par, slot});
+  const void *p1 = f1.data_ptr(), *p2 = f2.data_ptr(), *sp = ptr(slot), *mp = ptr(occ);
+  const float* w0 = (const float*)ptr(flow[0]);
+  const float* w1 = (const float*)ptr(flow[1]);
+  long long* ap = (long long*)acc.data_ptr();
+  const long a0 = (long)off[0], a1 = (long)off[1];
+  const int b = (int)B, h = (int)H, w = (int)W, h0 = (int)H0, w0n = (int)W0, tp = (int)top, lf = (int)left;
+  return [=](hipStream_t s, int) { return jr_interp_splat(p1, p2, w0, w1, sp, a0, a1, mp, ap, pp, b, h, w, h0, w0n, tp, lf, s); };
+}
+static Launch make_interp_resolve(const TList& t, const IList& i, std::vector<at::Tensor>& keep) {
+  const std::string op = "interp_resolve";
+  at::Tensor f1 = opt(t, 0), f2 = opt(t, 1), acc = opt(t, 2), par = opt(t, 3), out = opt(t, 4), holes = opt(t, 5);
+  const int64_t B = i[0], H0 = i[1], W0 = i[2];
+  const int* pp = interp_common(op, B, H0, W0, i[3], f1, f2, acc, par);
+  const int64_t P = B * H0 * W0;
+  TORCH_CHECK(interp_is_u8(out, 3 * P), op, ": frame_t must be a contiguous device uint8 [B][H0][W0][3]");
+  TORCH_CHECK(interp_is_u8(holes, P), op, ": holes must be a contiguous device uint8 [B][H0][W0]");
+  check_one_device(op, acc, {out, holes});
+  check_no_alias(op, "frame_t", out, {f1, f2, acc, par, holes});
+  check_no_alias(op, "holes", holes, {f1, f2, acc, par});
+  hold(keep, {f1, f2, acc, par, out, holes});
+  const void *p1 = f1.data_ptr(), *p2 = f2.data_ptr();
+  const long long* ap = (const long long*)acc.data_ptr();
+  void *op_ = out.data_ptr(), *hp = holes.data_ptr();
+  const int b = (int)B, h0 = (int)H0, w0 = (int)W0;
+  return [=](hipStream_t s, int) { return jr_interp_resolve(p1, p2, ap, pp, op_, hp, b, h0, w0, s); };
+}
+
 // -------------------------------------------------------- training-data augmentation
 // (kernels augment.hip).  One row per layout of a batch (kernels.h: JR_AUGMENT_*); a builder per launch takes a row.
 struct AugmentLayout {
@@ -2539,6 +2625,8 @@ static const std::vector<OpRow>& op_table() {
       row_ti("forward_project", 4, 4, make_forward_project),
       row_ti("fb_check", 7, 9, make_fb_check),           // flow tensors 7, a plan's output slot 9
       row_ti("warp_frames", 8, 10, make_warp_frames),    // flow tensors 8, a plan's output slot 10
+      row_ti("interp_splat", 8, 10, make_interp_splat),  // flow tensors 8, a plan's output slot 10
+      row_ti("interp_resolve", 4, 4, make_interp_resolve),
       row_t("memset", make_memset),
       row_t("copy", make_copy),
       row_ti("copy_channels", 4, 4, make_copy_channels),

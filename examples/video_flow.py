@@ -4,7 +4,7 @@
 previous pair's refinement loop and this pair's encoders + correlation
 pyramid, and returns the previous pair's flow; ``flush()`` drains the last.
 
-  python examples/video_flow.py frame_0000.png frame_0001.png ... [--arch raft_small] [--iters 12] [--warm-start | --bidirectional [--warp [--out DIR]]]
+  python examples/video_flow.py frame_0000.png frame_0001.png ... [--arch raft_small] [--iters 12] [--warm-start | --bidirectional [--warp | --interpolate K] [--out DIR]]
 
 ``--warm-start`` runs the synchronous path instead (``RaftEngine.forward``) and
 starts every pair after the first from the previous pair's flow, projected
@@ -26,6 +26,13 @@ the mean absolute error in 8-bit levels over the kept pixels and the share of pi
 direction over the sequence -- a label-free check of the flow, not an accuracy figure (with
 random weights it says nothing about accuracy at all); ``--out DIR`` writes ``warped_fw_NNNN.png``
 (the PNG encoder runs on the host between the calls, so the printed pairs/s then measures it too).
+
+``--bidirectional --interpolate K`` adds K frames between the two of every pair, at the times
+``t = j / (K + 1)``, from the same call (``forward(bidirectional=True, interpolate=t)``): every
+pixel of both frames is splatted forward along a fraction of its flow and the contributions are
+normalised, on the GPU, bit for bit repeatable.  It prints the share of hole pixels (cells
+nothing reached, filled from the nearer frame) per ``t`` over the sequence; ``--out DIR`` writes
+``interp_NNNN_j.png``.  With random weights the frames say nothing about interpolation quality.
 
 Without frames a synthetic drifting sequence is used.  Needs an MI355X (the
 native engine); prints the pairs/s of the steady state.
@@ -69,11 +76,18 @@ def main():
                     help="synchronous forwards that return both directions' flows and the occlusion masks")
     ap.add_argument("--warp", action="store_true",
                     help="with --bidirectional: also the motion-compensated frames and the masked photometric error")
-    ap.add_argument("--out", default=None, help="with --warp: a directory for warped_fw_NNNN.png")
+    ap.add_argument("--interpolate", type=int, default=0, metavar="K",
+                    help="with --bidirectional: also K frames between the two of every pair, at t = j / (K + 1) (1 to 8)")
+    ap.add_argument("--out", default=None, help="with --warp: a directory for warped_fw_NNNN.png; with --interpolate: "
+                                                "for interp_NNNN_j.png")
     args = ap.parse_args()
     assert not (args.warm_start and args.bidirectional), "--warm-start and --bidirectional exclude each other"
     assert args.bidirectional or not args.warp, "--warp needs --bidirectional"
-    assert args.warp or args.out is None, "--out needs --warp"
+    assert args.bidirectional or not args.interpolate, "--interpolate needs --bidirectional"
+    assert not (args.warp and args.interpolate), "--warp and --interpolate exclude each other (one consumer per plan)"
+    assert 0 <= args.interpolate <= 8, "--interpolate takes 1 to 8 frames per pair"
+    assert args.warp or args.interpolate or args.out is None, "--out needs --warp or --interpolate"
+    times = [j / (args.interpolate + 1) for j in range(1, args.interpolate + 1)]
     if args.out:
         os.makedirs(args.out, exist_ok=True)
     assert torch.cuda.is_available(), "the pipelined engine runs on the GPU"
@@ -86,12 +100,22 @@ def main():
     flows, prev, padder = [], None, None
     flows_bw, occ_fw, occ_bw = [], [], []
     photo, frame = None, None   # --warp: the running (2, 2) int64 sums over the sequence, on the device
+    n_holes = None              # --interpolate: the running hole counts (K,) over the sequence, on the device
     t0, n_pairs = None, 0
     for img in frames(args.frames, raw=args.bidirectional):
         if args.bidirectional:   # raw frames: padded, cropped and windowed by the engine
             cur = img.to(dev)
             if prev is not None:
-                res = eng.forward(prev, cur, args.iters, return_all_iters=False, bidirectional=True, warp=args.warp)
+                res = eng.forward(prev, cur, args.iters, return_all_iters=False, bidirectional=True, warp=args.warp,
+                                  interpolate=times or None)
+                if times:
+                    holes = res.holes.sum((1, 2, 3))
+                    n_holes = holes if n_holes is None else n_holes + holes
+                    frame = tuple(cur.shape[1:3])
+                    if args.out:
+                        for j in range(len(times)):
+                            write_png(os.path.join(args.out, f"interp_{len(flows):04d}_{j + 1}.png"),
+                                      res.frames[j, 0].cpu().numpy())
                 if args.warp:
                     photo = res.photo.sum(1) if photo is None else photo + res.photo.sum(1)
                     frame = tuple(cur.shape[1:3])
@@ -144,6 +168,9 @@ def main():
         cov = cov / len(flows)   # the sums run over every pair of the sequence
         print("masked photometric error (8-bit levels) / pixels kept: "
               f"1->2 {float(mae[0]):.2f} / {100 * float(cov[0]):.1f} %, 2->1 {float(mae[1]):.2f} / {100 * float(cov[1]):.1f} %")
+    if n_holes is not None:
+        share = n_holes.cpu().double() / (len(flows) * cur.shape[0] * frame[0] * frame[1])
+        print("interpolated frames, hole pixels: " + ", ".join(f"t = {t:.3f}: {100 * float(v):.2f} %" for t, v in zip(times, share)))
     print(f"{len(flows)} flow fields {tuple(flows[0].shape) if flows else ()}; "
           f"steady state {n_pairs / dt if dt > 0 and n_pairs else float('nan'):.1f} pairs/s")
 

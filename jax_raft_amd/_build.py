@@ -53,6 +53,7 @@ KERNEL_SOURCES = [
     CSRC / "kernels" / "warm.hip",
     CSRC / "kernels" / "fbcheck.hip",
     CSRC / "kernels" / "framewarp.hip",
+    CSRC / "kernels" / "interp.hip",
     CSRC / "kernels" / "augment.hip",
     CSRC / "kernels" / "metrics.hip",
     CSRC / "kernels" / "unsup.hip",

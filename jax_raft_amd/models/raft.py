@@ -78,7 +78,8 @@ class RAFT(nn.Module):
 
     def forward(self, image1, image2, train: bool = False, num_flow_updates: int = 12, return_all_iters: bool = True,
                 flow_init=None, return_flow_low: bool = False, bidirectional: bool = False, fb_alpha: float = 0.01,
-                fb_beta: float = 0.5, warp: bool = False, **engine_kw):
+                fb_beta: float = 0.5, warp: bool = False, interpolate=None, interp_min_cover: float = 1.0 / 64,
+                **engine_kw):
         """Upsampled flows of every refinement iteration, (num_flow_updates, B, H, W, 2)
         (reference semantics, ``model.py:605``).  ``return_all_iters=False`` (inference
         serving mode) upsamples and returns only the final flow, shape (1, B, H, W, 2).
@@ -105,8 +106,21 @@ class RAFT(nn.Module):
         returns :class:`~jax_raft_amd.models.reference.BidirectionalWarp`: the same four fields,
         the motion-compensated frames ``warped_fw`` / ``warped_bw`` (B, H0, W0, 3) uint8 and
         ``photo`` (2, B, 2) int64, the masked photometric sums (:func:`reference.warp_frames`) --
-        the last kernel of the same plan, or the golden warp elsewhere."""
+        the last kernel of the same plan, or the golden warp elsewhere.
+
+        ``bidirectional=True, interpolate=t`` (uint8 frames; ``t`` a float or a sequence of 1 to 8
+        floats strictly between 0 and 1; not together with ``warp=True``; anything else is a
+        ``ValueError``) returns :class:`~jax_raft_amd.models.reference.BidirectionalInterp`: the
+        same four fields, ``frames`` (K, B, H0, W0, 3) uint8 -- the frames at the times ``t``
+        between frame 1 and frame 2 by forward splatting along both flows -- and ``holes``
+        (K, B, H0, W0) bool (:func:`reference.interpolate_frames` with ``min_cover =
+        interp_min_cover``) -- the last kernels of the same plan, or the golden op elsewhere."""
         image1, image2 = _as_tensor(image1), _as_tensor(image2)
+        if interpolate is not None and not bidirectional:
+            raise ValueError("interpolate=t requires bidirectional=True (the splat uses both flows and their "
+                             "occlusion masks)")
+        if interpolate is not None and warp:
+            raise ValueError("bidirectional: interpolate and warp=True exclude each other (one consumer per call)")
         corr = check_corr(engine_kw.get("corr", "volume"))
         if corr == "on_demand":
             # what the on-demand engine does not lower, refused here (an engine's refusal would read
@@ -134,8 +148,15 @@ class RAFT(nn.Module):
             if warp and not (image1.dtype == torch.uint8 and image2.dtype == torch.uint8):
                 raise ValueError(f"bidirectional, warp=True requires uint8 frames (the warp samples the frames as "
                                  f"given), got {image1.dtype}")
+            times = None
+            if interpolate is not None:
+                if not (image1.dtype == torch.uint8 and image2.dtype == torch.uint8):
+                    raise ValueError(f"bidirectional, interpolate=t requires uint8 frames (the splat reads the frames "
+                                     f"as given), got {image1.dtype}")
+                _, many = R.interp_times(interpolate, interp_min_cover, R.INTERP_MAX_TIMES)   # ValueError before any work
+                times = (list(interpolate) if many else [interpolate], interp_min_cover)
             return self._forward_bidirectional(image1, image2, num_flow_updates, return_all_iters, fb_alpha, fb_beta,
-                                               engine_kw, warp)
+                                               engine_kw, warp, times)
         B, H, W, _ = image1.shape
         assert (H, W) == tuple(image2.shape[-3:-1]), "input images should have the same shape"
         warm = dict(flow_init=flow_init, return_flow_low=return_flow_low)
@@ -169,11 +190,11 @@ class RAFT(nn.Module):
         return self.forward_reference(image1, image2, train, num_flow_updates, return_all_iters, **warm, corr=corr)
 
     def _forward_bidirectional(self, image1, image2, num_flow_updates, return_all_iters, alpha, beta, engine_kw,
-                               warp=False):
+                               warp=False, times=None):
         """``forward(bidirectional=True)``: the native engine's bidirectional plan for a model on
         the GPU it can lower (float or uint8 frames); everywhere else two passes of
         :meth:`forward` and the golden check of their final flows (+ the golden warp of both
-        frames with ``warp``)."""
+        frames with ``warp``, or the golden interpolation at ``times = (list of t, min_cover)``)."""
         dev = self._param_device()
         if dev.type == "cuda" and self._lowering_error is None:
             eng = self._try_engine(dev, {k: v for k, v in engine_kw.items() if k not in ("autograd", "fused")})
@@ -184,7 +205,8 @@ class RAFT(nn.Module):
                 if not image1.is_cuda and image1.dtype != torch.uint8:
                     image1, image2 = image1.to(dev), image2.to(dev)
                 return eng.forward(image1, image2, num_flow_updates, return_all_iters=return_all_iters,
-                                   bidirectional=True, fb_alpha=alpha, fb_beta=beta, warp=warp)
+                                   bidirectional=True, fb_alpha=alpha, fb_beta=beta, warp=warp,
+                                   **({} if times is None else dict(interpolate=times[0], interp_min_cover=times[1])))
         with torch.no_grad():
             fw = self.forward(image1, image2, False, num_flow_updates, return_all_iters, **engine_kw)
             bw = self.forward(image2, image1, False, num_flow_updates, return_all_iters, **engine_kw)
@@ -194,6 +216,12 @@ class RAFT(nn.Module):
                 warped_fw, photo_fw = R.warp_frames(f2, fw[-1].contiguous(), occ_fw, f1)
                 warped_bw, photo_bw = R.warp_frames(f1, bw[-1].contiguous(), occ_bw, f2)
                 return R.BidirectionalWarp(fw, bw, occ_fw, occ_bw, warped_fw, warped_bw, torch.stack([photo_fw, photo_bw]))
+            if times is not None:   # likewise
+                f1, f2 = image1.to(fw.device), image2.to(fw.device)
+                res = [R.interpolate_frames(f1, f2, fw[-1].contiguous(), bw[-1].contiguous(), t, occ_fw, occ_bw,
+                                            min_cover=times[1]) for t in times[0]]
+                return R.BidirectionalInterp(fw, bw, occ_fw, occ_bw, torch.stack([r[0] for r in res]),
+                                             torch.stack([r[1] for r in res]))
         return R.BidirectionalFlow(fw, bw, occ_fw, occ_bw)
 
     def _forward_u8(self, image1, image2, train, num_flow_updates, return_all_iters, engine_kw, warm):

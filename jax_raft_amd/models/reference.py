@@ -37,6 +37,11 @@ __all__ = [
     "BidirectionalFlow",
     "warp_frames",
     "BidirectionalWarp",
+    "interpolate_frames",
+    "interp_params",
+    "interp_times",
+    "BidirectionalInterp",
+    "CONSISTENT",
 ]
 
 
@@ -665,3 +670,139 @@ def warp_frames(src: torch.Tensor, flow: torch.Tensor, occ: Optional[torch.Tenso
     d = (w.to(torch.int64) - own.to(torch.int64)).abs().sum(-1)
     photo = torch.stack([(d * keep).sum((1, 2)), keep.sum((1, 2))], dim=-1)
     return warped, photo
+
+
+class BidirectionalInterp(NamedTuple):
+    """What ``bidirectional=True, interpolate=t`` returns: :class:`BidirectionalFlow`'s four fields,
+    then ``frames`` (K, B, H0, W0, 3) uint8, the frames at the K times ``t`` between frame 1
+    (``t = 0``) and frame 2 (``t = 1``), and ``holes`` (K, B, H0, W0) bool, the pixels nothing was
+    splatted onto, which hold the nearer input frame's pixel (:func:`interpolate_frames`)."""
+    flows_fw: torch.Tensor
+    flows_bw: torch.Tensor
+    occ_fw: torch.Tensor
+    occ_bw: torch.Tensor
+    frames: torch.Tensor
+    holes: torch.Tensor
+
+
+CONSISTENT = 16             # the splat confidence of a pixel its own mask does not call occluded (occluded: 1); untuned
+INTERP_COVER_UNIT = 1 << 20   # D of a cell covered fully by consistent pixels of both directions
+INTERP_MAX_TIMES = 8          # times per model / engine call (each adds a clear and two kernels to the plan)
+INTERP_MAX_MAPS = 65535       # directions * B of one splat launch (its grid's second dimension)
+INTERP_MAX_PIXELS = 1 << 30   # H0 * W0 (warp_frames' limit): keeps every sum inside an int64
+
+
+def interp_params(t: float, min_cover: float = 1.0 / 64) -> Tuple[int, int]:
+    """Step 0 of :func:`interpolate_frames`: ``(tq, Dmin)`` of one time -- ``tq = int(rint(t * 256))``
+    in [1, 255] and ``Dmin = max(1, ceil(min_cover * 2**20))``; ``ValueError`` otherwise (a NaN, 0 or
+    1 for ``t``; a ``min_cover`` outside [0, 1])."""
+    t, min_cover = float(t), float(min_cover)
+    tq = int(round(t * 256.0)) if math.isfinite(t) else -1     # Python's round: ties to even, as rint
+    if not 1 <= tq <= 255:
+        raise ValueError(f"interpolate_frames: t = {t} must round to a 256th in [1/256, 255/256] (strictly between "
+                         "the two frames)")
+    if not 0.0 <= min_cover <= 1.0:   # NaN fails
+        raise ValueError(f"interpolate_frames: min_cover = {min_cover} must lie in [0, 1]")
+    return tq, max(1, int(math.ceil(min_cover * INTERP_COVER_UNIT)))
+
+
+def interp_times(t, min_cover: float = 1.0 / 64, max_times: Optional[int] = None):
+    """``(rows, many)`` of ``t``, a float or a sequence of floats: ``rows`` the :func:`interp_params` of
+    every time (``ValueError`` for a time or ``min_cover`` out of range, or an empty or too long
+    sequence), ``many`` whether ``t`` was a sequence."""
+    many = not isinstance(t, (int, float)) and getattr(t, "ndim", 1) != 0   # a numpy / tensor scalar is one time
+    ts = list(t) if many else [t]
+    if not ts or (max_times is not None and len(ts) > max_times):
+        raise ValueError(f"interpolate_frames: t must be a float or a sequence of 1 to {max_times or 'any number of'} "
+                         f"floats, got {len(ts)}")
+    return [interp_params(v, min_cover) for v in ts], many
+
+
+def interpolate_frames(frame1: torch.Tensor, frame2: torch.Tensor, flow_fw: torch.Tensor, flow_bw: torch.Tensor,
+                       t: float, occ_fw: Optional[torch.Tensor] = None, occ_bw: Optional[torch.Tensor] = None,
+                       window: Optional[Tuple[int, int, int, int]] = None, min_cover: float = 1.0 / 64,
+                       return_acc: bool = False):
+    """The frame at time ``t`` between frame 1 (``t = 0``) and frame 2 (``t = 1``) by forward
+    splatting: every pixel of both frames is pushed along a fraction of its own flow, and what meets
+    in a cell is normalised.  Returns ``(frame_t, holes)``: (B, H0, W0, 3) uint8 and (B, H0, W0) bool.
+
+    frame1 / frame2: (B, H0, W0, 3) uint8; flow_fw (1 -> 2) / flow_bw (2 -> 1): (B, H, W, 2) fp32,
+    channel 0 = x; occ_fw / occ_bw: (B, H, W) bool or None, as :func:`fb_consistency` returns them;
+    ``window = (H0, W0, top, left)``: the frame's rectangle inside the flow map (default: the whole
+    map), as in :func:`warp_frames`.
+
+    Exact integer arithmetic after two fp32 operations per axis, so neither the order of a scatter
+    nor the order of atomics can change a bit (the kernels csrc/kernels/interp.hip equal it bit for
+    bit, the accumulator included):
+
+    0. ``tq, Dmin = interp_params(t, min_cover)``.  Direction 0 is (frame1, flow_fw, occ_fw) with
+       the step ``s = fp32(tq) / 256`` and the temporal weight ``a0 = 256 - tq``; direction 1 is
+       (frame2, flow_bw, occ_bw) with ``s = fp32(256 - tq) / 256`` and ``a1 = tq`` (``s`` is exact).
+    1. For the frame pixel (y, x) of direction d with ``f = flow_d[top + y, left + x]``:
+       ``px = float(x) + s * f.x``, ``py = float(y) + s * f.y`` -- the product rounded on its own,
+       then the sum.  The pixel contributes iff ``-1 < px < W0`` and ``-1 < py < H0`` (float
+       comparisons: NaN and +-inf fail).
+    2. ``x0 = floor(px)``, ``qx = int(rint((px - x0) * 16))`` (ties to even, in [0, 16]); y likewise
+       (``train/occlusion.py:range_map``'s steps 2 and 3).
+    3. The four taps ``(x0 + dx, y0 + dy)`` have the integer weights ``w = (dx ? qx : 16 - qx) *
+       (dy ? qy : 16 - qy)``: 256 per source.
+    4. Confidence ``k = 1`` where the pixel's own mask calls it occluded, else ``CONSISTENT = 16``
+       (no mask: 16).  A tap inside the frame adds ``(w*k, w*k*R, w*k*G, w*k*B)`` to the int64 cell
+       ``acc[d, b, ty, tx, 0:4]``: a consistent pixel dominates an occluded one that lands on the
+       same cell, and occluded pixels still fill what nothing else reaches.
+    5. Per frame pixel: ``D = a0 * acc[0].w + a1 * acc[1].w``, ``N_c = a0 * acc[0].c + a1 *
+       acc[1].c``, ``hole = D < Dmin``, ``v_c = (2 * N_c + D) // (2 * D)`` (round half up; in
+       [0, 255] since ``N_c <= 255 * D``), and ``frame_t = hole ? (tq <= 128 ? frame1 : frame2)[y, x]
+       : v``.  A cell covered fully by consistent pixels of both directions has ``D = 2**20``, the
+       unit of ``min_cover``.
+
+    Bound: one contribution is below 2^20 (256 * 16 * 255) and ``H0 * W0 <= 2**30`` is required, so
+    a cell stays below 2^50 and step 5 below 2^61, whatever the flow.  ``CONSISTENT`` and the default
+    ``min_cover`` are placeholders, untuned.  ``return_acc`` appends ``acc`` (2, B, H0, W0, 4) int64."""
+    tq, dmin = interp_params(t, min_cover)
+    assert flow_fw.ndim == 4 and flow_fw.shape[-1] == 2 and flow_fw.dtype == torch.float32, "flow_fw: (B, H, W, 2) fp32"
+    assert flow_bw.shape == flow_fw.shape and flow_bw.dtype == torch.float32, "flow_bw: like flow_fw"
+    B, H, W, _ = flow_fw.shape
+    H0, W0, top, left = (H, W, 0, 0) if window is None else map(int, window)
+    assert H0 >= 1 and W0 >= 1 and top >= 0 and left >= 0 and top + H0 <= H and left + W0 <= W, \
+        "window (H0, W0, top, left) must lie inside the map"
+    assert H0 * W0 <= INTERP_MAX_PIXELS, "H0 * W0 must be at most 2^30 (an int64 cell could overflow)"
+    for name, fr in (("frame1", frame1), ("frame2", frame2)):
+        assert tuple(fr.shape) == (B, H0, W0, 3) and fr.dtype == torch.uint8, f"{name}: (B, H0, W0, 3) uint8"
+    for name, o in (("occ_fw", occ_fw), ("occ_bw", occ_bw)):
+        assert o is None or (tuple(o.shape) == (B, H, W) and o.dtype == torch.bool), f"{name}: (B, H, W) bool"
+    dev = flow_fw.device
+    P = H0 * W0
+    acc = torch.zeros((2, B * P, 4), dtype=torch.int64, device=dev)
+    xs = torch.arange(W0, device=dev, dtype=torch.float32).view(1, 1, W0)
+    ys = torch.arange(H0, device=dev, dtype=torch.float32).view(1, H0, 1)
+    base = (torch.arange(B, device=dev, dtype=torch.int64) * P).view(B, 1, 1)
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    one = torch.ones((), dtype=torch.int64, device=dev)
+    for d, (frame, flow, occ, step) in enumerate(((frame1, flow_fw, occ_fw, tq), (frame2, flow_bw, occ_bw, 256 - tq))):
+        s = torch.tensor(float(step), dtype=torch.float32, device=dev) / 256.0
+        f = flow[:, top:top + H0, left:left + W0]
+        px = xs + s * f[..., 0]
+        py = ys + s * f[..., 1]
+        ok = (px > -1) & (px < W0) & (py > -1) & (py < H0)          # NaN, +-inf fail
+        pxs, pys = torch.where(ok, px, zero), torch.where(ok, py, zero)
+        x0f, y0f = torch.floor(pxs), torch.floor(pys)
+        qx = torch.round((pxs - x0f) * 16.0).to(torch.int64)        # torch.round: ties to even
+        qy = torch.round((pys - y0f) * 16.0).to(torch.int64)
+        x0, y0 = x0f.to(torch.int64), y0f.to(torch.int64)
+        k = CONSISTENT * one if occ is None else torch.where(occ[:, top:top + H0, left:left + W0], one, CONSISTENT * one)
+        rgb1 = torch.cat([torch.ones((B, H0, W0, 1), dtype=torch.int64, device=dev), frame.to(torch.int64)], -1)
+        for dy in (0, 1):
+            for dx in (0, 1):
+                tx, ty = x0 + dx, y0 + dy
+                w = (qx if dx else 16 - qx) * (qy if dy else 16 - qy) * k
+                sel = ok & (tx >= 0) & (tx < W0) & (ty >= 0) & (ty < H0)
+                acc[d].index_add_(0, (base + ty * W0 + tx)[sel], w[sel].unsqueeze(-1) * rgb1[sel])
+    acc = acc.view(2, B, H0, W0, 4)
+    tot = (256 - tq) * acc[0] + tq * acc[1]
+    D = tot[..., :1]
+    holes = D[..., 0] < dmin
+    Ds = torch.where(holes.unsqueeze(-1), one, D)                   # a hole's quotient is not used
+    v = torch.div(2 * tot[..., 1:] + Ds, 2 * Ds, rounding_mode="floor").clamp_(0, 255).to(torch.uint8)
+    frame_t = torch.where(holes.unsqueeze(-1), frame1 if tq <= 128 else frame2, v)
+    return (frame_t, holes, acc) if return_acc else (frame_t, holes)

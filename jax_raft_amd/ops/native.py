@@ -728,6 +728,76 @@ def _augment_pairs(op: str, img1_u8, img2_u8, flow, valid_u8, params, crop):
     return out1, out2, oflow, valid
 
 
+def interpolate_frames(frame1: torch.Tensor, frame2: torch.Tensor, flow_fw: torch.Tensor, flow_bw: torch.Tensor, t,
+                       occ_fw: Optional[torch.Tensor] = None, occ_bw: Optional[torch.Tensor] = None,
+                       window: Optional[Tuple[int, int, int, int]] = None, min_cover: float = 1.0 / 64):
+    """The frame at time ``t`` between two frames by forward splatting, ``(frame_t, holes)``:
+    ``models/reference.py:interpolate_frames`` -- that golden op itself on CPU tensors, the HIP
+    kernels (csrc/kernels/interp.hip, bitwise equal: the clear of the accumulator, the splat of both
+    directions and the resolve, per time, one accumulator reused) on GPU tensors.  frame1 / frame2:
+    (B, H0, W0, 3) uint8, flow_fw / flow_bw: (B, H, W, 2) fp32, occ_fw / occ_bw: (B, H, W) bool or
+    None, ``window = (H0, W0, top, left)`` (default: the whole map).  ``t``: a float, or a sequence
+    of K floats, which returns (K, B, H0, W0, 3) uint8 and (K, B, H0, W0) bool.  Returns fresh
+    tensors.  Wrong arguments raise ``ValueError`` before anything is launched."""
+    from ..models.reference import INTERP_MAX_MAPS, INTERP_MAX_PIXELS, interp_times
+
+    rows, many = interp_times(t, min_cover)
+    for name, f in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
+        if not isinstance(f, torch.Tensor) or f.ndim != 4 or f.shape[-1] != 2 or f.dtype != torch.float32:
+            raise ValueError(f"interpolate_frames: {name} must be (B, H, W, 2) fp32, got "
+                             f"{tuple(f.shape) if isinstance(f, torch.Tensor) else f} {getattr(f, 'dtype', '')}")
+    if flow_fw.shape != flow_bw.shape or flow_fw.device != flow_bw.device:
+        raise ValueError("interpolate_frames: flow_fw and flow_bw must have the same shape and device")
+    B, H, W, _ = flow_fw.shape
+    win = [H, W, 0, 0] if window is None else [int(v) for v in window]
+    if len(win) != 4 or win[0] < 1 or win[1] < 1 or win[2] < 0 or win[3] < 0 or win[2] + win[0] > H or win[3] + win[1] > W:
+        raise ValueError(f"interpolate_frames: window (H0, W0, top, left) = {tuple(win)} must lie inside the {H} x {W} map")
+    H0, W0, top, left = win
+    if B < 1 or H0 * W0 > INTERP_MAX_PIXELS or 2 * B > INTERP_MAX_MAPS:
+        raise ValueError(f"interpolate_frames: sizes (1 <= 2 * B <= {INTERP_MAX_MAPS}, H0 * W0 <= {INTERP_MAX_PIXELS}), "
+                         f"got B = {B}, {H0} x {W0}")
+    dev = flow_fw.device
+    for name, fr in (("frame1", frame1), ("frame2", frame2)):
+        if not isinstance(fr, torch.Tensor) or tuple(fr.shape) != (B, H0, W0, 3) or fr.dtype != torch.uint8:
+            raise ValueError(f"interpolate_frames: {name} must be {(B, H0, W0, 3)} uint8, got "
+                             f"{tuple(fr.shape) if isinstance(fr, torch.Tensor) else fr} {getattr(fr, 'dtype', '')}")
+        if fr.device != dev:
+            raise ValueError(f"interpolate_frames: {name} is on {fr.device}, the flows on {dev}")
+    for name, o in (("occ_fw", occ_fw), ("occ_bw", occ_bw)):
+        if o is None:
+            continue
+        if not isinstance(o, torch.Tensor) or tuple(o.shape) != (B, H, W) or o.dtype != torch.bool:
+            raise ValueError(f"interpolate_frames: {name} must be {(B, H, W)} bool, got "
+                             f"{tuple(o.shape) if isinstance(o, torch.Tensor) else o} {getattr(o, 'dtype', '')}")
+        if o.device != dev:
+            raise ValueError(f"interpolate_frames: {name} is on {o.device}, the flows on {dev}")
+    if not flow_fw.is_cuda:
+        from ..models.reference import interpolate_frames as golden
+
+        res = [golden(frame1, frame2, flow_fw, flow_bw, v, occ_fw, occ_bw, win, min_cover) for v in (t if many else [t])]
+        return (torch.stack([r[0] for r in res]), torch.stack([r[1] for r in res])) if many else res[0]
+    flows = []
+    for f in (flow_fw, flow_bw):
+        f = f.contiguous()
+        flows.append(f.clone() if f.data_ptr() % 8 else f)   # the kernel's 8-byte loads
+    mask = None
+    if occ_fw is not None or occ_bw is not None:   # one mask only: the other direction is all consistent
+        zeros = torch.zeros((B, H, W), dtype=torch.bool, device=dev)
+        mask = torch.stack([zeros if occ_fw is None else occ_fw, zeros if occ_bw is None else occ_bw]).view(torch.uint8)
+    K = len(rows)
+    frame1, frame2 = frame1.contiguous(), frame2.contiguous()
+    par = torch.tensor(rows, dtype=torch.int32).to(dev)
+    acc = torch.empty((2, B, H0, W0, 4), dtype=torch.int64, device=dev)
+    out = torch.empty((K, B, H0, W0, 3), dtype=torch.uint8, device=dev)
+    holes = torch.empty((K, B, H0, W0), dtype=torch.uint8, device=dev)
+    for k in range(K):
+        acc.zero_()
+        ops().interp_splat([frame1, frame2, flows[0], flows[1], mask, acc, par], [B, H, W] + win + [k])
+        ops().interp_resolve([frame1, frame2, acc, par, out[k], holes[k]], [B, H0, W0, k])
+    holes = holes.bool()
+    return (out, holes) if many else (out[0], holes[0])
+
+
 def augment_sums(img1_u8: torch.Tensor, img2_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Exact per-channel integer sums of two batches of (B, Hs, Ws, 3) uint8 GPU frames ->
     int32 (2, B, 3) (launch 1 of :func:`augment_pairs`; the kernel clears ``out`` itself)."""

@@ -39,7 +39,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from ..models.reference import BidirectionalFlow, BidirectionalWarp
+from ..models.reference import INTERP_MAX_TIMES, BidirectionalFlow, BidirectionalInterp, BidirectionalWarp, interp_times
 from ..models.layers import (
     NORM_BATCH,
     NORM_CUSTOM,
@@ -156,6 +156,14 @@ class _PlanState:
     # the flow 1 -> 2) and the photometric sums (2, B, 2) int64 (framewarp.hip)
     warped: Optional[torch.Tensor] = None
     photo: Optional[torch.Tensor] = None
+    # ... with ``interpolate`` (K times): the splat accumulator (2, B, H0, W0, 4) int64, shared by the times, the
+    # device-side (tq, Dmin) rows (K, 2) int32 and the values they currently hold, the frames (K, B, H0, W0, 3)
+    # uint8 and the hole masks (K, B, H0, W0) uint8 (interp.hip)
+    acc: Optional[torch.Tensor] = None
+    par: Optional[torch.Tensor] = None
+    par_vals: Optional[tuple] = None
+    interp: Optional[torch.Tensor] = None
+    holes: Optional[torch.Tensor] = None
 
 
 _VERSION = operator.attrgetter("_version")
@@ -393,11 +401,12 @@ class RaftEngine:
         return (B, H, W, n_iters, bool(all_iters))
 
     def _build_key(self, key: tuple, *, parts: Optional[int] = None, slot: bool = False) -> _PlanState:
-        """Key layout: (B, H, W, n, all)[ + ("u8", H0, W0, pt, pl)][ + ("warm",) | ("bidir",) | ("bidir", "warp")]
-        [ + ("pslot", slot)].  ``parts`` / ``slot``: see :meth:`_build` (a bidirectional plan is one part)."""
+        """Key layout: (B, H, W, n, all)[ + ("u8", H0, W0, pt, pl)][ + ("warm",) | ("bidir",) | ("bidir", "warp") |
+        ("bidir", "interp", K)][ + ("pslot", slot)].  ``parts`` / ``slot``: see :meth:`_build` (a bidirectional plan is one part)."""
         src = tuple(key[6:10]) if len(key) >= 10 and key[5] == "u8" else None
         if "bidir" in key[5:]:
-            return self._build_bidir(*key[:5], src, warp="warp" in key[5:], slot=slot)
+            interp = key[key.index("interp") + 1] if "interp" in key[5:] else 0
+            return self._build_bidir(*key[:5], src, warp="warp" in key[5:], slot=slot, interp=interp)
         return self._build(*key[:5], src=src, warm="warm" in key[5:], parts=parts, slot=slot)
 
     @staticmethod
@@ -1167,15 +1176,17 @@ class RaftEngine:
         return lowering.build(self, B, H, W, n_iters, all_iters, src, warm, parts=parts, slot=slot)
 
     def _build_bidir(self, B: int, H: int, W: int, n_iters: int, all_iters: bool,
-                     src: Optional[Tuple[int, int, int, int]], warp: bool = False, *, slot: bool = False) -> _PlanState:
+                     src: Optional[Tuple[int, int, int, int]], warp: bool = False, *, slot: bool = False,
+                     interp: int = 0) -> _PlanState:
         """Record the plan of ``forward(bidirectional=True)`` (runtime/lowering.py:build_bidir)."""
-        return lowering.build_bidir(self, B, H, W, n_iters, all_iters, src, warp, slot=slot)
+        return lowering.build_bidir(self, B, H, W, n_iters, all_iters, src, warp, slot=slot, interp=interp)
 
     # --------------------------------------------------------------- forward
     @torch.no_grad()
     def forward(self, image1: torch.Tensor, image2: torch.Tensor, num_flow_updates: int = 12,
                 return_all_iters: bool = True, flow_init=None, return_flow_low: bool = False,
-                bidirectional: bool = False, fb_alpha: float = 0.01, fb_beta: float = 0.5, warp: bool = False):
+                bidirectional: bool = False, fb_alpha: float = 0.01, fb_beta: float = 0.5, warp: bool = False,
+                interpolate=None, interp_min_cover: float = 1.0 / 64):
         """All ``num_flow_updates`` upsampled flows (N, B, H, W, 2), as the reference
         returns; ``return_all_iters=False`` returns only the final one, (1, B, H, W, 2).
 
@@ -1195,6 +1206,15 @@ class RaftEngine:
         int64, the masked photometric sums (``models/reference.py:warp_frames``), from one more
         kernel (+ the clear of the sums) at the end of a plan of its own (plan key + "bidir",
         "warp"); every other plan is recorded as before.
+
+        ``bidirectional=True, interpolate=t`` (uint8 frames; ``t`` a float or a sequence of 1 to 8
+        floats strictly between 0 and 1; anything else, ``warp=True`` with it included, is a
+        ``ValueError``) returns :class:`BidirectionalInterp`: the same four fields, then ``frames``
+        (K, B, H0, W0, 3) uint8, the frames at the K times between frame 1 and frame 2 by forward
+        splatting along both flows, and ``holes`` (K, B, H0, W0) bool, the pixels nothing reached
+        (``models/reference.py:interpolate_frames`` with ``min_cover = interp_min_cover``) -- a clear
+        and two kernels per time at the end of a plan of its own (plan key + "bidir", "interp", K).
+        The times live in a device tensor, so other times of the same count build no new plan.
 
         Warm start (video): ``flow_init`` -- a (B, h, w, 2) fp32 tensor in 1/8-resolution
         pixels, channel 0 = x (h, w = the plan's size / 8: the *padded* size for uint8 frames)
@@ -1221,12 +1241,18 @@ class RaftEngine:
         if warp and not bidirectional:
             raise ValueError("forward(warp=True) requires bidirectional=True (the warp is the last op of the "
                              "bidirectional plan)")
+        if interpolate is not None and not bidirectional:
+            raise ValueError("forward(interpolate=t) requires bidirectional=True (the splat uses both flows and "
+                             "their occlusion masks)")
+        if interpolate is not None and warp:
+            raise ValueError("forward(bidirectional=True): interpolate and warp=True exclude each other (one consumer "
+                             "per plan)")
         if bidirectional and self.corr_mode == "on_demand":
             raise NotImplementedError("forward(bidirectional=True): not with corr='on_demand' (the bidirectional "
                                       "plan is lowered for the all-pairs volume only)")
         if bidirectional:
             return self._forward_bidir(image1, image2, num_flow_updates, return_all_iters, flow_init,
-                                       return_flow_low, fb_alpha, fb_beta, warp)
+                                       return_flow_low, fb_alpha, fb_beta, warp, interpolate, interp_min_cover)
         if image1.dtype == torch.uint8 and not self._native_u8:
             a, b, src = self._host_u8(image1, image2)
             res = self.forward(a, b, num_flow_updates, return_all_iters, flow_init, return_flow_low)
@@ -1289,7 +1315,7 @@ class RaftEngine:
         return res
 
     def _forward_bidir(self, image1, image2, n_iters: int, all_iters: bool, flow_init, return_flow_low: bool,
-                       alpha: float, beta: float, warp: bool = False):
+                       alpha: float, beta: float, warp: bool = False, interpolate=None, min_cover: float = 1.0 / 64):
         """``forward(bidirectional=True)`` (weights already repacked where stale)."""
         if flow_init is not None or return_flow_low:
             raise NotImplementedError("forward(bidirectional=True): not with flow_init / return_flow_low (the warm "
@@ -1303,15 +1329,25 @@ class RaftEngine:
         if warp and not (image1.dtype == torch.uint8 and image2.dtype == torch.uint8):
             raise ValueError("forward(bidirectional=True, warp=True) requires uint8 frames (the warp samples the "
                              f"frames as uploaded), got {image1.dtype}")
+        rows = None
+        if interpolate is not None:
+            if not (image1.dtype == torch.uint8 and image2.dtype == torch.uint8):
+                raise ValueError("forward(bidirectional=True, interpolate=t) requires uint8 frames (the splat reads "
+                                 f"the frames as uploaded), got {image1.dtype}")
+            rows = tuple(interp_times(interpolate, min_cover, INTERP_MAX_TIMES)[0])
         # a later flow_init="previous" must not seed from this call's half-batch
         self._last = None
-        key = self._key(image1, image2, n_iters, all_iters) + (("bidir", "warp") if warp else ("bidir",))
+        suffix = ("bidir", "warp") if warp else ("bidir", "interp", len(rows)) if rows else ("bidir",)
+        key = self._key(image1, image2, n_iters, all_iters) + suffix
         st = self._plan_state(key, lambda: self._build_key(key))
         st.inp1.copy_(image1)
         st.inp2.copy_(image2)
         if st.thr_vals != (float(alpha), float(beta)):   # stream-ordered, before the replay
             st.thr.copy_(torch.tensor([alpha, beta], dtype=F32))
             st.thr_vals = (float(alpha), float(beta))
+        if rows and st.par_vals != rows:   # likewise: another time rewrites two ints, and builds nothing
+            st.par.copy_(torch.tensor(rows, dtype=torch.int32))
+            st.par_vals = rows
         self._pre_launch(st)
         fresh = self.copy_output and st.slot_ok
         out = torch.empty_like(st.out) if fresh else st.out
@@ -1326,6 +1362,8 @@ class RaftEngine:
         if warp:   # fresh tensors, copied in stream order
             warped, photo = st.warped.clone(), st.photo.clone()
             return BidirectionalWarp(res[:, :B], res[:, B:], occ[0], occ[1], warped[0], warped[1], photo)
+        if rows:   # likewise
+            return BidirectionalInterp(res[:, :B], res[:, B:], occ[0], occ[1], st.interp.clone(), st.holes.bool())
         return BidirectionalFlow(res[:, :B], res[:, B:], occ[0], occ[1])
 
     @staticmethod

@@ -673,7 +673,7 @@ def build(eng, B: int, H: int, W: int, n_iters: int, all_iters: bool = True, src
 
 
 def build_bidir(eng, B: int, H: int, W: int, n_iters: int, all_iters: bool, src, warp: bool = False,
-                slot: bool = False):
+                slot: bool = False, interp: int = 0):
     """The plan of ``forward(bidirectional=True)``: one part (``split`` would lay ``out`` by part)
     whose loop runs both directions at batch 2B, so the lane decision, the ConvGRU lowering and
     every tile choice are those of loop batch 2B; ``out`` is (N, 2B, H, W, 2) with 1 -> 2 in
@@ -684,10 +684,17 @@ def build_bidir(eng, B: int, H: int, W: int, n_iters: int, all_iters: bool, src,
     ``warp`` (uint8 frames): the same recording followed, on lane 0 after the check, by the
     ``memset`` of the photometric sums and one ``warp_frames`` over both directions
     (framewarp.hip): it samples the frames as uploaded (``inp1`` / ``inp2``) with the same two
-    flows, masked by ``occ``, into the plan's ``warped`` and ``photo``."""
+    flows, masked by ``occ``, into the plan's ``warped`` and ``photo``.
+
+    ``interp = K`` (uint8 frames, not with ``warp``): the same recording followed, on lane 0 after
+    the check, by ``memset`` of the accumulator, ``interp_splat`` and ``interp_resolve`` for each of
+    K times (interp.hip): they splat the frames as uploaded along the same two flows, weighted by
+    ``occ``, into the plan's ``acc`` and resolve it into ``interp[k]`` / ``holes[k]``; the times
+    are rows of the device tensor ``par``."""
     if eng.cp:
         raise NotImplementedError("bidirectional flow is not lowered under context parallelism")
     assert not warp or src is not None, "warp: uint8 frames only"
+    assert not interp or (src is not None and not warp), "interp: uint8 frames only, and not together with warp"
     lanes = (0, 1, 2) if eng.uses_lanes(2 * B, all_iters, parts=1) else (0, 0, 0)
     c = choose(eng, B, 2 * B, H // 8, W // 8, all_iters, lanes, bidir=True, slot=slot)
     st = new_state(eng, B, H, W, n_iters, all_iters, src, 1, 2 * B)
@@ -710,4 +717,14 @@ def build_bidir(eng, B: int, H: int, W: int, n_iters: int, all_iters: bool, src,
         plan.add_memset([st.photo])
         frames = [st.inp2, st.inp1, st.inp1, st.inp2]   # src (fw, bw), own (fw, bw)
         plan.add_warp_frames(frames + flows + [st.occ, st.warped, st.photo] + tail, ints + [2] + offs)
+    if interp:
+        H0, W0 = src[0], src[1]
+        st.acc = torch.zeros((2, B, H0, W0, 4), dtype=torch.int64, device=dev)
+        st.par = torch.zeros((interp, 2), dtype=torch.int32, device=dev)
+        st.interp = torch.zeros((interp, B, H0, W0, 3), dtype=torch.uint8, device=dev)
+        st.holes = torch.zeros((interp, B, H0, W0), dtype=torch.uint8, device=dev)
+        for k in range(interp):
+            plan.add_memset([st.acc])
+            plan.add_interp_splat([st.inp1, st.inp2] + flows + [st.occ, st.acc, st.par] + tail, ints + [k] + offs)
+            plan.add_interp_resolve([st.inp1, st.inp2, st.acc, st.par, st.interp[k], st.holes[k]], [B, H0, W0, k])
     return _finish(eng, st)

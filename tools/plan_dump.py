@@ -98,7 +98,8 @@ def cases():
     od = dict(corr="on_demand")
     variants = [("cold", (), None, None), ("warm", ("warm",), None, None), ("bidir", ("bidir",), None, None),
                 ("u8", U8, None, None), ("u8_bidir_warp", U8 + ("bidir", "warp"), None, None),
-                ("ondemand", (), od, None), ("ondemand_warm", ("warm",), od, None), ("pslot", (), None, 0)]
+                ("ondemand", (), od, None), ("ondemand_warm", ("warm",), od, None), ("pslot", (), None, 0),
+                ("u8_bidir_interp2", U8 + ("bidir", "interp", 2), None, None)]
     for model in FACTORIES:
         for B in (1, 2, 4):
             for all_iters in (True, False):
